@@ -1,7 +1,13 @@
 #!/usr/bin/env python3
 """bench.py — PMCE hot-path throughput on MI355X.
 
-    python bench.py --gpus N --steps K --warmup W
+    python bench.py --gpus N --steps K --warmup W [--dump-outputs DIR] [--full]
+
+A plain run measures the headline figure only: set-up, W warm-up steps, ONE timed window of exactly K steps, the compact JSON line
+(`value` = clips/s of that window, `ms_per_step` = its milliseconds per step).  `--dump-outputs DIR` writes what the timed path returned
+in its last step (mesh, pose, pose3d, pred as float32 .npy; inputs and weights are seeded, so two builds compare output for output).
+`--full` adds everything else described below: the median of `--windows` windows, the sustained window, per-kernel timing and rooflines,
+latency, the host-fed rate, the CPU baseline, the second width, the fp32-pipe variant and the other BASELINE configurations.
 
 N > 1: one process per GPU over RCCL.  Either the caller launches the ranks (`python -m torch.distributed.run
 --nproc-per-node N ... bench.py --gpus N`, RANK/LOCAL_RANK/WORLD_SIZE/MASTER_* in the environment) or, when WORLD_SIZE is
@@ -10,11 +16,11 @@ not set, this script spawns its own N ranks on 127.0.0.1 and relays rank 0's JSO
 A "step" is one pass of the full two-stream hot path (temporal pose encoder + CoEvoDecoder + 6890-vertex upsample +
 J_regressor projection) over one batch of synthetic 16-frame clips per GPU, inputs resident in HBM.  The headline
 configuration is the one BASELINE.json's north_star quotes throughput on — (B=256, T=16, J=17, C=512), BASELINE configs[2]
-batch — and the same line carries a second complete record for C=256, the width every reference config ships
-(`/root/reference/lib/core/config.py:59`).  Rank 0 prints ONE JSON line: whole-job clips/s (median of `--windows` timed
-windows of exactly K steps each, every window bracketed by barrier + synchronize, MAX over ranks), the roofline of the
-dominant kernel class and of the north-star cross-attention kernel (HIP events recorded inside this run on the launch
-stream), small-batch latency, and the oracle's CPU baseline on the host cores (rank 0, N = 1 only).
+batch — and with `--full` the same line carries a second complete record for C=256, the width every reference config ships
+(the reference's lib/core/config.py:59).  Rank 0 prints ONE JSON line: whole-job clips/s (median of `--windows` timed
+windows of exactly K steps each, one window unless `--full`, every window bracketed by barrier + synchronize, MAX over ranks); with
+`--full` also the roofline of the dominant kernel class and of the north-star cross-attention kernel (HIP events recorded inside this
+run on the launch stream), small-batch latency, and the oracle's CPU baseline on the host cores (rank 0).
 """
 from __future__ import annotations
 
@@ -404,8 +410,44 @@ def dominant_kernel_roofline(kernel_ms, launches, B, J, C, gemm_mode, clk_ghz=No
 
 
 # ------------------------------------------------------------------------------------------------------------------
+def bench_inputs(B, J, dev, rank):
+    """The seeded synthetic batches the timed loop rotates through (step k uses batch k % len): the same on every run."""
+    import torch
+    NB = max(1, min(8, (288 << 20) // max(1, B * (16 * 2048 + 16 * J * 2) * 4) + 1))
+    gen = torch.Generator(device=dev)
+    gen.manual_seed(1000 + rank)
+    inputs = []
+    for _ in range(NB):
+        p = torch.rand(B, 16, J, 2, device=dev, generator=gen) * 2 - 1                 # normalised screen coordinates
+        f = torch.relu(torch.randn(B, 16, 2048, device=dev, generator=gen))            # non-negative pooled CNN features
+        inputs.append((p, f))
+    return inputs
+
+
+DUMP_LIMIT = 64 << 20    # bytes of all --dump-outputs files together
+
+
+def dump_outputs(dirname, named):
+    """`named` (name -> tensor with the clip as its first dimension) -> DIRNAME/<name>.npy as float32.  Beyond DUMP_LIMIT bytes in
+    all, the same fixed, seeded sample of clips is kept from every tensor and its clip numbers are written as clip_index.npy."""
+    import numpy as np
+    arrays = {k: v.detach().float().cpu().numpy() for k, v in named.items() if v is not None}
+    n = next(iter(arrays.values())).shape[0]
+    per_clip = sum(a[:1].nbytes for a in arrays.values())
+    keep = max(1, DUMP_LIMIT // max(1, per_clip))
+    if keep < n:
+        idx = np.sort(np.random.default_rng(0).choice(n, keep, replace=False))
+        arrays = {k: a[idx] for k, a in arrays.items()}
+        arrays["clip_index"] = idx.astype(np.float64)
+    os.makedirs(dirname, exist_ok=True)
+    for k, a in arrays.items():
+        np.save(os.path.join(dirname, f"{k}.npy"), np.ascontiguousarray(a))
+    return sorted(arrays)
+
+
 def measure_config(args, dev, rank, world, J, C, B, steps, warmup, windows, full=True):
-    """Throughput + per-kernel-class timing of one configuration.  Returns (record, model, pipe, inputs)."""
+    """Throughput of one configuration; `full` adds the sustained window and the per-kernel-class timing.  Returns (record, model,
+    pipe, inputs, state dict)."""
     import torch
     from pmce_amd import _lib, assets, models, sharding, synth
     from pmce_amd.workload import flops_per_clip
@@ -439,14 +481,8 @@ def measure_config(args, dev, rank, world, J, C, B, steps, warmup, windows, full
 
     # synthetic clips resident in HBM; NB distinct batches are rotated so that the timed loop's inputs (NB x 33.6 MB at
     # B = 256) do not sit in the 256 MB Infinity Cache from one step to the next
-    NB = max(1, min(8, (288 << 20) // max(1, B * (16 * 2048 + 16 * J * 2) * 4) + 1))
-    gen = torch.Generator(device=dev)
-    gen.manual_seed(1000 + rank)
-    inputs = []
-    for _ in range(NB):
-        p = torch.rand(B, 16, J, 2, device=dev, generator=gen) * 2 - 1                 # normalised screen coordinates
-        f = torch.relu(torch.randn(B, 16, 2048, device=dev, generator=gen))            # non-negative pooled CNN features
-        inputs.append((p, f))
+    inputs = bench_inputs(B, J, dev, rank)
+    NB = len(inputs)
 
     depth = 1 if args.single_stream else max(1, args.pipeline_depth)
     pipe = model.pipeline(depth, stagger=(True if args.stagger else False if args.no_stagger else None)).prepare(B) if depth > 1 else None
@@ -492,6 +528,8 @@ def measure_config(args, dev, rank, world, J, C, B, steps, warmup, windows, full
     if pipe is not None:
         out = out.result()
     mesh, pose, pose3d, pred = out
+    if args.dump_outputs and rank == 0:      # the last timed step's results, before any --full record runs more forwards
+        dump_outputs(args.dump_outputs, {"mesh": mesh, "pose": pose, "pose3d": pose3d, "pred": pred})
     partial = torch.stack([pred.abs().sum().double(), mesh.abs().sum().double(),
                            torch.tensor(float(B), device=dev, dtype=torch.float64)])
     total = sharding.reduce_metric_sums(partial)
@@ -517,7 +555,7 @@ def measure_config(args, dev, rank, world, J, C, B, steps, warmup, windows, full
            "per_rank_weights_load_s": [round(r[0], 3) for r in startup], "per_rank_first_step_s": [round(r[1], 3) for r in startup],
            "metric_reduction": {"collective": "all_reduce(SUM) of 3 fp64 partials per rank", "clips_counted": int(total[2].item()),
                                 "backend": (torch.distributed.get_backend() if world > 1 else None)}}
-    if args.sustained_seconds > 0 and not args.single_stream:
+    if full and args.sustained_seconds > 0 and not args.single_stream:
         rec["sustained"] = sustained_record(model, pipe, step, dev, B, world, args.sustained_seconds, clips_per_s, gemm_mode)
     if not full:
         return rec, model, pipe, inputs, sd
@@ -746,7 +784,15 @@ def main():
     ap.add_argument("--gpus", type=int, default=1)
     ap.add_argument("--steps", type=int, default=20)
     ap.add_argument("--warmup", type=int, default=3)
-    ap.add_argument("--windows", type=int, default=5, help="timed windows of --steps steps each; `value` is the median window")
+    ap.add_argument("--windows", type=int, default=None,
+                    help="timed windows of --steps steps each; `value` is the median window (default: 1, with --full 5)")
+    ap.add_argument("--full", action="store_true",
+                    help="measure everything beside the headline figure too: the median of several windows, sustained window, per-kernel "
+                         "timing and rooflines, host-fed rate, latency, CPU baseline, the other width, the fp32-pipe variant and the other "
+                         "BASELINE configurations (a plain run times the headline workload only)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the last step returned (mesh, pose, pose3d, pred) as DIR/<name>.npy, float32, "
+                         "at most 64 MB in all (a fixed, seeded sample of clips beyond that)")
     ap.add_argument("--batch", type=int, default=256, help="clips per GPU per step")
     ap.add_argument("--joints", type=int, default=17)
     ap.add_argument("--embed-dim", type=int, default=512,
@@ -769,12 +815,17 @@ def main():
     ap.add_argument("--gemm-mode", choices=("split_f16", "f32"), default="split_f16",
                     help="the large products as three f16 matrix products each (fp32 accumulate, fp32 accuracy) or on the fp32 matrix "
                          "pipe; both with two streams inside a forward and two batches in flight")
-    ap.add_argument("--detail-file", default=os.path.join(REPO, "bench_detail.json"),
+    ap.add_argument("--detail-file", default=None,
                     help="where rank 0 writes the FULL record (variants, other BASELINE configs, latency, per-kernel tables); stdout carries "
-                         "only the compact record, as its one and last line")
+                         "only the compact record, as its one and last line (default: bench_detail.json in the repository with --full, "
+                         "no file otherwise)")
     ap.add_argument("--dist-check", action="store_true",
                     help="rendezvous + the path's collectives only (no GPU work): what the non-GPU test of the N>1 entry point runs")
     args = ap.parse_args()
+    if args.windows is None:
+        args.windows = 5 if args.full else 1
+    if args.detail_file is None and args.full:
+        args.detail_file = os.path.join(REPO, "bench_detail.json")
 
     if args.gpus > 1 and "WORLD_SIZE" not in os.environ:
         sys.exit(launch_ranks(args.gpus, sys.argv[1:]))
@@ -797,7 +848,7 @@ def main():
     def child_record(extra, cpu_ok, sus=0.0):
         cmd = [sys.executable, os.path.abspath(__file__), "--gpus", "1", "--steps", str(args.steps), "--warmup", str(args.warmup),
                "--windows", str(args.windows), "--batch", str(B), "--joints", str(J),
-               "--pipeline-depth", str(args.pipeline_depth), "--no-variant", "--no-host-fed", "--no-latency",
+               "--pipeline-depth", str(args.pipeline_depth), "--full", "--no-variant", "--no-host-fed", "--no-latency",
                "--cpu-seconds", str(min(args.cpu_seconds, 8.0)), "--sustained-seconds", str(sus), *extra]
         cmd += ["--stagger"] if args.stagger else ["--no-stagger"] if args.no_stagger else []
         cmd += ["--no-cpu-baseline"] if (args.no_cpu_baseline or not cpu_ok) else []
@@ -829,7 +880,7 @@ def main():
         return {"error": (r.stderr or r.stdout)[-400:], "what": what}
 
     other_configs = {}
-    if (args.gpus == 1 and int(os.environ.get("WORLD_SIZE", "1")) == 1 and not args.no_variant and not args.single_stream
+    if (args.full and args.gpus == 1 and int(os.environ.get("WORLD_SIZE", "1")) == 1 and not args.no_variant and not args.single_stream
             and not args.dist_check and C in (256, 512)):
         # BASELINE.json configs[1], [3], [4] (C = 256, the width every reference config ships): decoder-only at batch 64; the
         # 3DPW-sized clip-sharded evaluation (35,515 clips, COCO input J = 19: forward + on-device metrics + the one reduction)
@@ -890,19 +941,19 @@ def main():
             raise SystemExit(f"bench.py: {world} ranks on {ndev} GPU(s) but the process group backend is {dist.get_backend()!r}, not 'nccl' "
                              f"(RCCL); unset PMCE_DIST_BACKEND")
 
-    head, model, pipe, inputs, sd = measure_config(args, dev, rank, world, J, C, B, args.steps, args.warmup, args.windows)
+    head, model, pipe, inputs, sd = measure_config(args, dev, rank, world, J, C, B, args.steps, args.warmup, args.windows, full=args.full)
 
     solo = rank == 0 and world == 1
     host_fed = latency = cpu = None
-    if solo and not args.no_host_fed and not args.single_stream:
+    if args.full and solo and not args.no_host_fed and not args.single_stream:
         host_fed = host_fed_record(model, pipe, dev, B, J, max(5, min(args.steps, 20)))
-    if solo and not args.no_latency:
+    if args.full and solo and not args.no_latency:
         latency = latency_record(model, dev, J)
     vj = model.vj_relation
     del model, pipe, inputs
     torch.cuda.empty_cache()
 
-    if rank == 0 and not args.no_cpu_baseline:      # host-only work last; at N > 1 on rank 0 while the others wait at the final barrier
+    if args.full and rank == 0 and not args.no_cpu_baseline:      # host-only work last; at N > 1 on rank 0 while the others wait at the final barrier
         cpu = cpu_baseline_record(sd, vj, J, C, args.cpu_seconds)
 
     if rank == 0:
@@ -913,13 +964,13 @@ def main():
             "dtype": "f32",
             "dtype_note": ("fp32 operands, results and accumulation; in split_f16 mode each large fp32 product is three f16 MFMA products "
                            "(hi*hi + hi*lo + lo*hi), error vs fp64 at or below the fp32 matrix pipe's"),
-            "data": "synthetic",
-            "config": head["config"], "roofline": head["roofline"], "roofline_cross_attention": head["roofline_cross_attention"],
+            "data": "synthetic", "full": args.full,
+            "config": head["config"], "roofline": head.get("roofline"), "roofline_cross_attention": head.get("roofline_cross_attention"),
             "roofline_attention": head.get("roofline_attention"),
             "cpu_baseline": cpu, "windows": head["windows"], "sustained": head.get("sustained"), "host_fed": host_fed, "latency": latency,
             f"variant_c{256 if C == 512 else 512}": variant, "variant_f32_pipe": variant_f32,
-            "kernel_ms_per_step": head["kernel_ms_per_step"], "launches_per_step": head["launches_per_step"],
-            "kernel_ms_total_single_stream": head["kernel_ms_total_single_stream"],
+            "kernel_ms_per_step": head.get("kernel_ms_per_step"), "launches_per_step": head.get("launches_per_step"),
+            "kernel_ms_total_single_stream": head.get("kernel_ms_total_single_stream"),
             "ref_equiv_tflops": head["ref_equiv_tflops"], "outputs_finite": head["outputs_finite"],
             "per_rank_clips_s": head["per_rank_clips_s"], "per_rank_ms_per_step": head["per_rank_ms_per_step"],
             "per_rank_sustained_clock_ghz": head.get("per_rank_sustained_clock_ghz"),
@@ -986,7 +1037,7 @@ def compact_record(full: dict, detail_file: str | None) -> dict:
             others[k] = next((v[f] for f in ("clips_per_s", "clips_per_s_incl_metrics", "windows_per_s") if f in v), "error")
     lat = full.get("latency") or {}
     rec = {k: full.get(k) for k in ("metric", "value", "unit", "n_gpus", "steps", "warmup", "ms_per_step", "higher_is_better", "scaling",
-                                    "vs_baseline", "dtype", "data")}
+                                    "vs_baseline", "dtype", "data", "full")}
     rec.update({"config": cfg, "roofline": roofline, "cpu_baseline": cpu,
                 "sustained": _pick(full.get("sustained"), ("value", "seconds", "steps", "ratio_to_value", "clock_ghz_end")),
                 "roofline_cross_attention": ca, "outputs_finite": full.get("outputs_finite"),
@@ -1015,7 +1066,8 @@ def emit(full: dict, detail_file: str | None):
         except OSError as e:
             sys.stderr.write(f"[bench] could not write {detail_file}: {e}\n")
             detail_file = None
-    sys.stderr.write(f"[bench] full record ({len(json.dumps(full))} bytes): {detail_file}\n")
+    if detail_file:
+        sys.stderr.write(f"[bench] full record ({len(json.dumps(full))} bytes): {detail_file}\n")
     _print_record(json.dumps(compact_record(full, detail_file)))
 
 

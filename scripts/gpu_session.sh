@@ -25,7 +25,7 @@ quick)
   echo "pytest quick exit: $?"; tail -n 40 $O/pytest_quick.log
   ;;
 bench)
-  timeout 1200 python bench.py --detail-file $O/bench_detail.json > $O/bench_line.json 2> $O/bench.err
+  timeout 1200 python bench.py --full --detail-file $O/bench_detail.json > $O/bench_line.json 2> $O/bench.err
   echo "bench exit: $?"; echo "stdout: $(wc -l < $O/bench_line.json) line(s), $(wc -c < $O/bench_line.json) bytes"; cat $O/bench_line.json
   python scripts/show_bench.py $O/bench_detail.json 2>/dev/null | head -120 || head -c 3000 $O/bench_detail.json
   tail -n 5 $O/bench.err | grep -v amdgpu.ids || true

@@ -169,3 +169,26 @@ def test_rank_cpu_slices_and_shared_weights(monkeypatch, tmp_path):
     win, _ = bench.class_work("gemm_lifter", 256, 17, 512, streaming=True)
     assert 0.75 * full < win < full                                            # 5 of 6 blocks, no imgfeat_embed
     assert bench.class_work("gemm_gru_in", 256, 17, 512, streaming=True)[0] < 0.4 * bench.class_work("gemm_gru_in", 256, 17, 512)[0]   # layer 1 only
+
+
+def test_dump_outputs_keeps_a_fixed_sample_within_the_limit(tmp_path, monkeypatch):
+    """--dump-outputs: float32 .npy per output; past DUMP_LIMIT bytes the same seeded clips of every output, their numbers in clip_index."""
+    import numpy as np
+    import torch
+    bench = _bench_module()
+    g = torch.Generator().manual_seed(0)
+    named = {"mesh": torch.randn(40, 30, 3, generator=g), "pose": torch.randn(40, 5, 3, generator=g, dtype=torch.float64), "none": None}
+    assert bench.dump_outputs(str(tmp_path / "all"), named) == ["mesh", "pose"]
+    assert np.array_equal(np.load(tmp_path / "all" / "mesh.npy"), named["mesh"].numpy())
+    assert np.load(tmp_path / "all" / "pose.npy").dtype == np.float32
+    per_clip = (30 + 5) * 3 * 4
+    monkeypatch.setattr(bench, "DUMP_LIMIT", 10 * per_clip)
+    for d in ("s1", "s2"):
+        assert bench.dump_outputs(str(tmp_path / d), named) == ["clip_index", "mesh", "pose"]
+    idx = np.load(tmp_path / "s1" / "clip_index.npy")
+    assert idx.dtype == np.float64 and len(idx) == 10 and len(set(idx.tolist())) == 10 and np.all(np.diff(idx) > 0)
+    mesh = np.load(tmp_path / "s1" / "mesh.npy")
+    assert mesh.dtype == np.float32 and mesh.nbytes + np.load(tmp_path / "s1" / "pose.npy").nbytes <= 10 * per_clip
+    assert np.array_equal(mesh, named["mesh"].numpy()[idx.astype(np.int64)])
+    for n in ("clip_index", "mesh", "pose"):
+        assert np.array_equal(np.load(tmp_path / "s1" / f"{n}.npy"), np.load(tmp_path / "s2" / f"{n}.npy"))

@@ -70,12 +70,12 @@ def test_collectives_on_rccl():
     assert d["rows"] == np.arange(12, dtype=np.float32).reshape(4, 3).tolist() and d["rows_device"].startswith("cuda")
 
 
-def test_bench_two_ranks_on_this_box():
+def test_bench_two_ranks_on_this_box(tmp_path):
     env = dict(os.environ, PMCE_BENCH_SHARE_GPU="1", PMCE_DIST_BACKEND="gloo")
     for k in ("RANK", "LOCAL_RANK", "WORLD_SIZE", "MASTER_ADDR", "MASTER_PORT"):
         env.pop(k, None)
-    r = subprocess.run([sys.executable, "bench.py", "--gpus", "2", "--steps", "3", "--warmup", "1", "--windows", "2", "--batch",
-                        "32", "--embed-dim", "256", "--cpu-seconds", "2", "--sustained-seconds", "1", "--detail-file", "/tmp/pmce_bench_detail_2r.json"],
+    r = subprocess.run([sys.executable, "bench.py", "--gpus", "2", "--full", "--steps", "3", "--warmup", "1", "--windows", "2", "--batch",
+                        "32", "--embed-dim", "256", "--cpu-seconds", "2", "--sustained-seconds", "1", "--detail-file", str(tmp_path / "detail_2r.json")],
                        cwd=REPO, env=env, capture_output=True, text=True, timeout=900)
     assert r.returncode == 0, r.stderr[-3000:]
     assert r.stdout.count("\n") == 1 and len(r.stdout) < 8192, r.stdout[:2000]     # ONE compact line is all of stdout
@@ -104,15 +104,15 @@ def test_bench_two_ranks_over_rccl_when_two_gpus_are_visible():
     assert d["outputs_finite"] and min(d["per_rank_clips_s"]) > 0.5 * max(d["per_rank_clips_s"])
 
 
-def test_bench_eight_ranks_dry_run_prints_one_compact_line():
+def test_bench_eight_ranks_dry_run_prints_one_compact_line(tmp_path):
     """Dry run of the line the driver's 8-GPU scaling run will parse: eight ranks share this box's one device (gloo for the
     metric reduction), tiny batch.  Asserted: stdout is ONE line under 8 KB that parses, n_gpus 8, eight entries per per-rank list, roofline
     and cpu_baseline present; the detail file holds the full record.  No scaling number is read off this."""
     env = dict(os.environ, PMCE_BENCH_SHARE_GPU="1", PMCE_DIST_BACKEND="gloo")
     for k in ("RANK", "LOCAL_RANK", "WORLD_SIZE", "MASTER_ADDR", "MASTER_PORT"):
         env.pop(k, None)
-    detail = "/tmp/pmce_bench_detail_8r.json"
-    r = subprocess.run([sys.executable, "bench.py", "--gpus", "8", "--steps", "2", "--warmup", "1", "--windows", "1", "--batch", "8",
+    detail = str(tmp_path / "detail_8r.json")
+    r = subprocess.run([sys.executable, "bench.py", "--gpus", "8", "--full", "--steps", "2", "--warmup", "1", "--windows", "1", "--batch", "8",
                         "--embed-dim", "256", "--cpu-seconds", "1", "--sustained-seconds", "1", "--detail-file", detail],
                        cwd=REPO, env=env, capture_output=True, text=True, timeout=1200)
     assert r.returncode == 0, r.stderr[-3000:]

@@ -281,3 +281,45 @@ def test_eval_sharded_mpii3d_flavour_vs_metrics_oracle():
     print({k: got[k] for k in ("MPJPE", "PA-MPJPE", "ACCEL")}, "oracle", {k: ref[k] for k in ("MPJPE", "PA_MPJPE", "ACCEL")})
     for k, r in (("MPJPE", "MPJPE"), ("PA-MPJPE", "PA_MPJPE"), ("ACCEL", "ACCEL")):
         assert abs(got[k] - ref[r]) < 2e-3, (k, got[k], ref[r])
+
+
+def test_bench_plain_run_times_its_steps_and_dumps_the_last_step(tmp_path):
+    """`bench.py` without --full: one timed window of exactly --steps steps and nothing beside the headline figure; --dump-outputs writes
+    what the timed path returned in its last step, the same bits on a second run, and those are the forward of that step's seeded input."""
+    import importlib.util
+    from pmce_amd import assets, models, synth
+    B, J, C, steps, warmup = 8, 17, 256, 3, 2
+    env = dict(os.environ, PMCE_SYNTHETIC_BASE_DATA="1")
+    for k in ("RANK", "LOCAL_RANK", "WORLD_SIZE", "MASTER_ADDR", "MASTER_PORT"):
+        env.pop(k, None)
+    dumps = []
+    for run in range(2):
+        out = tmp_path / f"run{run}"
+        r = subprocess.run([sys.executable, "bench.py", "--gpus", "1", "--steps", str(steps), "--warmup", str(warmup), "--batch", str(B),
+                            "--embed-dim", str(C), "--dump-outputs", str(out)], cwd=REPO, env=env, capture_output=True, text=True, timeout=600)
+        assert r.returncode == 0, r.stderr[-3000:]
+        assert r.stdout.count("\n") == 1, r.stdout[:2000]
+        d = json.loads(r.stdout)
+        assert d["steps"] == steps and d["warmup"] == warmup and d["full"] is False and d["outputs_finite"]
+        assert d["ms_per_step"] > 0 and abs(d["value"] - B / (d["ms_per_step"] * 1e-3)) < 0.01 * d["value"] + 0.2
+        assert d["roofline"] is None and d["cpu_baseline"] is None and d["detail_file"] is None
+        dumps.append({n: np.load(out / f"{n}.npy") for n in ("mesh", "pose", "pose3d", "pred")})
+    a, b = dumps
+    assert a["mesh"].shape == (B, 6890, 3) and a["pose"].shape == a["pose3d"].shape == (B, J, 3) and a["pred"].shape[0] == B
+    for n in a:
+        assert a[n].dtype == np.float32 and np.isfinite(a[n]).all() and np.array_equal(a[n], b[n]), n
+    spec = importlib.util.spec_from_file_location("bench_mod", osp.join(REPO, "bench.py"))
+    bench = importlib.util.module_from_spec(spec)
+    spec.loader.exec_module(bench)
+    dev = torch.device("cuda:0")
+    assets.allow_synthetic_base_data()
+    model = models.PMCE.get_model(J, C, 3)
+    model.load_state_dict(synth.make_state_dict(synth.pmce_spec(J, C, 3), seed=123))
+    model.set_j_regressor(assets.load_j_regressor("h36m"))
+    model = model.to(dev)
+    model.set_gemm_mode("split_f16")                          # bench.py's default --gemm-mode
+    inputs = bench.bench_inputs(B, J, dev, 0)
+    p, f = inputs[(warmup + steps - 1) % len(inputs)]          # the last timed step's batch
+    got = [t.cpu().numpy() for t in model.forward_with_joints(p, f)]
+    for n, g in zip(("mesh", "pose", "pose3d", "pred"), got):
+        assert np.array_equal(a[n], g), (n, float(np.abs(a[n] - g).max()))
