@@ -2,33 +2,37 @@
 // and the acceleration error, replacing the reference's per-batch D2H copy of [B,6890,3] meshes + numpy
 // (data/PW3D/dataset.py:269-282 compute_both_err, :351-462 evaluate; lib/coord_utils.py:151-173 rigid_align,
 // :218-245 compute_error_accel).  The mesh part is a 165 KB/sample streaming reduction (HBM-bound); the 14-joint
-// Procrustes alignment (3x3 SVD) runs in fp64 on one lane per sample.
+// Procrustes alignment (3x3 SVD by one-sided Jacobi) runs in fp64 on one lane per sample.
 #include "common.hpp"
 
 #define MAXJ 32
 
-// cyclic Jacobi eigen-decomposition of a symmetric 3x3 matrix (fp64): S = V diag(w) V^T, columns of V = eigenvectors
-__device__ void jacobi3(double S[3][3], double V[3][3], double w[3]) {
+// SVD of a 3x3 matrix by one-sided (Hestenes) Jacobi in fp64: the columns of A = H*V are rotated in pairs until they are mutually
+// orthogonal; their norms are then the singular values and V holds the right singular vectors.  H itself is worked on, never H^T H:
+// squaring H squares its condition number and leaves a small singular value known only to sqrt(eps) of the largest, which is what a
+// thin, planar or collinear joint set (in a plane that is not axis-aligned) needs to be resolved.  On return A[:,c] = H V[:,c].
+__device__ void jacobi_svd3(double A[3][3], double V[3][3]) {
   for (int i = 0; i < 3; ++i)
     for (int j = 0; j < 3; ++j) V[i][j] = (i == j) ? 1.0 : 0.0;
-  for (int sweep = 0; sweep < 24; ++sweep) {
-    const double off = S[0][1] * S[0][1] + S[0][2] * S[0][2] + S[1][2] * S[1][2];
-    if (off < 1e-300) break;
+  for (int sweep = 0; sweep < 30; ++sweep) {
+    bool rotated = false;
     for (int p = 0; p < 2; ++p)
       for (int q = p + 1; q < 3; ++q) {
-        if (fabs(S[p][q]) < 1e-300) continue;
-        const double theta = (S[q][q] - S[p][p]) / (2.0 * S[p][q]);
-        const double t = (theta >= 0 ? 1.0 : -1.0) / (fabs(theta) + sqrt(theta * theta + 1.0));
-        const double c = 1.0 / sqrt(t * t + 1.0), s = t * c;
-        for (int k = 0; k < 3; ++k) {  // S <- S J
-          const double skp = S[k][p], skq = S[k][q];
-          S[k][p] = c * skp - s * skq;
-          S[k][q] = s * skp + c * skq;
+        double al = 0.0, be = 0.0, ga = 0.0;
+        for (int k = 0; k < 3; ++k) {
+          al += A[k][p] * A[k][p];
+          be += A[k][q] * A[k][q];
+          ga += A[k][p] * A[k][q];
         }
-        for (int k = 0; k < 3; ++k) {  // S <- J^T S
-          const double spk = S[p][k], sqk = S[q][k];
-          S[p][k] = c * spk - s * sqk;
-          S[q][k] = s * spk + c * sqk;
+        if (!(ga * ga > 1e-30 * al * be)) continue;  // columns orthogonal to 1e-15 (or one of them zero, or NaN): nothing to do
+        rotated = true;
+        const double zeta = (be - al) / (2.0 * ga);
+        const double t = (zeta >= 0 ? 1.0 : -1.0) / (fabs(zeta) + sqrt(zeta * zeta + 1.0));
+        const double c = 1.0 / sqrt(t * t + 1.0), s = t * c;
+        for (int k = 0; k < 3; ++k) {  // A <- A J
+          const double akp = A[k][p], akq = A[k][q];
+          A[k][p] = c * akp - s * akq;
+          A[k][q] = s * akp + c * akq;
         }
         for (int k = 0; k < 3; ++k) {  // V <- V J
           const double vkp = V[k][p], vkq = V[k][q];
@@ -36,8 +40,108 @@ __device__ void jacobi3(double S[3][3], double V[3][3], double w[3]) {
           V[k][q] = s * vkp + c * vkq;
         }
       }
+    if (!rotated) break;
   }
-  for (int i = 0; i < 3; ++i) w[i] = S[i][i];
+}
+
+// a <- a / |a|; false (a untouched) when |a|^2 is not above floor2, i.e. a is zero, rounding noise or NaN
+__device__ bool normalise3(double a[3], double floor2) {
+  const double n2 = a[0] * a[0] + a[1] * a[1] + a[2] * a[2];
+  if (!(n2 > floor2)) return false;
+  const double inv = 1.0 / sqrt(n2);
+  for (int k = 0; k < 3; ++k) a[k] *= inv;
+  return true;
+}
+
+// r <- the coordinate axis that is furthest from the unit vector u, made orthogonal to u and normalised
+__device__ void any_orthogonal3(const double u[3], double r[3]) {
+  const int k = (fabs(u[0]) <= fabs(u[1]) && fabs(u[0]) <= fabs(u[2])) ? 0 : (fabs(u[1]) <= fabs(u[2]) ? 1 : 2);
+  for (int i = 0; i < 3; ++i) r[i] = (i == k ? 1.0 : 0.0) - u[k] * u[i];
+  normalise3(r, 0.0);
+}
+
+__device__ void cross3(const double a[3], const double b[3], double c[3]) {
+  c[0] = a[1] * b[2] - a[2] * b[1];
+  c[1] = a[2] * b[0] - a[0] * b[2];
+  c[2] = a[0] * b[1] - a[1] * b[0];
+}
+
+// PA-MPJPE of one sample: mean_j || c R P_j + t - G_j || with the similarity (c, R, t) of rigid_transform_3D (coord_utils.py:151-167).
+// H = U diag(s) V^T, R = V U^T.  U and V are built as right-handed frames (third column = cross product of the first two), so R is a
+// proper rotation by construction and no determinant test is needed; the third singular value s2 = u2^T H v2 then carries the sign:
+// it is negative exactly when the reference flips its last singular pair (:158-161).  The error VALUE is continuous in the inputs
+// also where R is not unique (collinear sets: any rotation about the line), so the arbitrary choices below do not show in it.
+__device__ double procrustes_pa(const double (*P)[3], const double (*G)[3], int n_eval) {
+  double cA[3] = {0, 0, 0}, cB[3] = {0, 0, 0};
+  for (int e = 0; e < n_eval; ++e)
+    for (int k = 0; k < 3; ++k) {
+      cA[k] += P[e][k];
+      cB[k] += G[e][k];
+    }
+  for (int k = 0; k < 3; ++k) {
+    cA[k] /= n_eval;
+    cB[k] /= n_eval;
+  }
+  double H[3][3] = {{0, 0, 0}, {0, 0, 0}, {0, 0, 0}};
+  double varP = 0.0;
+  for (int e = 0; e < n_eval; ++e)
+    for (int i = 0; i < 3; ++i) {
+      const double a = P[e][i] - cA[i];
+      varP += a * a;
+      for (int j = 0; j < 3; ++j) H[i][j] += a * (G[e][j] - cB[j]);
+    }
+  varP /= n_eval;
+  for (int i = 0; i < 3; ++i)
+    for (int j = 0; j < 3; ++j) H[i][j] /= n_eval;
+  double A[3][3], Vm[3][3], nrm[3];
+  for (int i = 0; i < 3; ++i)
+    for (int j = 0; j < 3; ++j) A[i][j] = H[i][j];
+  jacobi_svd3(A, Vm);
+  for (int c = 0; c < 3; ++c) nrm[c] = A[0][c] * A[0][c] + A[1][c] * A[1][c] + A[2][c] * A[2][c];
+  int ord[3] = {0, 1, 2};  // descending singular values
+  for (int i = 0; i < 2; ++i)
+    for (int j = i + 1; j < 3; ++j)
+      if (nrm[ord[j]] > nrm[ord[i]]) {
+        const int t = ord[i];
+        ord[i] = ord[j];
+        ord[j] = t;
+      }
+  double u[3][3], v[3][3];  // u[c], v[c]: the c-th left / right singular vector
+  for (int c = 0; c < 2; ++c)
+    for (int i = 0; i < 3; ++i) {
+      u[c][i] = A[i][ord[c]];
+      v[c][i] = Vm[i][ord[c]];
+    }
+  cross3(v[0], v[1], v[2]);
+  if (!normalise3(u[0], 0.0)) {  // H = 0 (all targets or all predictions identical): every frame serves
+    u[0][0] = 1.0;
+    u[0][1] = u[0][2] = 0.0;
+  }
+  // Gram-Schmidt of the second column; below 1e-15 of the first it is rounding noise (collinear set), and any unit vector orthogonal
+  // to u0 serves as well
+  const double d01 = u[0][0] * u[1][0] + u[0][1] * u[1][1] + u[0][2] * u[1][2];
+  for (int i = 0; i < 3; ++i) u[1][i] -= d01 * u[0][i];
+  if (!normalise3(u[1], 1e-30 * nrm[ord[0]])) any_orthogonal3(u[0], u[1]);
+  cross3(u[0], u[1], u[2]);
+  double ssum = 0.0;  // s0 + s1 + s2, s_c = u_c^T H v_c
+  for (int c = 0; c < 3; ++c)
+    for (int i = 0; i < 3; ++i) ssum += u[c][i] * (H[i][0] * v[c][0] + H[i][1] * v[c][1] + H[i][2] * v[c][2]);
+  double Rm[3][3];  // R = V U^T
+  for (int i = 0; i < 3; ++i)
+    for (int j = 0; j < 3; ++j) Rm[i][j] = v[0][i] * u[0][j] + v[1][i] * u[1][j] + v[2][i] * u[2][j];
+  const double cs = ssum / varP;
+  double tt[3];
+  for (int i = 0; i < 3; ++i) tt[i] = -cs * (Rm[i][0] * cA[0] + Rm[i][1] * cA[1] + Rm[i][2] * cA[2]) + cB[i];
+  double pa = 0.0;
+  for (int e = 0; e < n_eval; ++e) {
+    double d2 = 0.0;
+    for (int i = 0; i < 3; ++i) {
+      const double a = cs * (Rm[i][0] * P[e][0] + Rm[i][1] * P[e][1] + Rm[i][2] * P[e][2]) + tt[i] - G[e][i];
+      d2 += a * a;
+    }
+    pa += sqrt(d2);
+  }
+  return pa / n_eval;
 }
 
 // One workgroup per sample.
@@ -111,83 +215,7 @@ __global__ __launch_bounds__(256) void sample_errors_kernel(const float* __restr
     }
   }
   out_mpjpe[b] = (float)(mp / n_eval);
-  // ---- Procrustes (coord_utils.py:151-167) ----
-  double cA[3] = {0, 0, 0}, cB[3] = {0, 0, 0};
-  for (int e = 0; e < n_eval; ++e)
-    for (int k = 0; k < 3; ++k) {
-      cA[k] += P[e][k];
-      cB[k] += G[e][k];
-    }
-  for (int k = 0; k < 3; ++k) {
-    cA[k] /= n_eval;
-    cB[k] /= n_eval;
-  }
-  double H[3][3] = {{0, 0, 0}, {0, 0, 0}, {0, 0, 0}};
-  double varP = 0.0;
-  for (int e = 0; e < n_eval; ++e)
-    for (int i = 0; i < 3; ++i) {
-      const double a = P[e][i] - cA[i];
-      varP += a * a;
-      for (int j = 0; j < 3; ++j) H[i][j] += a * (G[e][j] - cB[j]);
-    }
-  varP /= n_eval;
-  for (int i = 0; i < 3; ++i)
-    for (int j = 0; j < 3; ++j) H[i][j] /= n_eval;
-  // SVD of H through the eigen-decomposition of H^T H:  H = U diag(sv) Vm^T
-  double S[3][3], Vm[3][3], w[3];
-  for (int i = 0; i < 3; ++i)
-    for (int j = 0; j < 3; ++j) S[i][j] = H[0][i] * H[0][j] + H[1][i] * H[1][j] + H[2][i] * H[2][j];
-  jacobi3(S, Vm, w);
-  int ord[3] = {0, 1, 2};  // descending eigenvalues
-  for (int i = 0; i < 2; ++i)
-    for (int j = i + 1; j < 3; ++j)
-      if (w[ord[j]] > w[ord[i]]) {
-        const int t = ord[i];
-        ord[i] = ord[j];
-        ord[j] = t;
-      }
-  double sv[3], U[3][3], Vs[3][3];
-  for (int c = 0; c < 3; ++c) {
-    sv[c] = sqrt(fmax(w[ord[c]], 0.0));
-    for (int i = 0; i < 3; ++i) Vs[i][c] = Vm[i][ord[c]];
-  }
-  for (int c = 0; c < 2; ++c) {
-    const double inv = sv[c] > 1e-300 ? 1.0 / sv[c] : 0.0;
-    for (int i = 0; i < 3; ++i) U[i][c] = (H[i][0] * Vs[0][c] + H[i][1] * Vs[1][c] + H[i][2] * Vs[2][c]) * inv;
-  }
-  if (sv[2] > 1e-12 * sv[0]) {
-    for (int i = 0; i < 3; ++i) U[i][2] = (H[i][0] * Vs[0][2] + H[i][1] * Vs[1][2] + H[i][2] * Vs[2][2]) / sv[2];
-  } else {  // rank-deficient: complete the basis
-    U[0][2] = U[1][0] * U[2][1] - U[2][0] * U[1][1];
-    U[1][2] = U[2][0] * U[0][1] - U[0][0] * U[2][1];
-    U[2][2] = U[0][0] * U[1][1] - U[1][0] * U[0][1];
-  }
-  double Rm[3][3];
-  auto build_R = [&]() {  // R = V U^T
-    for (int i = 0; i < 3; ++i)
-      for (int j = 0; j < 3; ++j) Rm[i][j] = Vs[i][0] * U[j][0] + Vs[i][1] * U[j][1] + Vs[i][2] * U[j][2];
-  };
-  build_R();
-  const double det = Rm[0][0] * (Rm[1][1] * Rm[2][2] - Rm[1][2] * Rm[2][1]) - Rm[0][1] * (Rm[1][0] * Rm[2][2] - Rm[1][2] * Rm[2][0]) +
-                     Rm[0][2] * (Rm[1][0] * Rm[2][1] - Rm[1][1] * Rm[2][0]);
-  if (det < 0) {  // reflection: flip the last singular pair (coord_utils.py:158-161)
-    sv[2] = -sv[2];
-    for (int i = 0; i < 3; ++i) Vs[i][2] = -Vs[i][2];
-    build_R();
-  }
-  const double cs = (sv[0] + sv[1] + sv[2]) / varP;
-  double tt[3];
-  for (int i = 0; i < 3; ++i) tt[i] = -cs * (Rm[i][0] * cA[0] + Rm[i][1] * cA[1] + Rm[i][2] * cA[2]) + cB[i];
-  double pa = 0.0;
-  for (int e = 0; e < n_eval; ++e) {
-    double d2 = 0.0;
-    for (int i = 0; i < 3; ++i) {
-      const double a = cs * (Rm[i][0] * P[e][0] + Rm[i][1] * P[e][1] + Rm[i][2] * P[e][2]) + tt[i] - G[e][i];
-      d2 += a * a;
-    }
-    pa += sqrt(d2);
-  }
-  out_pampjpe[b] = (float)(pa / n_eval);
+  out_pampjpe[b] = (float)procrustes_pa(P, G, n_eval);
 }
 
 // acceleration error per sample (coord_utils.py:218-245 as used by dataset.py:415-429): the first and last sample of

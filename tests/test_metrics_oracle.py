@@ -51,6 +51,30 @@ def test_rigid_align_known_answers():
     assert np.allclose(acc, np.sqrt(3.0))
 
 
+def test_rigid_align_degenerate_known_answers():
+    """Exact similarities of planar and collinear sets (in a plane / on a line that is not axis-aligned): the alignment error is 0.
+    H then has one / two zero singular values and R is fixed only up to the reflection branch / a rotation about the line, but the
+    error is not affected.  The GPU tests of degenerate joint sets (tests/test_gpu_metrics_edges.py) lean on the oracle exactly here.
+    Bounds: the oracle gives 7e-13 mm (planar) and 4e-6 mm (collinear: two singular values known to sqrt(eps) of the first)."""
+    rng = np.random.default_rng(2)
+
+    def rot():
+        q, _ = np.linalg.qr(rng.standard_normal((3, 3)))
+        return q * np.sign(np.linalg.det(q))
+
+    for kind, bound in (("planar", 1e-9), ("collinear", 1e-4)):
+        worst = 0.0
+        for n in (3, 14, 17, 19) * 125:
+            A = rng.standard_normal((n, 3)) * np.array([200.0, 450.0, 120.0])
+            A[:, 2 if kind == "planar" else slice(1, 3)] = 0.0
+            A = A @ rot().T
+            for mirror in (1.0, -1.0):                                  # a mirrored planar / collinear set is still a rotated copy of itself
+                B = rng.uniform(0.5, 2.0) * (A * np.array([mirror, 1.0, 1.0])) @ rot().T + rng.standard_normal(3) * 100.0
+                worst = max(worst, np.sqrt(((MO.rigid_align(A, B) - B) ** 2).sum(1)).mean())
+        print(f"rigid_align on exact similarities of {kind} sets: worst error {worst:.2e} mm (bound {bound:g})")
+        assert worst < bound
+
+
 def test_h36m_flavour_matches_reference(golden):
     """Human36M.evaluate / compute_both_err (data/Human36M/dataset.py:611-623,715-848): camera-4 filter, annotated GT joints."""
     from make_golden_metrics_h36m import gt_joints, layout
