@@ -460,6 +460,32 @@ int pmce_assemble_windows_f32(const float* pose, const float* feat, const int* w
 int pmce_prepare_pose2d_f32(const float* kp, int kp_stride, const int* shape, float* out, int L, int J0, int n_extra, int lhip,
                             int rhip, int lsho, int rsho, pmce_stream_t stream);
 
+/* ---------------------------------------------------------------------------------------------------------
+ * The demo's weak-perspective camera fit (main/run_demo.py:134-173 optimize_cam_param on lib/models/project_net.py:6-16
+ * OptimzeCamLayer): per window, `steps` Adam steps (betas 0.9 / 0.999, eps 1e-8, moments zeroed per window) on cam = (s, tx, ty)
+ * against the L1 loss mean_jc |(scale * joints3d[w][j][c] + cam[1 + c]) * cam[0] * crop_size/2 + crop_size/2 - target2d[w][j][c]|,
+ * j < n_fit, c < 2.  _f32 / _f64: the compute type, which is also the type of EVERY floating-point buffer of the call.
+ *   joints3d[W][n_fit][3], target2d[W][n_target][2] (n_target >= n_fit: the demo passes 19 rows and fits the first 17), n_fit in 1..32;
+ *   step_table[steps][2] = (lr_t / (1 - 0.9^t), sqrt(1 - 0.999^t)) for t = 1..steps, computed by the caller in double (it carries the
+ *     learning-rate schedule; pmce_amd.camera.step_table makes the demo's: 0.1, 0.05 after loop index 100, 0.001 after 200);
+ *   chains: windows seq_offsets[s] .. seq_offsets[s + 1] - 1 (int32[S + 1], monotone, first 0, last W) form one chain - its first window
+ *     starts from init[s] (init[S][3]), each later one from its predecessor's result, as the demo does along a tracklet (its project_net
+ *     is created once, :245).  The table is given twice: seq_offsets_host is validated here, seq_offsets is the same table in device
+ *     memory.  Both NULL (then S == W): every window is its own chain and starts from init[w];
+ *   cam[W][3] = the camera after `steps` updates, loss[W] = the L1 loss at that camera;
+ *   optional (all or none): bbox[W][4] = (x, y, w, h), img_w, img_h > 0 -> orig_cam[W][4] = (sx, sy, tx, ty), the demo's
+ *     convert_crop_cam_to_orig_img (run_demo.py:49-67); otherwise NULL, NULL and img_w = img_h = 0.
+ * One wave per chain, results bit-identical whatever W, S and the window's place in the batch.  fp64 follows the reference's fp64 run to
+ * rounding; fp32 is the reference's dtype, where the loop is chaotic (sign gradients) and agrees as the reference's fp32 does with its fp64. */
+int pmce_camfit_f32(const float* joints3d, const float* target2d, const float* init, const int* seq_offsets_host,
+                    const int* seq_offsets, const float* step_table, float* cam, float* loss, const float* bbox, float* orig_cam, int W,
+                    int S, int n_fit, int n_target, int steps, double scale, double crop_size, double img_w, double img_h,
+                    pmce_stream_t stream);
+int pmce_camfit_f64(const double* joints3d, const double* target2d, const double* init, const int* seq_offsets_host,
+                    const int* seq_offsets, const double* step_table, double* cam, double* loss, const double* bbox, double* orig_cam,
+                    int W, int S, int n_fit, int n_target, int steps, double scale, double crop_size, double img_w, double img_h,
+                    pmce_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif

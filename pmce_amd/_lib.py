@@ -16,6 +16,7 @@ _i = C.c_int
 _l = C.c_longlong
 _s = C.c_void_p      # hipStream_t
 _fl = C.c_float
+_d = C.c_double
 
 # name -> argtypes  (restype is int unless listed in _RESTYPES); mirrors include/pmce_hip.h one-to-one
 PROTOTYPES = {
@@ -117,6 +118,8 @@ PROTOTYPES = {
     "pmce_accel_error_f32": [_f, _f, _f, _f, _i, _i, _s],
     "pmce_assemble_windows_f32": [_f, _f, _f, _f, _f, _i, _i, _i, _s],
     "pmce_prepare_pose2d_f32": [_f, _i, _f, _f, _i, _i, _i, _i, _i, _i, _i, _s],
+    "pmce_camfit_f32": [_f, _f, _f, C.POINTER(C.c_int), _f, _f, _f, _f, _f, _f, _i, _i, _i, _i, _i, _d, _d, _d, _d, _s],
+    "pmce_camfit_f64": [_f, _f, _f, C.POINTER(C.c_int), _f, _f, _f, _f, _f, _f, _i, _i, _i, _i, _i, _d, _d, _d, _d, _s],
 }
 _RESTYPES = {
     "pmce_last_error_string": C.c_char_p,

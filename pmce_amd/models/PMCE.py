@@ -77,6 +77,18 @@ class PMCE(HipModuleBase):
         return self._guarded(lambda eng: self._run(pose2d, img_feat, True, eng))
 
     @torch.no_grad()
+    def forward_with_camera(self, pose2d, img_feat, target2d, **fit_kwargs):
+        """(cam_mesh, cam_pose, pose3d, pred_joints_mm, cam, loss): :meth:`forward_with_joints` followed, on the same stream, by the demo's
+        weak-perspective camera fit of the regressed joints to ``target2d`` [B, >= rows, >= 2] (``camera.fit_camera``, whose keyword
+        arguments pass through; main/run_demo.py:134-173).  Needs ``set_j_regressor(assets.load_j_regressor("coco"))`` or any regressor
+        with <= 32 rows.  The regressed joints are millimetres (J @ (mesh * 1000)) while the demo fits metres (run_demo.py:146), so the
+        fit runs with ``scale=1e-3``: that differs from regressing in metres by one fp32 rounding of each input coordinate."""
+        from .. import camera
+        mesh, pose, pose3d, pred = self.forward_with_joints(pose2d, img_feat)
+        fit_kwargs.setdefault("scale", 1e-3)
+        return (mesh, pose, pose3d, pred) + tuple(camera.fit_camera(pred, target2d, **fit_kwargs))
+
+    @torch.no_grad()
     def forward_checked(self, pose2d, img_feat, want_joints: bool = False):
         """``forward`` / ``forward_with_joints`` with the "rerun" behaviour whatever the module's policy, saying whether it happened:
         returns (outputs, reran)."""
