@@ -165,12 +165,24 @@ int pmce_stream_precompute(pmce_model* m, const float* pose2d_frames, const floa
                            void* ws, size_t ws_bytes, pmce_stream_t stream);
 int pmce_stream_forward(pmce_model* m, const float* x0, const float* gi0, const int* win, int W, int L, float* cam_mesh,
                         float* cam_pose, float* pose3d, float* pred_pose, void* ws, size_t ws_bytes, pmce_stream_t stream);
+/* The same with the demo's middle-frame override (main/run_demo.py:340-344: j2d_processing overwrites frame 8 of every window in place
+ * before normalize_screen_coordinates, so the model sees that frame's 500-px crop coordinates, screen-normalised).  x0_mid[L,J,C] is a
+ * second window-independent token table: the x0 output of a pmce_stream_precompute over (the poses each frame has AS THE MIDDLE of its
+ * window - pmce_demo_targets_f32's mid_pose2d ordered by frame -, feat_frames); token rows (w, 8, j) are taken from it, every other row
+ * and the whole GRU branch from x0 / gi0.  x0_mid == x0 gives pmce_stream_forward's bits. */
+int pmce_stream_forward_mid(pmce_model* m, const float* x0, const float* x0_mid, const float* gi0, const int* win, int W, int L,
+                            float* cam_mesh, float* cam_pose, float* pose3d, float* pred_pose, void* ws, size_t ws_bytes,
+                            pmce_stream_t stream);
 /* building blocks of the above */
 int pmce_window_tokens_f32(const float* x0, const int* win, const float* tpos, const float* w2, const float* b2, float eps2,
                            float* X, float* XN, int W, int L, int T, int J, int C, pmce_stream_t stream);
 /* XN written pre-split (see pmce_ln_chain_ex_f32). */
 int pmce_window_tokens_ex_f32(const float* x0, const int* win, const float* tpos, const float* w2, const float* b2, float eps2,
                            float* X, float* XN, int W, int L, int T, int J, int C, int xn_split, pmce_stream_t stream);
+/* Rewrites the W * J rows (w, t_mid, j) of X / XN (filled by pmce_window_tokens_ex_f32) from x0_mid: X = x0_mid[m(w),j,:] + tpos[t_mid,:],
+ * XN = LN(X), m(w) = start + t_mid (start when start == end); the arithmetic of pmce_window_tokens_ex_f32. */
+int pmce_window_mid_tokens_f32(const float* x0_mid, const int* win, const float* tpos, const float* w2, const float* b2, float eps2,
+                               float* X, float* XN, int W, int L, int T, int J, int C, int t_mid, int xn_split, pmce_stream_t stream);
 int pmce_window_rows_f32(const float* src, const int* win, float* dst, int W, int L, int T, int ncols, pmce_stream_t stream);
 
 /* enable != 0 (default): pmce_forward / pmce_decoder_forward run the image-feature branch (GRU, AdaLN parameters) and the
@@ -485,6 +497,21 @@ int pmce_camfit_f64(const double* joints3d, const double* target2d, const double
                     const int* seq_offsets, const double* step_table, double* cam, double* loss, const double* bbox, double* orig_cam,
                     int W, int S, int n_fit, int n_target, int steps, double scale, double crop_size, double img_w, double img_h,
                     pmce_stream_t stream);
+
+/* ---------------------------------------------------------------------------------------------------------
+ * The demo's per-window target preparation (main/run_demo.py:340-344), one launch for a window table win[W,2] over per-frame pixel
+ * keypoints kp[L,J0,kp_stride] (x, y first; COCO-17 in the demo).  With m = start + t_mid (start when start == end) the window's middle
+ * frame: pelvis and neck are appended (run_demo.py:116-128), get_bbox and process_bbox(aspect_ratio = 1, scale = box_scale) give
+ * bbox[W,4] = (x, y, w, h) in the reference's float32 operation order (lib/coord_utils.py:45-90), j2d_processing's rot = 0 affine gives
+ * target2d[W,J0+2,2] in pixels of the crop_size x crop_size crop (lib/aug_utils.py:51-64), and mid_pose2d[W,J0+2,2] =
+ * target2d / img_w * 2 - (1, img_h / img_w) is what the reference's in-place write leaves the model to see as that window's frame t_mid.
+ * valid[W] (int32) is 0 where process_bbox returns None (w * h <= 0, or a box less than a pixel wide or high) or a keypoint is not finite:
+ * bbox, target2d and mid_pose2d of such a window are NaN. */
+int pmce_demo_targets_f32(const float* kp, int kp_stride, const int* win, float* bbox, float* target2d, float* mid_pose2d, int* valid,
+                          int W, int L, int J0, int t_mid, float img_w, float img_h, float crop_size, float box_scale, int lhip, int rhip,
+                          int lsho, int rsho, pmce_stream_t stream);
+/* pose_windows[W,T,J,2] (pmce_assemble_windows_f32's out_pose): row t_mid of every window replaced by mid_pose2d[W,J,2]. */
+int pmce_demo_override_mid_f32(float* pose_windows, const float* mid_pose2d, int W, int T, int J, int t_mid, pmce_stream_t stream);
 
 #ifdef __cplusplus
 }

@@ -42,6 +42,8 @@ PROTOTYPES = {
     "pmce_coevo_block_forward": [C.c_void_p, _i, _f, _f, _f, _f, _f, _i, _f, C.c_size_t, _s],
     "pmce_stream_precompute": [C.c_void_p, _f, _f, _i, _f, _f, _f, C.c_size_t, _s],
     "pmce_stream_forward": [C.c_void_p, _f, _f, _f, _i, _i, _f, _f, _f, _f, _f, C.c_size_t, _s],
+    "pmce_stream_forward_mid": [C.c_void_p, _f, _f, _f, _f, _i, _i, _f, _f, _f, _f, _f, C.c_size_t, _s],
+    "pmce_window_mid_tokens_f32": [_f, _f, _f, _f, _f, _fl, _f, _f, _i, _i, _i, _i, _i, _i, _i, _s],
     "pmce_window_tokens_f32": [_f, _f, _f, _f, _f, _fl, _f, _f, _i, _i, _i, _i, _i, _s],
     "pmce_window_tokens_ex_f32": [_f, _f, _f, _f, _f, _fl, _f, _f, _i, _i, _i, _i, _i, _i, _s],
     "pmce_window_rows_f32": [_f, _f, _f, _i, _i, _i, _i, _s],
@@ -120,6 +122,8 @@ PROTOTYPES = {
     "pmce_prepare_pose2d_f32": [_f, _i, _f, _f, _i, _i, _i, _i, _i, _i, _i, _s],
     "pmce_camfit_f32": [_f, _f, _f, C.POINTER(C.c_int), _f, _f, _f, _f, _f, _f, _i, _i, _i, _i, _i, _d, _d, _d, _d, _s],
     "pmce_camfit_f64": [_f, _f, _f, C.POINTER(C.c_int), _f, _f, _f, _f, _f, _f, _i, _i, _i, _i, _i, _d, _d, _d, _d, _s],
+    "pmce_demo_targets_f32": [_f, _i, _f, _f, _f, _f, _f, _i, _i, _i, _i, _fl, _fl, _fl, _fl, _i, _i, _i, _i, _s],
+    "pmce_demo_override_mid_f32": [_f, _f, _i, _i, _i, _i, _s],
 }
 _RESTYPES = {
     "pmce_last_error_string": C.c_char_p,

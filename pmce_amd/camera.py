@@ -2,7 +2,8 @@
 
 Replaces ``optimize_cam_param`` (reference main/run_demo.py:134-173: 300 Adam steps through autograd per window on the three
 numbers of lib/models/project_net.py's ``OptimzeCamLayer``) and ``convert_crop_cam_to_orig_img`` (run_demo.py:49-67).  The
-target preparation (``get_bbox`` / ``process_bbox`` / ``j2d_processing``) stays with the caller.
+targets (``get_bbox`` / ``process_bbox`` / ``j2d_processing``) are prepared on the device by ``pmce_amd.demo.demo_targets``;
+``demo.run_tracklet`` runs targets, forward and this fit for a whole tracklet.  A caller with targets of its own passes them here.
 
     cam, loss = fit_camera(joints3d_m, target2d)                          # W independent windows
     cam, loss = fit_camera(joints3d_m, target2d, chain=True)              # one tracklet: each window starts from the previous result

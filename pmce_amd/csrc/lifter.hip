@@ -636,6 +636,75 @@ extern "C" int pmce_window_tokens_f32(const float* x0, const int* win, const flo
   return pmce_window_tokens_ex_f32(x0, win, tpos, w2, b2, eps2, X, XN, W, L, T, J, C, 0, stream);
 }
 
+// Streaming, the demo's middle-frame override (main/run_demo.py:340-344 overwrites frame T/2 of every window before the model sees it): the
+// W * J token rows (w, t_mid, j) of X / XN, already filled by pmce_window_tokens_ex_f32, are rewritten from a SECOND per-frame table x0_mid
+// ("this frame as the middle of its window"):  X = x0_mid[m(w), j, :] + tpos[t_mid, :],  XN = LN(X; w2, b2, eps2),  m(w) = start + t_mid, or
+// start when start == end.  One wavefront per row with ln_chain_kernel's lane layout, loads, additions and LayerNorm: a window whose x0_mid
+// row equals its x0 row gets the bits it already had.
+template <int C>
+__global__ __launch_bounds__(256) void window_mid_tokens_kernel(const float* __restrict__ x0_mid, const int* __restrict__ win,
+                                                                const float* __restrict__ tpos, const float* __restrict__ w2,
+                                                                const float* __restrict__ b2, float eps2, float* __restrict__ X,
+                                                                float* __restrict__ XN, int W, int nframes, int T, int J, int t_mid,
+                                                                int xn_split) {
+  constexpr int NV = C / 64;
+  const int lane = threadIdx.x & 63;
+  const long long r = (long long)blockIdx.x * 4 + (threadIdx.x >> 6);  // (w, j)
+  if (r >= (long long)W * J) return;
+  const long long w = r / J;
+  const int j = (int)(r % J);
+  const int s0 = win[2 * w], e0 = win[2 * w + 1];
+  const int fr = min(max(s0 == e0 ? s0 : s0 + t_mid, 0), nframes - 1);
+  const long long src = (long long)fr * J + j, row = (w * T + t_mid) * J + j;
+  float v[NV];
+#pragma unroll
+  for (int i4 = 0; i4 < NV / 4; ++i4) {
+    const f32x4 t = __builtin_nontemporal_load(reinterpret_cast<const f32x4*>(x0_mid + src * C + i4 * 256 + lane * 4));
+#pragma unroll
+    for (int i = 0; i < 4; ++i) v[i4 * 4 + i] = t[i];
+  }
+  const float* a = tpos + (long long)t_mid * C;
+#pragma unroll
+  for (int i4 = 0; i4 < NV / 4; ++i4) {
+    const f32x4 t = *reinterpret_cast<const f32x4*>(a + i4 * 256 + lane * 4);
+#pragma unroll
+    for (int i = 0; i < 4; ++i) v[i4 * 4 + i] += t[i];
+  }
+#pragma unroll
+  for (int i4 = 0; i4 < NV / 4; ++i4) {
+    f32x4 t;
+#pragma unroll
+    for (int i = 0; i < 4; ++i) t[i] = v[i4 * 4 + i];
+    __builtin_nontemporal_store(t, reinterpret_cast<f32x4*>(X + row * C + i4 * 256 + lane * 4));
+  }
+  ln_regs<C>(v, w2, b2, eps2, lane);
+#pragma unroll
+  for (int i4 = 0; i4 < NV / 4; ++i4) {
+    f32x4 t;
+#pragma unroll
+    for (int i = 0; i < 4; ++i) t[i] = v[i4 * 4 + i];
+    if (xn_split) store4_split_f16(XN + row * C, i4 * 256 + lane * 4, t);
+    else *reinterpret_cast<f32x4*>(XN + row * C + i4 * 256 + lane * 4) = t;
+  }
+}
+
+extern "C" int pmce_window_mid_tokens_f32(const float* x0_mid, const int* win, const float* tpos, const float* w2, const float* b2,
+                                          float eps2, float* X, float* XN, int W, int L, int T, int J, int C, int t_mid, int xn_split,
+                                          hipStream_t stream) {
+  PMCE_REQUIRE(C == 256 || C == 512, "window_mid_tokens: C must be 256 or 512");
+  PMCE_REQUIRE(x0_mid && win && tpos && w2 && b2 && X && XN && W > 0 && L > 0 && T > 0 && J > 0 && t_mid >= 0 && t_mid < T,
+               "window_mid_tokens: bad args");
+  const long long rows = (long long)W * J;
+  const unsigned grid = (unsigned)((rows + 3) / 4);
+  if (C == 256)
+    hipLaunchKernelGGL((window_mid_tokens_kernel<256>), dim3(grid), dim3(256), 0, stream, x0_mid, win, tpos, w2, b2, eps2, X, XN, W, L,
+                       T, J, t_mid, xn_split);
+  else
+    hipLaunchKernelGGL((window_mid_tokens_kernel<512>), dim3(grid), dim3(256), 0, stream, x0_mid, win, tpos, w2, b2, eps2, X, XN, W, L,
+                       T, J, t_mid, xn_split);
+  return pmce_check_launch("window_mid_tokens");
+}
+
 // Streaming: time-major gather of per-frame rows:  dst[t][w][:] = src[frame(w,t)][:]   (ncols % 4 == 0)
 __global__ __launch_bounds__(256) void window_rows_kernel(const float* __restrict__ src, const int* __restrict__ win,
                                                           float* __restrict__ dst, int W, int L, int T, int ncols) {

@@ -1226,6 +1226,8 @@ int pmce_forward(pmce_model* m, const float* pose2d, const float* img_feat, floa
 int pmce_window_tokens_f32(const float* x0, const int* win, const float* tpos, const float* w2, const float* b2, float eps2,
                            float* X, float* XN, int W, int L, int T, int J, int C, hipStream_t stream);
 int pmce_window_rows_f32(const float* src, const int* win, float* dst, int W, int L, int T, int ncols, hipStream_t stream);
+int pmce_window_mid_tokens_f32(const float* x0_mid, const int* win, const float* tpos, const float* w2, const float* b2, float eps2,
+                               float* X, float* XN, int W, int L, int T, int J, int C, int t_mid, int xn_split, hipStream_t stream);
 
 int pmce_stream_precompute(pmce_model* m, const float* pose2d_frames, const float* feat_frames, int L, float* x0, float* gi0,
                            void* ws, size_t ws_bytes, pmce_stream_t stream) {
@@ -1252,7 +1254,8 @@ int pmce_stream_precompute(pmce_model* m, const float* pose2d_frames, const floa
   return PMCE_OK;
 }
 
-static int stream_forward_impl(pmce_model* m, const float* x0, const float* gi0, const int* win, int W, int L,
+// x0_mid != null: the demo's middle-frame override - token rows (w, T/2, j) come from that second per-frame table
+static int stream_forward_impl(pmce_model* m, const float* x0, const float* x0_mid, const float* gi0, const int* win, int W, int L,
                                float* cam_mesh, float* cam_pose, float* pose3d, float* pred_pose, LifterWs& lw, DecoderWs& dw,
                                hipStream_t stream) {
   const bool single = !two_streams(m);
@@ -1271,6 +1274,9 @@ static int stream_forward_impl(pmce_model* m, const float* x0, const float* gi0,
   if (!single) PMCE_TRY(ev_record(m->ev_join, m->side, "stream_forward join"));
   RUN(P_LN, pmce_window_tokens_ex_f32(x0, win, m->w.tpos, m->w.blk[1][0].norm1_w, m->w.blk[1][0].norm1_b, 1e-6f, lw.X, lw.XN, W, L,
                                    T, m->J, m->C, pk(m), stream));
+  if (x0_mid)
+    RUN(P_LN, pmce_window_mid_tokens_f32(x0_mid, win, m->w.tpos, m->w.blk[1][0].norm1_w, m->w.blk[1][0].norm1_b, 1e-6f, lw.X, lw.XN, W,
+                                         L, T, m->J, m->C, T / 2, pk(m), stream));
   PMCE_TRY(lifter_rest(m, pose3d, W, lw, stream));
   RUN(P_MISC, pmce_div_scalar_f32(pose3d, dw.JM, (long long)W * m->J * 3, 1000.0f, stream));
   PMCE_TRY(mark_lifter_done(m, stream));
@@ -1282,8 +1288,9 @@ static int stream_forward_impl(pmce_model* m, const float* x0, const float* gi0,
   return PMCE_OK;
 }
 
-int pmce_stream_forward(pmce_model* m, const float* x0, const float* gi0, const int* win, int W, int L, float* cam_mesh,
-                        float* cam_pose, float* pose3d, float* pred_pose, void* ws, size_t ws_bytes, pmce_stream_t stream) {
+static int stream_forward_entry(pmce_model* m, const float* x0, const float* x0_mid, const float* gi0, const int* win, int W, int L,
+                                float* cam_mesh, float* cam_pose, float* pose3d, float* pred_pose, void* ws, size_t ws_bytes,
+                                pmce_stream_t stream) {
   PMCE_TRY(check_ws(m, W, ws, ws_bytes));
   SinkGuard sink_guard;
   PMCE_REQUIRE(m->has_lifter && m->has_decoder, "stream_forward: needs both lifter and decoder tensors");
@@ -1296,8 +1303,20 @@ int pmce_stream_forward(pmce_model* m, const float* x0, const float* gi0, const 
   carve_lifter(c, m, W, lw);
   carve_decoder(c, m, W, dw);
   if (two_streams(m)) PMCE_TRY(ensure_side(m));
-  const int rc = stream_forward_impl(m, x0, gi0, win, W, L, cam_mesh, cam_pose, pose3d, pred_pose, lw, dw, stream);
+  const int rc = stream_forward_impl(m, x0, x0_mid, gi0, win, W, L, cam_mesh, cam_pose, pose3d, pred_pose, lw, dw, stream);
   return rc == PMCE_OK ? rc : fail_after_fork(m, stream, rc);
+}
+
+int pmce_stream_forward(pmce_model* m, const float* x0, const float* gi0, const int* win, int W, int L, float* cam_mesh,
+                        float* cam_pose, float* pose3d, float* pred_pose, void* ws, size_t ws_bytes, pmce_stream_t stream) {
+  return stream_forward_entry(m, x0, nullptr, gi0, win, W, L, cam_mesh, cam_pose, pose3d, pred_pose, ws, ws_bytes, stream);
+}
+
+int pmce_stream_forward_mid(pmce_model* m, const float* x0, const float* x0_mid, const float* gi0, const int* win, int W, int L,
+                            float* cam_mesh, float* cam_pose, float* pose3d, float* pred_pose, void* ws, size_t ws_bytes,
+                            pmce_stream_t stream) {
+  PMCE_REQUIRE(x0_mid, "stream_forward_mid: x0_mid is null (pmce_stream_forward is the call without a middle-frame table)");
+  return stream_forward_entry(m, x0, x0_mid, gi0, win, W, L, cam_mesh, cam_pose, pose3d, pred_pose, ws, ws_bytes, stream);
 }
 
 int pmce_model_wait_lifter(pmce_model* m, pmce_stream_t stream) {

@@ -1,0 +1,225 @@
+"""The reference demo's per-person stretch (main/run_demo.py:323-367) on the GPU: a tracklet's per-frame keypoints and image features
+in, what the demo saves per person out - ``pred_cam``, ``mesh``, ``bboxes`` (``frame_ids`` are the caller's).
+
+    model.set_j_regressor(assets.load_j_regressor("coco"))
+    out = demo.run_tracklet(model, keypoints[N,17,>=2], features[N,2048], img_wh=(1920, 1080))
+    outs = demo.run_tracklets(model, [(kp_a, feat_a), (kp_b, feat_b)], img_wh=(1920, 1080))     # batches filled across people
+
+Per frame k the demo builds one window (``streaming.demo_window_list``), prepares the fit target from the window's middle frame
+(csrc/demo_prep.hip: add_pelvis_and_neck, get_bbox, process_bbox, j2d_processing), runs the model on the window and fits the
+weak-perspective camera, one ``project_net`` persisting along the tracklet (``camera.fit_camera`` chains).
+
+The middle-frame override.  run_demo.py:343 hands ``nj2d[seq_len//2].numpy()`` - a view that shares memory with the window - to
+j2d_processing, which writes the 500-px crop coordinates back in place (lib/aug_utils.py:57-59); only then is the window
+screen-normalised (:344).  Frame 8 of every window therefore enters the model as the normalisation of its crop coordinates, the other
+15 frames as what they are.  ``middle_frame="reference"`` (default) reproduces that, ``"clean"`` feeds every frame its plain
+normalisation.  Frame reuse survives it: every frame is the middle of exactly one window of the demo's list, so a second per-frame token
+table ("as middle frame") serves row 8 of every window (``streaming.precompute_mid_frames``, pmce_stream_forward_mid).
+"""
+from __future__ import annotations
+
+from collections import OrderedDict
+
+import numpy as np
+import torch
+
+from . import _lib, camera, staging, streaming
+from .config import FEAT_DIM, SEQLEN
+
+BOX_SCALE = 1.25                   # process_bbox(bbox, aspect_ratio=1.0, scale=1.25), run_demo.py:342
+CROP = camera.DEMO_CROP            # virtual_crop_size, run_demo.py:236
+MIDDLE_FRAME = ("reference", "clean")
+
+
+def demo_windows_device(lengths, device) -> torch.Tensor:
+    """``streaming.demo_window_list`` of each tracklet, offset into the concatenated frame table, built ON the device (int32 [sum N, 2]):
+    window k is the one frame k is the middle of.  No upload, so the host never waits for the stream."""
+    h = SEQLEN // 2
+    parts, off = [], 0
+    for n in lengths:
+        k = torch.arange(n, device=device, dtype=torch.int32)
+        single = (k < h) | (k > n - h)                       # the first 8 and the last 7 frames: one frame repeated
+        parts.append(torch.stack([torch.where(single, k, k - h), torch.where(single, k, k + (h - 1))], 1) + off)
+        off += n
+    return torch.cat(parts).contiguous()
+
+
+def demo_targets(keypoints: torch.Tensor, windows, img_wh, crop_size: float = CROP, box_scale: float = BOX_SCALE,
+                 joints_name=staging.COCO_JOINTS):
+    """keypoints[L, J0, >=2] pixels (GPU) + windows int[W,2] (host table, or int32 tensor on the GPU) ->
+    (bbox[W,4] (x, y, w, h), target2d[W,J0+2,2] crop pixels, mid_pose2d[W,J0+2,2], valid int32[W]) of every window's middle frame:
+    pmce_demo_targets_f32.  ``valid`` is 0 where the reference's process_bbox returns None; that window's rows are NaN."""
+    lib = _lib.load()
+    kp = keypoints.to(torch.float32).contiguous()
+    L, J0, D = kp.shape
+    dev = kp.device
+    w = windows.contiguous() if streaming._device_table(windows) else \
+        torch.as_tensor(streaming.validate_windows(windows, L), device=dev).contiguous()
+    W = w.shape[0]
+    bbox = torch.empty(W, 4, device=dev, dtype=torch.float32)
+    target = torch.empty(W, J0 + 2, 2, device=dev, dtype=torch.float32)
+    mid = torch.empty(W, J0 + 2, 2, device=dev, dtype=torch.float32)
+    valid = torch.empty(W, device=dev, dtype=torch.int32)
+    if W == 0:
+        return bbox, target, mid, valid
+    idx = [joints_name.index(n) for n in ('L_Hip', 'R_Hip', 'L_Shoulder', 'R_Shoulder')]
+    _lib.check(lib.pmce_demo_targets_f32(_lib.ptr(kp), D, _lib.ptr(w), _lib.ptr(bbox), _lib.ptr(target), _lib.ptr(mid), _lib.ptr(valid),
+                                         W, L, J0, SEQLEN // 2, float(img_wh[0]), float(img_wh[1]), float(crop_size), float(box_scale),
+                                         *idx, _lib.current_stream()), "demo_targets")
+    return bbox, target, mid, valid
+
+
+def override_middle(pose_windows: torch.Tensor, mid_pose2d: torch.Tensor) -> torch.Tensor:
+    """In place: row SEQLEN // 2 of every assembled window pose_windows[W,16,J,2] := mid_pose2d[W,J,2] (pmce_demo_override_mid_f32)."""
+    W, T, J, _ = pose_windows.shape
+    if tuple(mid_pose2d.shape) != (W, J, 2) or pose_windows.dtype != torch.float32 or mid_pose2d.dtype != torch.float32:
+        raise ValueError(f"override_middle: float32 [W,16,J,2] and [W,J,2] expected (got {tuple(pose_windows.shape)}, {tuple(mid_pose2d.shape)})")
+    if W:
+        _lib.check(_lib.load().pmce_demo_override_mid_f32(_lib.ptr(pose_windows), _lib.ptr(mid_pose2d.contiguous()), W, T, J, T // 2,
+                                                          _lib.current_stream()), "demo_override_mid")
+    return pose_windows
+
+
+def _as_device(x, dev, what):
+    t = x if isinstance(x, torch.Tensor) else torch.from_numpy(np.ascontiguousarray(x))
+    if not t.dtype.is_floating_point:
+        raise ValueError(f"{what} must be floating point (got {t.dtype})")
+    return t.to(device=dev, dtype=torch.float32, non_blocking=True)
+
+
+@torch.no_grad()
+def run_tracklets(model, tracklets, img_wh, chain_across: bool = False, middle_frame: str = "reference", reuse: bool = True,
+                  batch: int = 256, init=None, seed: int = 0, precision: str = "f32", check: bool = True):
+    """``run_tracklet`` for several tracklets [(keypoints[N_i,17,>=2], features[N_i,2048]), ...] of one video (one ``img_wh``) at once:
+    the per-frame tables are concatenated and the window tables offset, so that batches of ``batch`` windows are filled across people;
+    each tracklet is its own camera chain (``init`` [S,3], default seeded uniform) - or, with ``chain_across=True``, all tracklets in
+    order are ONE chain (``init`` [1,3]), which is what the reference's single persistent project_net does between persons.
+    Returns one dict per tracklet (views of the shared result tensors)."""
+    if middle_frame not in MIDDLE_FRAME:
+        raise ValueError(f"middle_frame must be one of {MIDDLE_FRAME} (got {middle_frame!r})")
+    if len(tracklets) == 0:
+        return []
+    if len(img_wh) != 2 or not (float(img_wh[0]) > 0 and float(img_wh[1]) > 0):
+        raise ValueError(f"img_wh must be (width, height), both positive (got {img_wh!r})")
+    if float(img_wh[0]) != int(img_wh[0]) or float(img_wh[1]) != int(img_wh[1]):
+        raise ValueError(f"img_wh must be whole pixels (got {img_wh!r})")
+    if int(batch) < 1:
+        raise ValueError(f"batch must be >= 1 (got {batch})")
+    if getattr(model, "_j_regressor", None) is None:
+        raise _lib.PmceError("demo.run_tracklet needs a joint regressor: model.set_j_regressor(assets.load_j_regressor('coco')) first")
+    J0 = model.num_joint - 2
+    lengths = []
+    for i, (kp, feat) in enumerate(tracklets):
+        if kp.ndim != 3 or kp.shape[1] != J0 or kp.shape[2] < 2:
+            raise ValueError(f"tracklet {i}: keypoints must be [N, {J0}, >= 2] for this model of {model.num_joint} joints (got {tuple(kp.shape)})")
+        n = int(kp.shape[0])
+        if feat.ndim != 2 or tuple(feat.shape) != (n, FEAT_DIM):
+            raise ValueError(f"tracklet {i}: features must be [N = {n}, {FEAT_DIM}] (got {tuple(feat.shape)})")
+        if n < SEQLEN:
+            raise ValueError(f"tracklet {i}: the demo's window list needs at least {SEQLEN} frames (got {n})")
+        lengths.append(n)
+    eng = model._ensure_packed()
+    dev = eng.device
+    kps = [_as_device(kp, dev, "keypoints")[..., :2] for kp, _ in tracklets]
+    feats = [_as_device(feat, dev, "features") for _, feat in tracklets]
+    kp_all = (kps[0] if len(kps) == 1 else torch.cat(kps)).contiguous()
+    feat_all = (feats[0] if len(feats) == 1 else torch.cat(feats)).contiguous()
+    offsets = np.concatenate([[0], np.cumsum(lengths)]).astype(np.int32)
+    N = int(offsets[-1])
+
+    win = demo_windows_device(lengths, dev)                                  # window k <-> frame k
+    bbox, target, mid, valid = demo_targets(kp_all, win, img_wh)
+    shapes = torch.cat([torch.full((N, 1), int(img_wh[1]), device=dev, dtype=torch.int32),           # (height, width), filled on
+                        torch.full((N, 1), int(img_wh[0]), device=dev, dtype=torch.int32)], 1)       # the device: no upload
+    pose_fr = staging.prepare_pose2d(kp_all, shapes)
+    override = middle_frame == "reference"
+    if reuse:
+        cache = streaming.precompute_frames(model, pose_fr, feat_all)
+        if override:
+            cache = streaming.precompute_mid_frames(model, cache, mid, feat_all)   # window k <-> frame k: mid is ordered by frame
+        mesh, _, _, joints = streaming.stream_forward_cached(model, cache, windows=win, batch=batch, with_joints=True)
+    else:
+        ms, js = [], []
+        for lo in range(0, N, batch):
+            p, f = streaming.assemble_windows(pose_fr, feat_all, win[lo:lo + batch])
+            if override:
+                override_middle(p, mid[lo:lo + batch])
+            o = model.forward_with_joints(p, f)
+            ms.append(o[0])
+            js.append(o[3])
+        mesh, joints = torch.cat(ms), torch.cat(js)
+    seq = np.array([0, N], dtype=np.int32) if chain_across else offsets
+    cam, loss, orig = camera.fit_camera(joints, target, init=init, seq_offsets=seq, precision=precision, scale=1e-3, bbox=bbox,
+                                        img_wh=img_wh, seed=seed)
+    if check:
+        bad = np.nonzero(valid.cpu().numpy() == 0)[0]                        # the one host wait
+        if bad.size:
+            t = int(np.searchsorted(offsets, bad[0], side="right") - 1)
+            raise ValueError(f"tracklet {t}, frame {int(bad[0] - offsets[t])}: the keypoints span no box (the reference's process_bbox "
+                             f"returns None there and the demo stops); {bad.size} such frame(s) in all - check=False keeps them as NaN")
+    outs = []
+    for a, b in zip(offsets[:-1], offsets[1:]):
+        a, b = int(a), int(b)
+        outs.append({"mesh": mesh[a:b], "pred_cam": cam[a:b], "bboxes": bbox[a:b], "orig_cam": orig[a:b], "loss": loss[a:b],
+                     "joints_mm": joints[a:b], "target2d": target[a:b]})
+    return outs
+
+
+@torch.no_grad()
+def run_tracklet(model, keypoints, features, img_wh, middle_frame: str = "reference", reuse: bool = True, batch: int = 256, init=None,
+                 seed: int = 0, precision: str = "f32", check: bool = True):
+    """One person's tracklet: keypoints[N,17,>=2] (pixels, COCO order; further columns such as the score are ignored) and
+    features[N,2048] (numpy or torch, any device) -> one row per frame:
+
+        mesh[N,6890,3] m, pred_cam[N,3] (s, tx, ty of the 500-px crop), bboxes[N,4] (x, y, w, h), orig_cam[N,4] (sx, sy, tx, ty in the
+        image), loss[N], joints_mm[N,rows,3] (the regressed joints the camera was fitted to), target2d[N,19,2] (crop pixels)
+
+    middle_frame: "reference" reproduces the demo's overwrite of every window's middle frame (module docstring), "clean" does not.
+    reuse: True serves the windows from per-frame tables (``streaming.stream_forward_cached``), False assembles every window and runs
+    ``model.forward_with_joints`` on it.  The camera is one chain along the tracklet from ``init`` [1,3] (default: seeded uniform), in
+    ``precision`` "f32" or "f64" (the fit only).  Fewer than 16 frames raise ValueError, a model without regressor PmceError.
+    Everything is enqueued on the current stream without a host wait (with ``reuse=False`` under the model's default "rerun" overflow
+    policy ``forward_with_joints`` itself waits per batch: ``model.set_overflow_policy("report")`` removes that); with ``check=True`` the
+    per-window ``valid`` flags are read back once at the end, and a frame on which the reference would have stopped (process_bbox
+    returning None) raises ValueError naming it.  With ``check=False`` its rows are NaN."""
+    return run_tracklets(model, [(keypoints, features)], img_wh, middle_frame=middle_frame, reuse=reuse, batch=batch, init=init,
+                         seed=seed, precision=precision, check=check)[0]
+
+
+def tracklet_span(joints2d, vis_thresh: float = 0.3):
+    """(start, end) - first usable frame and one past the last - by which the reference's CropDataset trims a tracklet before anything
+    else (lib/utils/_dataset_demo.py:48-54): the two indices ``get_all_bbox_params`` returns (lib/utils/smooth_bbox.py:62-103).  A frame
+    is usable when it has a keypoint with score > vis_thresh and those keypoints span at least half a pixel (:49-56); ``None`` entries
+    are unusable.  joints2d: sequence of [K,3] (x, y, score).  No usable frame gives (-1, 0)."""
+    if len(joints2d) == 0:
+        raise ValueError("tracklet_span: empty tracklet")
+    ok = np.zeros(len(joints2d), dtype=bool)
+    for i, kp in enumerate(joints2d):
+        if kp is None:
+            continue
+        kp = np.asarray(kp)
+        vis = kp[:, 2] > vis_thresh
+        if vis.any():
+            ok[i] = np.linalg.norm(kp[vis, :2].max(0) - kp[vis, :2].min(0)) >= 0.5
+    hit = np.nonzero(ok)[0]
+    return (int(hit[0]), int(hit[-1]) + 1) if hit.size else (-1, 0)
+
+
+def frame_results(results: dict, frame_ids, num_frames: int):
+    """Per-frame view of per-person results, as ``prepare_rendering_results`` builds it (lib/utils/demo_utils.py:164-182):
+    results {person_id: {'mesh', 'pred_cam', 'bboxes'[, 'frame_ids']}} (host arrays, one row per frame of the tracklet) and frame_ids
+    {person_id: ids} (None: every entry carries its own 'frame_ids', as the demo's pickle does) -> list of ``num_frames`` OrderedDicts
+    {person_id: {'verts', 'cam', 'bbox'}}, the persons of a frame ordered by ``bbox[1]`` ascending (the reference's sort key)."""
+    frames = [{} for _ in range(num_frames)]
+    for pid, data in results.items():
+        ids = frame_ids[pid] if frame_ids is not None and pid in frame_ids else data["frame_ids"]
+        if len(ids) != len(data["mesh"]):
+            raise ValueError(f"person {pid!r}: {len(ids)} frame ids for {len(data['mesh'])} rows")
+        for idx, fid in enumerate(ids):
+            frames[int(fid)][pid] = {"verts": data["mesh"][idx], "cam": data["pred_cam"][idx], "bbox": data["bboxes"][idx]}
+    out = []
+    for fd in frames:
+        keys = list(fd.keys())
+        order = np.argsort([fd[k]["bbox"][1] for k in keys]) if keys else []
+        out.append(OrderedDict((keys[i], fd[keys[i]]) for i in order))
+    return out

@@ -66,6 +66,16 @@ def validate_windows(windows, num_frames: int, seqlen: int = SEQLEN) -> np.ndarr
     return np.ascontiguousarray(w, dtype=np.int32)
 
 
+def _device_table(windows) -> bool:
+    """A window table that is already an int32 [W,2] tensor on the GPU (pmce_amd.demo builds its tables there): used as it is - no
+    host check (the kernels clamp frame indices) and no upload, which would make the host wait for the stream."""
+    if not (isinstance(windows, torch.Tensor) and windows.is_cuda):
+        return False
+    if windows.dtype != torch.int32 or windows.dim() != 2 or windows.shape[1] != 2:
+        raise ValueError(f"a device window table must be int32 [W,2] (got {windows.dtype} {tuple(windows.shape)})")
+    return True
+
+
 def assemble_windows(pose2d_frames: torch.Tensor, feat_frames: torch.Tensor, windows) -> tuple:
     """Per-frame tables pose2d[L,J,2], feat[L,2048] (GPU) + windows int[W,2] -> (pose2d[W,16,J,2], img_feat[W,16,2048]).
     start == end means "this frame repeated 16 times" (the demo's head/tail windows)."""
@@ -74,7 +84,7 @@ def assemble_windows(pose2d_frames: torch.Tensor, feat_frames: torch.Tensor, win
     p = pose2d_frames.to(torch.float32).contiguous()
     f = feat_frames.to(torch.float32).contiguous()
     L, J, _ = p.shape
-    w = torch.as_tensor(validate_windows(windows, L), device=dev).contiguous()
+    w = windows.contiguous() if _device_table(windows) else torch.as_tensor(validate_windows(windows, L), device=dev).contiguous()
     W = w.shape[0]
     out_p = torch.empty(W, SEQLEN, J, 2, device=dev, dtype=torch.float32)
     out_f = torch.empty(W, SEQLEN, FEAT_DIM, device=dev, dtype=torch.float32)
@@ -85,10 +95,12 @@ def assemble_windows(pose2d_frames: torch.Tensor, feat_frames: torch.Tensor, win
 
 class FrameCache:
     """Per-frame tables of one sequence for the reuse path: x0[L,J,C] (lifter tokens after the window-independent first
-    spatial block) and gi0[L,6144] (GRU layer-0 input projections).  Built once by :func:`precompute_frames`."""
+    spatial block) and gi0[L,6144] (GRU layer-0 input projections).  Built once by :func:`precompute_frames`.
+    ``x0_mid`` (optional, :func:`precompute_mid_frames`): the tokens each frame has as the MIDDLE frame of its window under the demo's
+    middle-frame override; with it :func:`stream_forward_cached` takes token rows (w, 8, j) from that table."""
 
-    def __init__(self, x0, gi0, num_frames):
-        self.x0, self.gi0, self.L = x0, gi0, num_frames
+    def __init__(self, x0, gi0, num_frames, x0_mid=None):
+        self.x0, self.gi0, self.L, self.x0_mid = x0, gi0, num_frames, x0_mid
 
 
 @torch.no_grad()
@@ -108,16 +120,26 @@ def precompute_frames(model, pose2d_frames, feat_frames) -> FrameCache:
 
 
 @torch.no_grad()
+def precompute_mid_frames(model, cache: FrameCache, mid_pose2d_frames, feat_frames) -> FrameCache:
+    """``cache`` plus the middle-frame token table: a second per-frame pass over (mid_pose2d_frames[L,J,2] - what frame f looks like to the
+    model as the middle of its window, ``demo.demo_targets``' mid_pose2d ordered by frame -, feat_frames).  Only its x0 is kept."""
+    return FrameCache(cache.x0, cache.gi0, cache.L, precompute_frames(model, mid_pose2d_frames, feat_frames).x0)
+
+
+@torch.no_grad()
 def stream_forward_cached(model, cache: FrameCache, windows=None, batch: int = 256, with_joints: bool = False, lanes: int = 2):
     """Same outputs as :func:`stream_forward`, but the per-frame work is taken from ``cache`` (about 21 % fewer FLOPs per
     window: SpatialBlocks[0], imgfeat_embed and the GRU layer-0 input projection are not recomputed 16 times per frame).
     ``lanes`` window batches are in flight at once on handles that share the packed weights (models.PMCE.Pipeline's
     scheme: batch k on lane k % lanes, its lifter started when the previous batch's has finished); results do not depend
-    on it."""
+    on it.  A cache with ``x0_mid`` (:func:`precompute_mid_frames`) runs the demo's middle-frame override (pmce_stream_forward_mid).
+    ``windows`` may be an int32 [W,2] tensor on the GPU: it is used without a host check and without an upload."""
     import ctypes as C
     from .config import NUM_VERTS_FULL
     main = model._ensure_packed()
-    windows = validate_windows(window_indices(cache.L) if windows is None else windows, cache.L)
+    on_dev = _device_table(windows)
+    if not on_dev:
+        windows = validate_windows(window_indices(cache.L) if windows is None else windows, cache.L)
     dev = cache.x0.device
     J = model.num_joint
     nb = (len(windows) + batch - 1) // batch
@@ -135,7 +157,8 @@ def stream_forward_cached(model, cache: FrameCache, windows=None, batch: int = 2
     outs, prev = [], None
     for k, lo in enumerate(range(0, len(windows), batch)):
         eng, st = (engines[k % lanes], streams[k % lanes]) if lanes > 1 else (main, cur)
-        w = torch.as_tensor(np.asarray(windows[lo:lo + batch], dtype=np.int32), device=dev).contiguous()
+        w = windows[lo:lo + batch].contiguous() if on_dev else \
+            torch.as_tensor(np.asarray(windows[lo:lo + batch], dtype=np.int32), device=dev).contiguous()
         W = w.shape[0]
         if lanes > 1:
             st.wait_event(ready)
@@ -148,10 +171,13 @@ def stream_forward_cached(model, cache: FrameCache, windows=None, batch: int = 2
             pose3d = torch.empty(W, J, 3, device=dev, dtype=torch.float32)
             pred = torch.empty(W, eng.regressor_rows, 3, device=dev, dtype=torch.float32) if with_joints else None
             ws = eng.workspace(max(W, batch))
-            _lib.check(eng.lib.pmce_stream_forward(eng.handle, _lib.ptr(cache.x0), _lib.ptr(cache.gi0), _lib.ptr(w), W, cache.L,
-                                                   _lib.ptr(mesh), _lib.ptr(pose), _lib.ptr(pose3d), _lib.ptr(pred),
-                                                   C.c_void_p(ws.data_ptr()), ws.numel(), C.c_void_p(st.cuda_stream)),
-                       "stream_forward")
+            tail = (_lib.ptr(cache.gi0), _lib.ptr(w), W, cache.L, _lib.ptr(mesh), _lib.ptr(pose), _lib.ptr(pose3d), _lib.ptr(pred),
+                    C.c_void_p(ws.data_ptr()), ws.numel(), C.c_void_p(st.cuda_stream))
+            if cache.x0_mid is None:
+                _lib.check(eng.lib.pmce_stream_forward(eng.handle, _lib.ptr(cache.x0), *tail), "stream_forward")
+            else:
+                _lib.check(eng.lib.pmce_stream_forward_mid(eng.handle, _lib.ptr(cache.x0), _lib.ptr(cache.x0_mid), *tail),
+                           "stream_forward_mid")
             if lanes > 1:
                 w.record_stream(st)
         outs.append((mesh, pose, pose3d, pred) if with_joints else (mesh, pose, pose3d))
