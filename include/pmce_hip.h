@@ -173,14 +173,11 @@ int pmce_stream_forward(pmce_model* m, const float* x0, const float* gi0, const 
 int pmce_stream_forward_mid(pmce_model* m, const float* x0, const float* x0_mid, const float* gi0, const int* win, int W, int L,
                             float* cam_mesh, float* cam_pose, float* pose3d, float* pred_pose, void* ws, size_t ws_bytes,
                             pmce_stream_t stream);
-/* building blocks of the above */
+/* building blocks of the above; xn_split != 0: XN written pre-split (see pmce_ln_chain_f32) */
 int pmce_window_tokens_f32(const float* x0, const int* win, const float* tpos, const float* w2, const float* b2, float eps2,
-                           float* X, float* XN, int W, int L, int T, int J, int C, pmce_stream_t stream);
-/* XN written pre-split (see pmce_ln_chain_ex_f32). */
-int pmce_window_tokens_ex_f32(const float* x0, const int* win, const float* tpos, const float* w2, const float* b2, float eps2,
                            float* X, float* XN, int W, int L, int T, int J, int C, int xn_split, pmce_stream_t stream);
-/* Rewrites the W * J rows (w, t_mid, j) of X / XN (filled by pmce_window_tokens_ex_f32) from x0_mid: X = x0_mid[m(w),j,:] + tpos[t_mid,:],
- * XN = LN(X), m(w) = start + t_mid (start when start == end); the arithmetic of pmce_window_tokens_ex_f32. */
+/* Rewrites the W * J rows (w, t_mid, j) of X / XN (filled by pmce_window_tokens_f32) from x0_mid: X = x0_mid[m(w),j,:] + tpos[t_mid,:],
+ * XN = LN(X), m(w) = start + t_mid (start when start == end); the arithmetic of pmce_window_tokens_f32. */
 int pmce_window_mid_tokens_f32(const float* x0_mid, const int* win, const float* tpos, const float* w2, const float* b2, float eps2,
                                float* X, float* XN, int W, int L, int T, int J, int C, int t_mid, int xn_split, pmce_stream_t stream);
 int pmce_window_rows_f32(const float* src, const int* win, float* dst, int W, int L, int T, int ncols, pmce_stream_t stream);
@@ -218,7 +215,7 @@ int pmce_gemm_nt_f32(const float* A, const float* W, const float* bias, const fl
                      long long c_lo, long long c_hi, int batch, long long bsA, long long bsW, long long bsBias,
                      long long bsC, pmce_stream_t stream);
 /* Tuning aid only: force the tile configuration (0..3, -1 = automatic) and the persistent workgroups per CU (1..8, 0 =
- * automatic) of pmce_gemm_nt_f32 for the whole process (initial values: PMCE_GEMM_TILE / PMCE_GEMM_GRID, read once). */
+ * automatic) of pmce_gemm_nt_f32 for the whole process (initially automatic; no environment variable sets it, see pmce_model_create). */
 int pmce_gemm_set_tuning(int tile, int grid_per_cu);
 /* The same nn.Linear product on the f16 matrix pipe with fp32 operands, result and accuracy: W is split ONCE into f16
  * (hi, lo) planes of W[n] * 2^s(n) by pmce_gemm_pack_split_f16 (Wp: N*K floats of storage; wscale: N floats, 2^-s(n) - one power
@@ -226,54 +223,42 @@ int pmce_gemm_set_tuning(int tile, int grid_per_cu);
  * other rows' lo planes their bits), A is split into (hi, lo * 2^11) on the fly, C[m][n] = 2^-s(n) (Ahi Whi + Ahi Wlo + Alo Whi)
  * accumulated in fp32 - error at or below the fp32 product's own rounding.  A, bias, R, C stay fp32 and row-major (lda, ldc);
  * |A| must be below 65504 here (an element outside the f16 range yields inf/nan, never a silently wrong finite value; raw inputs
- * of arbitrary magnitude go through pmce_split_rows_scaled_f16 / pmce_gemm_nt_split_f16_rs below; inside a model call a non-finite
- * result also sets the model's overflow word, pmce_model_overflowed).
+ * of arbitrary magnitude go through pmce_split_rows_scaled_f16 and rscale below; inside a model call a non-finite result also sets the
+ * model's overflow word, pmce_model_overflowed).
  * MI355X: while a kernel that issues f16 matrix instructions runs, packed-fp32 vector arithmetic (v_pk_{fma,mul,add}_f32) of
  * any other wave on the same CU may return wrong results (scripts/microbench/libpmce_diag.so: pmce_dbg_victim reproduces it).  No kernel of this library contains
- * such instructions, so its entries may overlap each other freely; do not overlap these entries with foreign kernels that do. */
-int pmce_gemm_pack_split_f16(const float* W, int N, int K, int ldw, float* Wp, float* wscale, pmce_stream_t stream);
-int pmce_gemm_nt_split_f16(const float* A, const float* Wp, const float* wscale, const float* bias, const float* R, float* C,
-                           int M, int N, int K, long long lda, long long ldc, int act, int a_packed, pmce_stream_t stream);
-/* c_packed != 0 (packed A, GELU, no residual, N % 32 == 0): the result is written pre-split as well - it is the A operand of the
- * next product (the lifter's fc1 -> fc2). */
-int pmce_gemm_nt_split_f16_ex(const float* A, const float* Wp, const float* wscale, const float* bias, const float* R, float* C,
-                              int M, int N, int K, long long lda, long long ldc, int act, int a_packed, int c_packed,
-                              pmce_stream_t stream);
-/* The same with mapped output rows: row r of C at C + (r % c_div)*c_lo + (r / c_div)*c_hi (the GRU layer-0 input projection
- * writes (b,t) rows time-major). */
-int pmce_gemm_nt_split_f16_rowmap(const float* A, const float* Wp, const float* wscale, const float* bias, float* C, int M, int N,
-                                  int K, long long lda, int c_div, long long c_lo, long long c_hi, pmce_stream_t stream);
-/* RAW inputs of any finite fp32 magnitude: pmce_split_rows_scaled_f16 stores row m of A[M][lda] as f16 (hi, lo * 2^11) planes of
- * A[m] * 2^-e(m) (Ap: M*K floats of storage) and rscale[m] = 2^e(m), e(m) lifting the row's largest |a| into [2^14, 2^15) - the
- * per-row treatment pmce_gemm_pack_split_f16 gives W.  pmce_gemm_nt_split_f16_rs multiplies such an A:
- * C[m][n] = 2^e(m) 2^-s(n) (Ahi Whi + Ahi Wlo + Alo Whi) + bias[n]; c_div > 0 maps the output rows as in _rowmap (ldc == N then).
- * Rows holding inf / nan keep e = 0 and yield non-finite results in their own row only.
- * A row-scaled product needs K >= 128 (K = 32 .. 127 returns PMCE_ERR_ARG: the kernels read a tile's row scales after its last k-tile while
- * the LDS-DMA cursor runs up to three k-tile stages ahead; every row-scaled product of the path has K = 2048). */
+ * such instructions, so its entries may overlap each other freely; do not overlap these entries with foreign kernels that do.
+ * blocked != 0 / w_blocked != 0: the BLOCKED weight layout (what the model packs and multiplies) - the same planes as
+ * [ceil(N/64)][K/16][64 rows][16 hi | 16 lo] (Wp: ceil(N/64)*64*K floats of storage), so that what a tile fetches per k-tile is
+ * contiguous 4 KB pieces instead of 64-byte pieces one weight row apart.  Results are bit-identical in both layouts (same arithmetic,
+ * same k order).
+ * a_packed != 0: A is not fp32 but already split, [M][K/16][hi 16 f16 | lo*2^11 16 f16] (the layout the lifter's own producers write;
+ * pmce_split_rows_f16 makes it from fp32 rows; lda == K).  c_packed != 0 (packed A, GELU, no residual, N % 32 == 0, ldc == N): the result
+ * is written pre-split as well - it is the A operand of the next product (the lifter's fc1 -> fc2).
+ * c_div > 0 (no residual, ldc == N): mapped output rows, row r of C at C + (r % c_div)*c_lo + (r / c_div)*c_hi (the GRU layer-0 input
+ * projection writes (b,t) rows time-major); c_div == 0: row r at r*ldc.
+ * rscale != NULL: RAW inputs of any finite fp32 magnitude.  pmce_split_rows_scaled_f16 stores row m of A[M][lda] as f16 (hi, lo * 2^11)
+ * planes of A[m] * 2^-e(m) (Ap: M*K floats of storage) and rscale[m] = 2^e(m), e(m) lifting the row's largest |a| into [2^14, 2^15) - the
+ * per-row treatment pmce_gemm_pack_split_f16 gives W; A = Ap is then a packed A (whatever a_packed says; no activation, residual or packed
+ * result) and C[m][n] = 2^e(m) 2^-s(n) (Ahi Whi + Ahi Wlo + Alo Whi) + bias[n].  Rows holding inf / nan keep e = 0 and yield non-finite
+ * results in their own row only.  A row-scaled product needs K >= 128 (K = 32 .. 127 returns PMCE_ERR_ARG: the kernels read a tile's row
+ * scales after its last k-tile while the LDS-DMA cursor runs up to three k-tile stages ahead; every row-scaled product of the path has
+ * K = 2048). */
+int pmce_gemm_pack_split_f16(const float* W, int N, int K, int ldw, float* Wp, float* wscale, int blocked, pmce_stream_t stream);
+int pmce_gemm_nt_split_f16(const float* A, const float* rscale, const float* Wp, int w_blocked, const float* wscale, const float* bias,
+                           const float* R, float* C, int M, int N, int K, long long lda, long long ldc, int act, int a_packed,
+                           int c_packed, int c_div, long long c_lo, long long c_hi, pmce_stream_t stream);
+int pmce_split_rows_f16(const float* A, long long M, int K, long long lda, float* Ap, pmce_stream_t stream);
 int pmce_split_rows_scaled_f16(const float* A, long long M, int K, long long lda, float* Ap, float* rscale, pmce_stream_t stream);
-int pmce_gemm_nt_split_f16_rs(const float* Ap, const float* rscale, const float* Wp, const float* wscale, const float* bias, float* C,
-                              int M, int N, int K, long long ldc, int c_div, long long c_lo, long long c_hi, pmce_stream_t stream);
-/* The BLOCKED weight layout (round 4; what the model packs and multiplies): pmce_gemm_pack_split_f16_blk writes the same planes as
- * pmce_gemm_pack_split_f16 as [ceil(N/64)][K/16][64 rows][16 hi | 16 lo] (Wp: ceil(N/64)*64*K floats of storage), so that what a tile
- * fetches per k-tile is contiguous 4 KB pieces instead of 64-byte pieces one weight row apart.  pmce_gemm_nt_split_f16_blk is every
- * product form above on such a weight: rscale != null -> A row-scaled (as _rs), c_div > 0 -> mapped output rows (ldc == N), else as
- * _ex.  Results are bit-identical to the row-major forms (same arithmetic, same k order). */
-int pmce_gemm_pack_split_f16_blk(const float* W, int N, int K, int ldw, float* Wp, float* wscale, pmce_stream_t stream);
-int pmce_gemm_nt_split_f16_blk(const float* A, const float* rscale, const float* Wblk, const float* wscale, const float* bias,
-                               const float* R, float* C, int M, int N, int K, long long lda, long long ldc, int act, int a_packed,
-                               int c_packed, int c_div, long long c_lo, long long c_hi, pmce_stream_t stream);
 /* A product with N = 256 and a residual, followed by the LayerNorm chain of its consumer, in ONE launch (round 4; proj -> norm2 and
  * fc2 -> norm_s / norm_t -> next norm1 of a C = 256 lifter block, reference PoseEstimation.py:26-28,84-85,91-92,101-106): with
  * x = Ap W^T + bias + R,   y1 = ln1_w ? LN(x; ln1_w, ln1_b, ln1_eps) : x,   out1 = y1 (fp32 [M,256]; may alias R; may be NULL),
  * out2 = LN(y1; ln2_w, ln2_b, ln2_eps) written pre-split (the next product's packed A; may be NULL).  Ap pre-split [M,K]; Wp from
- * pmce_gemm_pack_split_f16 (w_blocked = 0) or _blk (1).  The same as pmce_gemm_nt_split_f16_blk + pmce_ln_chain_ex_f32 up to the
+ * pmce_gemm_pack_split_f16, w_blocked = its `blocked`.  The same as pmce_gemm_nt_split_f16 + pmce_ln_chain_f32 up to the
  * summation order of the row statistics (two-pass fp32 in both). */
 int pmce_gemm_nt_split_f16_ln(const float* Ap, const float* Wp, int w_blocked, const float* wscale, const float* bias, const float* R,
                               int M, int K, const float* ln1_w, const float* ln1_b, float ln1_eps, float* out1, const float* ln2_w,
                               const float* ln2_b, float ln2_eps, float* out2, pmce_stream_t stream);
-/* a_packed != 0: A is not fp32 but already split, [M][K/16][hi 16 f16 | lo*2^11 16 f16] (the layout the lifter's own
- * producers write; pmce_split_rows_f16 makes it from fp32 rows). */
-int pmce_split_rows_f16(const float* A, long long M, int K, long long lda, float* Ap, pmce_stream_t stream);
 /* Tuning aid only: force the tile configuration of pmce_gemm_nt_split_f16 (0: 128x256, 1: 128x128, 2: 64x128; -1 automatic). */
 int pmce_gemm_split_set_tuning(int tile);
 /* PoseEstimation.py:78-81 — x[tok] = joint_embed(pose2d) + imgfeat_embed(img_feat)[b,t] + spatial_pos[j]. */
@@ -281,42 +266,36 @@ int pmce_embed_tokens_f32(const float* pose2d, const float* E, const float* Wje,
                           float* x, long long ntok, int J, int C, pmce_stream_t stream);
 /* The same followed by LayerNorm(w2, b2, eps2) of every token row (SpatialBlocks[0].norm1, PoseEstimation.py:13-29 via :83) in ONE launch:
  * x = the tokens (fp32 [ntok, C]), xn = their LayerNorm - fp32, or pre-split [row][C/16][16 hi | 16 lo*2^11] f16 when xn_split (the operand of a
- * three-product f16 GEMM).  Bit-identical to pmce_embed_tokens_f32 + pmce_ln_chain_ex_f32(out2).  C = 256 or 512. */
+ * three-product f16 GEMM).  Bit-identical to pmce_embed_tokens_f32 + pmce_ln_chain_f32(out2).  C = 256 or 512. */
 int pmce_embed_ln_f32(const float* pose2d, const float* E, const float* Wje, const float* bje, const float* spos, float* x,
                       long long ntok, int J, int C, const float* w2, const float* b2, float eps2, float* xn, int xn_split,
                       pmce_stream_t stream);
 /* nn.LayerNorm chain over rows of C channels: y1 = (w1 ? LN(x;w1,b1,eps1) : x) + add[(row/add_div)%add_mod];
- * out1 = y1 (optional); out2 = LN(y1;w2,b2,eps2) (optional).  norm1/norm2/norm_s/norm_t (PoseEstimation.py:17,23,58-59). */
-/* _ex forms: out2 / out / XN written pre-split ([row][C/16][16 hi | 16 lo*2^11] f16 in the bytes of the fp32 row), i.e. directly as
- * the A operand of pmce_gemm_nt_split_f16_ex(a_packed = 1). */
-int pmce_ln_chain_ex_f32(const float* x, long long rows, int C, const float* w1, const float* b1, float eps1, const float* add,
-                         int add_div, int add_mod, float* out1, const float* w2, const float* b2, float eps2, float* out2,
-                         int out2_split, pmce_stream_t stream);
-int pmce_seq_attention_ex_f32(const float* qkv, float* out, int nseq, int N, int C, int seq_div, long long seq_lo,
-                              long long seq_hi, long long tok_stride, int out_split, pmce_stream_t stream);
+ * out1 = y1 (optional); out2 = LN(y1;w2,b2,eps2) (optional).  norm1/norm2/norm_s/norm_t (PoseEstimation.py:17,23,58-59).
+ * out2_split (and out_split / xn_split of the entries below) != 0: out2 / out / XN written pre-split ([row][C/16][16 hi | 16 lo*2^11] f16
+ * in the bytes of the fp32 row), i.e. directly as the A operand of pmce_gemm_nt_split_f16(a_packed = 1). */
+int pmce_ln_chain_f32(const float* x, long long rows, int C, const float* w1, const float* b1, float eps1, const float* add,
+                      int add_div, int add_mod, float* out1, const float* w2, const float* b2, float eps2, float* out2,
+                      int out2_split, pmce_stream_t stream);
+/* timm Attention core on qkv[tok][3C] for sequences of N <= 32 tokens, 8 heads (PoseEstimation.py:19 / CoevoDecoder.py:118-131).
+ * sequence s, position i -> token (s % seq_div)*seq_lo + (s / seq_div)*seq_hi + i*tok_stride. */
+int pmce_seq_attention_f32(const float* qkv, float* out, int nseq, int N, int C, int seq_div, long long seq_lo,
+                           long long seq_hi, long long tok_stride, int out_split, pmce_stream_t stream);
 /* The same attention (timm Attention of PoseEstimation.py:78-104) on the f16 matrix pipe in the three-product form: q, k, v read
  * as fp32 (split into f16 (hi, lo) planes inside the kernel), the result WRITTEN pre-split ([row][C/16][16 hi | 16 lo*2^11] f16 in
  * the bytes of the fp32 row) as the A operand of proj.  Sequence / token addressing as pmce_seq_attention_f32.  C = 256 or 512 (8 heads),
  * N = 16, 17 or 19 (pmce_seq_attention_split_supported tells); anything else returns PMCE_ERR_ARG - callers keep fp32 qkv and
- * pmce_seq_attention_ex_f32 there.  A non-finite result sets the calling thread's overflow sink like the products do. */
+ * pmce_seq_attention_f32 there.  A non-finite result sets the calling thread's overflow sink like the products do. */
 int pmce_seq_attention_split_supported(int N, int C);
 int pmce_seq_attention_split_f16(const float* qkv, float* out_planes, int nseq, int N, int C, int seq_div, long long seq_lo,
                                  long long seq_hi, long long tok_stride, pmce_stream_t stream);
-int pmce_ln_chain_f32(const float* x, long long rows, int C, const float* w1, const float* b1, float eps1,
-                      const float* add, int add_div, int add_mod, float* out1, const float* w2, const float* b2,
-                      float eps2, float* out2, pmce_stream_t stream);
-/* timm Attention core on qkv[tok][3C] for sequences of N <= 32 tokens, 8 heads (PoseEstimation.py:19 / CoevoDecoder.py:118-131).
- * sequence s, position i -> token (s % seq_div)*seq_lo + (s / seq_div)*seq_hi + i*tok_stride. */
-int pmce_seq_attention_f32(const float* qkv, float* out, int nseq, int N, int C, int seq_div, long long seq_lo,
-                           long long seq_hi, long long tok_stride, pmce_stream_t stream);
-/* PoseEstimation.py:62-66,109-113 — LayerNorm(1e-5) + Linear(C->3) + Conv2d(T->1) frame fusion. */
-int pmce_lifter_head_f32(const float* x, const float* lnw, const float* lnb, const float* Wr, const float* br,
-                         const float* wf, const float* bf, float* pose3d, int B, int T, int J, int C, pmce_stream_t stream);
-/* prew != NULL: x is the LAST TemporalBlock's output BEFORE its post-norm, and every row passes through LayerNorm(prew, preb, pre_eps) (norm_t,
- * PoseEstimation.py:92) on the way in - bit-identical to pmce_ln_chain_f32(out1) followed by pmce_lifter_head_f32, without the launch and the round trip. */
-int pmce_lifter_head_ex_f32(const float* x, const float* prew, const float* preb, float pre_eps, const float* lnw, const float* lnb,
-                            const float* Wr, const float* br, const float* wf, const float* bf, float* pose3d, int B, int T, int J, int C,
-                            pmce_stream_t stream);
+/* PoseEstimation.py:62-66,109-113 — LayerNorm(1e-5) + Linear(C->3) + Conv2d(T->1) frame fusion.
+ * prew != NULL: x is the LAST TemporalBlock's output BEFORE its post-norm, and every row passes through LayerNorm(prew, preb, pre_eps) (norm_t,
+ * PoseEstimation.py:92) on the way in - bit-identical to pmce_ln_chain_f32(out1) followed by the head on its result, without the launch and the
+ * round trip. */
+int pmce_lifter_head_f32(const float* x, const float* prew, const float* preb, float pre_eps, const float* lnw, const float* lnb,
+                         const float* Wr, const float* br, const float* wf, const float* bf, float* pose3d, int B, int T, int J, int C,
+                         pmce_stream_t stream);
 
 /* Fused nn.GRU time step for ndir directions: gh = h_prev W_hh^T + b_hh on the matrix cores, then the gate update
  * (CoevoDecoder.py:216-221); gi = W_ih x + b_ih comes from pmce_gemm_nt_f32.  hp == NULL means h_prev = 0. */
@@ -324,34 +303,27 @@ int pmce_gru_step_f32(const float* gi0, const float* gi1, const float* whh0, con
                       const float* bhh1, const float* hp0, const float* hp1, float* ho0, float* ho1, long long gi_rs,
                       long long h_rs, int B, int H, int ndir, pmce_stream_t stream);
 /* The same step with gh = h W_hh^T in the three-product f16 form (pmce_gemm_nt_split_f16's arithmetic): whh0p / whh1p are rows of
- * ONE weight packed by pmce_gemm_pack_split_f16 (K = H), wscale its scale pair. */
+ * ONE weight packed by pmce_gemm_pack_split_f16 (K = H), wscale its scale pair, w_blocked its `blocked` (1 is what the model runs: the
+ * 16 rows a DMA instruction fetches are 1 KB contiguous; whh0p / whh1p = the first row of each direction, a multiple of 64 rows apart).
+ * B <= 64 runs a small-batch kernel (a workgroup per 8 hidden units: 256 workgroups whatever the batch), larger batches 64 rows x 32 units
+ * per workgroup - same numbers, bit for bit, in both layouts and at every batch size. */
 int pmce_gru_step_split_f32(const float* gi0, const float* gi1, const float* whh0p, const float* whh1p, const float* wscale,
                             const float* bhh0, const float* bhh1, const float* hp0, const float* hp1, float* ho0, float* ho1,
-                            long long gi_rs, long long h_rs, int B, int H, int ndir, pmce_stream_t stream);
-/* The same on a W_hh packed by pmce_gemm_pack_split_f16_blk (the blocked layout: the 16 rows a DMA instruction fetches are 1 KB contiguous;
- * whh0b / whh1b = the first row of each direction, a multiple of 64 rows apart): what the model runs.  B <= 64 runs a small-batch kernel (a
- * workgroup per 8 hidden units: 256 workgroups whatever the batch), larger batches 64 rows x 32 units per workgroup - same numbers, bit for
- * bit, in both layouts and at every batch size. */
-int pmce_gru_step_split_blk_f32(const float* gi0, const float* gi1, const float* whh0b, const float* whh1b, const float* wscale,
-                                const float* bhh0, const float* bhh1, const float* hp0, const float* hp1, float* ho0, float* ho1,
-                                long long gi_rs, long long h_rs, int B, int H, int ndir, pmce_stream_t stream);
+                            long long gi_rs, long long h_rs, int B, int H, int ndir, int w_blocked, pmce_stream_t stream);
 /* y = x / denom (PMCE.py:18). */
 int pmce_div_scalar_f32(const float* x, float* y, long long n, float denom, pmce_stream_t stream);
 
 /* CoevoDecoder.py:232 — vertxs[b][v][:] = joints[b][vj[v]][:]; vj int32[431].  Bit-exact copy. */
 int pmce_vertex_init_gather_f32(const float* joints, const int* vj, float* vt, int B, int J, pmce_stream_t stream);
 /* Key/value side of the vertex<-joint CrossAttention (CoevoDecoder.py:47-62,83) with Wq / proj folded in:
- * GB[b][inst*128 + (gamma 0..63 | beta 64..127)] are the AdaLN parameters; Kf,Vf [B,64,64], s0 [B,64]. */
-int pmce_ca_fold_f32(const float* xk, const float* xv, const float* GB, int gb_stride, int iq, int ik, int iv,
-                     const float* Wq, const float* bq, const float* Wk, const float* bk, const float* Wv, const float* bv,
-                     const float* Wp, float* Kf, float* s0, float* Vf, int B, int J, pmce_stream_t stream);
-/* The same, also (img != NULL, J <= 23) writing the operands as the LDS image pmce_vertex_ca_mlp_pk_f32's split_f16 form copies: per clip
+ * GB[b][inst*128 + (gamma 0..63 | beta 64..127)] are the AdaLN parameters; Kf,Vf [B,64,64], s0 [B,64].
+ * img != NULL (J <= 23): also writes the operands as the LDS image pmce_vertex_ca_mlp_f32's split_f16 form copies: per clip
  * pmce_ca_image_floats() floats - s0, two scales, Kf and Vf as (hi | lo) f16 fragment planes scaled by one power of two each.  Kf / s0 / Vf may
  * each be NULL when only the image is wanted. */
 int pmce_ca_image_floats(void);
-int pmce_ca_fold_img_f32(const float* xk, const float* xv, const float* GB, int gb_stride, int iq, int ik, int iv,
-                         const float* Wq, const float* bq, const float* Wk, const float* bk, const float* Wv, const float* bv,
-                         const float* Wp, float* Kf, float* s0, float* Vf, float* img, int B, int J, pmce_stream_t stream);
+int pmce_ca_fold_f32(const float* xk, const float* xv, const float* GB, int gb_stride, int iq, int ik, int iv,
+                     const float* Wq, const float* bq, const float* Wk, const float* bk, const float* Wv, const float* bv,
+                     const float* Wp, float* Kf, float* s0, float* Vf, float* img, int B, int J, pmce_stream_t stream);
 /* The joint side of a CoevoBlock in ONE launch (what the model runs): the joint embedding of CoevoDecoder.py:177-180,184 -
  * jf = joint_proj(jt) + joint_pos_embed, xk = proj_j2v_dim(jf) + j2v_K_embed, xv = jf - followed by the fold above.  jf_out [B,J,64] may be
  * NULL (only the block-3 joint stream reads it). */
@@ -364,35 +336,27 @@ int pmce_joint_prep_f32(const float* jt, const float* Wj, const float* bj, const
  * xq := Wv3*vt + Eq formed on the fly from vt[B,431,3]. */
 int pmce_vertex_ca_f32(const float* xq, const float* vt, const float* Wv3, const float* Eq, const float* Kf,
                        const float* s0, const float* Vf, const float* bp, float* out, int B, int J, pmce_stream_t stream);
+/* The FFN of the two kernels below: split_f16 != 0 runs the 64->256->64 FFN in the three-product f16 form (activations split in registers;
+ * fp32 accumulate, fp32 results); ffn_img != NULL: every workgroup COPIES the FFN's f16 planes into LDS (LDS-DMA) from an image made once
+ * (pmce_ffn_pack_f16 from the same W1 [256,64] / W2 [64,256]: pmce_ffn_image_floats() floats, 16-byte aligned) instead of converting
+ * W1 / W2 itself - the same bits; pmce_model_finalize makes the six images. */
+int pmce_ffn_image_floats(void);
+int pmce_ffn_pack_f16(const float* W1, const float* W2, float* ffn_img, pmce_stream_t stream);
 /* x + Mlp(AdaLN(x)) on [B,431,64] (CoevoDecoder.py:85-86,104); optional Linear(64->3)+coordinate residual (:189). */
 int pmce_adaln_mlp_f32(const float* xin, const float* GB, int gb_stride, int inst, const float* W1, const float* b1,
                        const float* W2, const float* b2, float* yout, const float* Wc, const float* bc, const float* vt_in,
-                       float* vt_out, int B, pmce_stream_t stream);
-
+                       float* vt_out, int B, int split_f16, const float* ffn_img, pmce_stream_t stream);
 /* The whole CrossAttentionBlock of the vertex stream in one launch (reference CoevoDecoder.py:82-87): vertex_ca followed by
  * its FFN (adaln_mlp with AdaLN instance `inst` of GB), the intermediate never leaving registers; arguments as those two.
  * Same arithmetic in the same order as pmce_vertex_ca_f32 + pmce_adaln_mlp_f32.  J <= 23 runs fused; beyond that one clip's
  * folded operands do not fit beside the FFN weights in LDS and the call runs the two kernels through `scratch` [B,431,64]
- * (may be NULL when J <= 23). */
+ * (may be NULL when J <= 23; fp32 attention from Kf / s0 / Vf).  split_f16 != 0 also runs the cross-attention's two contractions in the
+ * three-product form and REQUIRES ca_img = the folded operands' image of pmce_ca_fold_f32 / pmce_joint_prep_f32 (Kf / s0 / Vf are then
+ * not read). */
 int pmce_vertex_ca_mlp_f32(const float* xq, const float* vt, const float* Wv3, const float* Eq, const float* Kf,
                            const float* s0, const float* Vf, const float* bp, const float* GB, int gb_stride, int inst,
                            const float* W1, const float* b1, const float* W2, const float* b2, float* yout, float* scratch,
-                           int B, int J, pmce_stream_t stream);
-/* _pk forms of the two FFN-carrying kernels.  split_f16 != 0 runs the 64->256->64 FFN in the three-product f16 form (activations split in
- * registers; fp32 accumulate, fp32 results); ffn_img != NULL: every workgroup COPIES the FFN's f16 planes into LDS (LDS-DMA) from an image
- * made once (pmce_ffn_pack_f16 from the same W1 [256,64] / W2 [64,256]: pmce_ffn_image_floats() floats, 16-byte aligned) instead of converting
- * W1 / W2 itself - the same bits; pmce_model_finalize makes the six images.  pmce_vertex_ca_mlp_pk_f32 with split_f16 != 0 also runs the
- * cross-attention's two contractions in that form and REQUIRES ca_img = the folded operands' image of pmce_ca_fold_img_f32 /
- * pmce_joint_prep_f32 (Kf / s0 / Vf are then not read); J > 23 takes the two-launch form through `scratch` (fp32 attention from Kf / s0 / Vf). */
-int pmce_ffn_image_floats(void);
-int pmce_ffn_pack_f16(const float* W1, const float* W2, float* ffn_img, pmce_stream_t stream);
-int pmce_adaln_mlp_pk_f32(const float* xin, const float* GB, int gb_stride, int inst, const float* W1, const float* b1,
-                          const float* W2, const float* b2, float* yout, const float* Wc, const float* bc, const float* vt_in,
-                          float* vt_out, int B, int split_f16, const float* ffn_img, pmce_stream_t stream);
-int pmce_vertex_ca_mlp_pk_f32(const float* xq, const float* vt, const float* Wv3, const float* Eq, const float* Kf,
-                              const float* s0, const float* Vf, const float* bp, const float* GB, int gb_stride, int inst,
-                              const float* W1, const float* b1, const float* W2, const float* b2, float* yout, float* scratch,
-                              int B, int J, int split_f16, const float* ffn_img, const float* ca_img, pmce_stream_t stream);
+                           int B, int J, int split_f16, const float* ffn_img, const float* ca_img, pmce_stream_t stream);
 
 /* fp32 pipe: qkv = Linear(64->192)(AdaLN(x)) on [B,431,64] (CoevoDecoder.py:103,120), then
  * y = x + proj(softmax(q k^T/sqrt(32)) v), 2 heads, 431x431 per clip (CoevoDecoder.py:118-131,103). */
@@ -413,17 +377,14 @@ int pmce_qkv_pack_f16(const float* Wqkv, float* qkv_img, pmce_stream_t stream);
 long long pmce_vertex_sab_scratch_floats(int B);
 int pmce_vertex_sab_split_f32(const float* xin, const float* GB, int gb_stride, int inst, const float* qkv_img, const float* bqkv,
                               const float* Wp, const float* bp, float* scratch, float* yout, int B, pmce_stream_t stream);
-/* k|v of the joint<-vertex CrossAttention for the 431 vertex tokens: kv[B,431,128] (CoevoDecoder.py:52-53,83,183). */
-int pmce_tokens_kv_f32(const float* xk, const float* xv, const float* vt, const float* Wv3, const float* Ev,
-                       const float* Wv2j, const float* Ek, const float* GB, int gb_stride, int ik, int iv, const float* Wk,
-                       const float* bk, const float* Wv, const float* bv, float* kv, int B, pmce_stream_t stream);
-/* The same with its three 64 x 64 products (proj_v2j_dim, wk, wv) in the three-product f16 form (what a model in split_f16 mode runs): tkv_img =
- * pmce_tkv_pack_f16(Wv2j, Wk, Wv), pmce_tkv_image_floats() floats, 16-byte aligned, made once; NULL = the fp32 form above. */
+/* k|v of the joint<-vertex CrossAttention for the 431 vertex tokens: kv[B,431,128] (CoevoDecoder.py:52-53,83,183).
+ * tkv_img != NULL: its three 64 x 64 products (proj_v2j_dim, wk, wv) in the three-product f16 form (what a model in split_f16 mode runs):
+ * tkv_img = pmce_tkv_pack_f16(Wv2j, Wk, Wv), pmce_tkv_image_floats() floats, 16-byte aligned, made once; NULL = the fp32 form. */
 int pmce_tkv_image_floats(void);
 int pmce_tkv_pack_f16(const float* Wv2j, const float* Wk, const float* Wv, float* tkv_img, pmce_stream_t stream);
-int pmce_tokens_kv_pk_f32(const float* xk, const float* xv, const float* vt, const float* Wv3, const float* Ev,
-                          const float* Wv2j, const float* Ek, const float* GB, int gb_stride, int ik, int iv, const float* Wk,
-                          const float* bk, const float* Wv, const float* bv, float* kv, int B, const float* tkv_img, pmce_stream_t stream);
+int pmce_tokens_kv_f32(const float* xk, const float* xv, const float* vt, const float* Wv3, const float* Ev,
+                       const float* Wv2j, const float* Ek, const float* GB, int gb_stride, int ik, int iv, const float* Wk,
+                       const float* bk, const float* Wv, const float* bv, float* kv, int B, const float* tkv_img, pmce_stream_t stream);
 /* Joint stream of a CoevoBlock (CoevoDecoder.py:183,187,189): stage 1 = joint<-vertex cross-attention +
  * residual only, 2 = + FFN, 3 = + self-attention block + coordinate head.  wptr: 18 weight pointers
  * (wq,bq,proj_w,proj_b,fc1_w,fc1_b,fc2_w,fc2_b,qkv_w,qkv_b,sproj_w,sproj_b,sfc1_w,sfc1_b,sfc2_w,sfc2_b,coor_w,coor_b);
@@ -431,10 +392,9 @@ int pmce_tokens_kv_pk_f32(const float* xk, const float* xv, const float* vt, con
 int pmce_joint_stream_f32(const float* xq, const float* jQ, const float* kv, const float* GB, int gb_stride,
                           const float* const* wptr, const int* inst, const float* jt, float* y_out, float* pose_out, int B,
                           int J, int stage, pmce_stream_t stream);
-/* Operand of the packed upsample+residual product: A[b] = [relu(g[b]) | vt[b] flattened | 0-pad] (CoevoDecoder.py:238-244). */
-int pmce_build_final_operand_f32(const float* g, const float* vt, float* A, int B, int KP, pmce_stream_t stream);
-/* packed != 0 (KP % 16 == 0): the rows are written pre-split - the A operand of pmce_gemm_nt_split_f16*(a_packed = 1); what the model runs. */
-int pmce_build_final_operand_pk_f32(const float* g, const float* vt, float* A, int B, int KP, int packed, pmce_stream_t stream);
+/* Operand of the packed upsample+residual product: A[b] = [relu(g[b]) | vt[b] flattened | 0-pad] (CoevoDecoder.py:238-244).
+ * packed != 0 (KP % 16 == 0): the rows are written pre-split - the A operand of pmce_gemm_nt_split_f16(a_packed = 1); what the model runs. */
+int pmce_build_final_operand_f32(const float* g, const float* vt, float* A, int B, int KP, int packed, pmce_stream_t stream);
 /* lib/core/base.py:223-225 — out[b][r][:] = sum_nz data * (mesh[b][col][:] * scale); CSR regressor [R,6890]. */
 int pmce_j_regress_f32(const float* mesh, const int* indptr, const int* indices, const float* data, float* out, int B,
                        int R, int NVF, float scale, pmce_stream_t stream);

@@ -44,8 +44,7 @@ PROTOTYPES = {
     "pmce_stream_forward": [C.c_void_p, _f, _f, _f, _i, _i, _f, _f, _f, _f, _f, C.c_size_t, _s],
     "pmce_stream_forward_mid": [C.c_void_p, _f, _f, _f, _f, _i, _i, _f, _f, _f, _f, _f, C.c_size_t, _s],
     "pmce_window_mid_tokens_f32": [_f, _f, _f, _f, _f, _fl, _f, _f, _i, _i, _i, _i, _i, _i, _i, _s],
-    "pmce_window_tokens_f32": [_f, _f, _f, _f, _f, _fl, _f, _f, _i, _i, _i, _i, _i, _s],
-    "pmce_window_tokens_ex_f32": [_f, _f, _f, _f, _f, _fl, _f, _f, _i, _i, _i, _i, _i, _i, _s],
+    "pmce_window_tokens_f32": [_f, _f, _f, _f, _f, _fl, _f, _f, _i, _i, _i, _i, _i, _i, _s],
     "pmce_window_rows_f32": [_f, _f, _f, _i, _i, _i, _i, _s],
     "pmce_model_set_concurrency": [C.c_void_p, _i],
     "pmce_model_wait_lifter": [C.c_void_p, _s],
@@ -65,56 +64,42 @@ PROTOTYPES = {
     "pmce_model_profile_read": [C.c_void_p, _i, C.POINTER(C.c_char_p), C.POINTER(C.c_double), C.POINTER(C.c_longlong)],
     "pmce_gemm_nt_f32": [_f, _f, _f, _f, _f, _i, _i, _i, _l, _i, _l, _i, _i, _l, _l, _i, _l, _l, _i, _l, _l, _l, _l, _s],
     "pmce_gemm_set_tuning": [_i, _i],
-    "pmce_gemm_pack_split_f16": [_f, _i, _i, _i, _f, _f, _s],
-    "pmce_gemm_nt_split_f16": [_f, _f, _f, _f, _f, _f, _i, _i, _i, _l, _l, _i, _i, _s],
+    "pmce_gemm_pack_split_f16": [_f, _i, _i, _i, _f, _f, _i, _s],
+    "pmce_gemm_nt_split_f16": [_f, _f, _f, _i, _f, _f, _f, _f, _i, _i, _i, _l, _l, _i, _i, _i, _i, _l, _l, _s],
     "pmce_split_rows_f16": [_f, _l, _i, _l, _f, _s],
     "pmce_split_rows_scaled_f16": [_f, _l, _i, _l, _f, _f, _s],
-    "pmce_gemm_nt_split_f16_rs": [_f, _f, _f, _f, _f, _f, _i, _i, _i, _l, _i, _l, _l, _s],
-    "pmce_gemm_pack_split_f16_blk": [_f, _i, _i, _i, _f, _f, _s],
-    "pmce_gemm_nt_split_f16_blk": [_f, _f, _f, _f, _f, _f, _f, _i, _i, _i, _l, _l, _i, _i, _i, _i, _l, _l, _s],
     "pmce_gemm_nt_split_f16_ln": [_f, _f, _i, _f, _f, _f, _i, _i, _f, _f, _fl, _f, _f, _f, _fl, _f, _s],
-    "pmce_gemm_nt_split_f16_ex": [_f, _f, _f, _f, _f, _f, _i, _i, _i, _l, _l, _i, _i, _i, _s],
-    "pmce_ln_chain_ex_f32": [_f, _l, _i, _f, _f, _fl, _f, _i, _i, _f, _f, _f, _fl, _f, _i, _s],
-    "pmce_seq_attention_ex_f32": [_f, _f, _i, _i, _i, _i, _l, _l, _l, _i, _s],
+    "pmce_ln_chain_f32": [_f, _l, _i, _f, _f, _fl, _f, _i, _i, _f, _f, _f, _fl, _f, _i, _s],
+    "pmce_seq_attention_f32": [_f, _f, _i, _i, _i, _i, _l, _l, _l, _i, _s],
     "pmce_seq_attention_split_supported": [_i, _i],
     "pmce_seq_attention_split_f16": [_f, _f, _i, _i, _i, _i, _l, _l, _l, _s],
-    "pmce_gemm_nt_split_f16_rowmap": [_f, _f, _f, _f, _f, _i, _i, _i, _l, _i, _l, _l, _s],
     "pmce_gemm_split_set_tuning": [_i],
     "pmce_embed_tokens_f32": [_f, _f, _f, _f, _f, _f, _l, _i, _i, _s],
     "pmce_embed_ln_f32": [_f, _f, _f, _f, _f, _f, _l, _i, _i, _f, _f, _fl, _f, _i, _s],
-    "pmce_ln_chain_f32": [_f, _l, _i, _f, _f, _fl, _f, _i, _i, _f, _f, _f, _fl, _f, _s],
-    "pmce_seq_attention_f32": [_f, _f, _i, _i, _i, _i, _l, _l, _l, _s],
-    "pmce_lifter_head_f32": [_f, _f, _f, _f, _f, _f, _f, _f, _i, _i, _i, _i, _s],
-    "pmce_lifter_head_ex_f32": [_f, _f, _f, _fl, _f, _f, _f, _f, _f, _f, _f, _i, _i, _i, _i, _s],
+    "pmce_lifter_head_f32": [_f, _f, _f, _fl, _f, _f, _f, _f, _f, _f, _f, _i, _i, _i, _i, _s],
     "pmce_gru_step_f32": [_f, _f, _f, _f, _f, _f, _f, _f, _f, _f, _l, _l, _i, _i, _i, _s],
-    "pmce_gru_step_split_f32": [_f, _f, _f, _f, _f, _f, _f, _f, _f, _f, _f, _l, _l, _i, _i, _i, _s],
-    "pmce_gru_step_split_blk_f32": [_f, _f, _f, _f, _f, _f, _f, _f, _f, _f, _f, _l, _l, _i, _i, _i, _s],
+    "pmce_gru_step_split_f32": [_f, _f, _f, _f, _f, _f, _f, _f, _f, _f, _f, _l, _l, _i, _i, _i, _i, _s],
     "pmce_div_scalar_f32": [_f, _f, _l, _fl, _s],
     "pmce_vertex_init_gather_f32": [_f, _f, _f, _i, _i, _s],
     "pmce_ca_image_floats": [],
-    "pmce_ca_fold_img_f32": [_f, _f, _f, _i, _i, _i, _i, _f, _f, _f, _f, _f, _f, _f, _f, _f, _f, _f, _i, _i, _s],
+    "pmce_ca_fold_f32": [_f, _f, _f, _i, _i, _i, _i, _f, _f, _f, _f, _f, _f, _f, _f, _f, _f, _f, _i, _i, _s],
     "pmce_joint_prep_f32": [_f, _f, _f, _f, _f, _f, _f, _f, _f, _i, _i, _i, _i, _f, _f, _f, _f, _f, _f, _f, _f, _f, _f, _f, _i, _i, _s],
-    "pmce_ca_fold_f32": [_f, _f, _f, _i, _i, _i, _i, _f, _f, _f, _f, _f, _f, _f, _f, _f, _f, _i, _i, _s],
     "pmce_vertex_ca_f32": [_f, _f, _f, _f, _f, _f, _f, _f, _f, _i, _i, _s],
-    "pmce_adaln_mlp_f32": [_f, _f, _i, _i, _f, _f, _f, _f, _f, _f, _f, _f, _f, _i, _s],
     "pmce_ffn_image_floats": [],
     "pmce_ffn_pack_f16": [_f, _f, _f, _s],
-    "pmce_adaln_mlp_pk_f32": [_f, _f, _i, _i, _f, _f, _f, _f, _f, _f, _f, _f, _f, _i, _i, _f, _s],
-    "pmce_vertex_ca_mlp_pk_f32": [_f, _f, _f, _f, _f, _f, _f, _f, _f, _i, _i, _f, _f, _f, _f, _f, _f, _i, _i, _i, _f, _f, _s],
-    "pmce_vertex_ca_mlp_f32": [_f, _f, _f, _f, _f, _f, _f, _f, _f, _i, _i, _f, _f, _f, _f, _f, _f, _i, _i, _s],
+    "pmce_adaln_mlp_f32": [_f, _f, _i, _i, _f, _f, _f, _f, _f, _f, _f, _f, _f, _i, _i, _f, _s],
+    "pmce_vertex_ca_mlp_f32": [_f, _f, _f, _f, _f, _f, _f, _f, _f, _i, _i, _f, _f, _f, _f, _f, _f, _i, _i, _i, _f, _f, _s],
     "pmce_adaln_qkv_f32": [_f, _f, _i, _i, _f, _f, _f, _i, _s],
     "pmce_qkv_image_floats": [],
     "pmce_qkv_pack_f16": [_f, _f, _s],
     "pmce_vertex_sa_f32": [_f, _f, _f, _f, _f, _i, _s],
     "pmce_vertex_sab_scratch_floats": [_i],
     "pmce_vertex_sab_split_f32": [_f, _f, _i, _i, _f, _f, _f, _f, _f, _f, _i, _s],
-    "pmce_tokens_kv_f32": [_f, _f, _f, _f, _f, _f, _f, _f, _i, _i, _i, _f, _f, _f, _f, _f, _i, _s],
     "pmce_tkv_image_floats": [],
     "pmce_tkv_pack_f16": [_f, _f, _f, _f, _s],
-    "pmce_tokens_kv_pk_f32": [_f, _f, _f, _f, _f, _f, _f, _f, _i, _i, _i, _f, _f, _f, _f, _f, _i, _f, _s],
+    "pmce_tokens_kv_f32": [_f, _f, _f, _f, _f, _f, _f, _f, _i, _i, _i, _f, _f, _f, _f, _f, _i, _f, _s],
     "pmce_joint_stream_f32": [_f, _f, _f, _f, _i, C.POINTER(C.c_void_p), C.POINTER(C.c_int), _f, _f, _f, _i, _i, _i, _s],
-    "pmce_build_final_operand_f32": [_f, _f, _f, _i, _i, _s],
-    "pmce_build_final_operand_pk_f32": [_f, _f, _f, _i, _i, _i, _s],
+    "pmce_build_final_operand_f32": [_f, _f, _f, _i, _i, _i, _s],
     "pmce_j_regress_f32": [_f, _f, _f, _f, _f, _i, _i, _i, _fl, _s],
     "pmce_sample_errors_f32": [_f, _f, _fl, _i, _f, _f, _f, _f, _i, _f, _f, _i, _i, _f, _f, _f, _f, _f, _i, _s],
     "pmce_accel_error_f32": [_f, _f, _f, _f, _i, _i, _s],

@@ -2069,24 +2069,18 @@ static int launch_ca_fold(const CaFoldArgs& a, int B, hipStream_t stream, const 
   return pmce_check_launch(what);
 }
 extern "C" int pmce_ca_image_floats(void) { return CA_IMG_STRIDE; }
-// img (may be null): the operands' f16 image per clip for pmce_vertex_ca_mlp_pk_f32's split_f16 form, [B][pmce_ca_image_floats()], J <= 23.
+// img (may be null): the operands' f16 image per clip for pmce_vertex_ca_mlp_f32's split_f16 form, [B][pmce_ca_image_floats()], J <= 23.
 // Kf / s0 / Vf may each be null when only the image is wanted.
-extern "C" int pmce_ca_fold_img_f32(const float* xk, const float* xv, const float* GB, int gb_stride, int iq, int ik, int iv,
-                                    const float* Wq, const float* bq, const float* Wk, const float* bk, const float* Wv,
-                                    const float* bv, const float* Wp, float* Kf, float* s0, float* Vf, float* img, int B, int J,
-                                    hipStream_t stream) {
+extern "C" int pmce_ca_fold_f32(const float* xk, const float* xv, const float* GB, int gb_stride, int iq, int ik, int iv,
+                                const float* Wq, const float* bq, const float* Wk, const float* bk, const float* Wv,
+                                const float* bv, const float* Wp, float* Kf, float* s0, float* Vf, float* img, int B, int J,
+                                hipStream_t stream) {
   PMCE_REQUIRE(xk && xv && GB && Wq && bq && Wk && bk && Wv && bv && Wp, "ca_fold: null pointer");
   CaFoldArgs a{};
   a.xk = xk; a.xv = xv; a.GB = GB; a.gb_stride = gb_stride; a.iq = iq; a.ik = ik; a.iv = iv;
   a.Wq = Wq; a.bq = bq; a.Wk = Wk; a.bk = bk; a.Wv = Wv; a.bv = bv; a.Wp = Wp;
   a.Kf = Kf; a.s0 = s0; a.Vf = Vf; a.img = img; a.J = J;
   return launch_ca_fold(a, B, stream, "ca_fold");
-}
-extern "C" int pmce_ca_fold_f32(const float* xk, const float* xv, const float* GB, int gb_stride, int iq, int ik, int iv,
-                                const float* Wq, const float* bq, const float* Wk, const float* bk, const float* Wv,
-                                const float* bv, const float* Wp, float* Kf, float* s0, float* Vf, int B, int J,
-                                hipStream_t stream) {
-  return pmce_ca_fold_img_f32(xk, xv, GB, gb_stride, iq, ik, iv, Wq, bq, Wk, bk, Wv, bv, Wp, Kf, s0, Vf, nullptr, B, J, stream);
 }
 // The joint side of a CoevoBlock in one launch: the joint embedding (CoevoDecoder.py:177-180,184: jf = joint_proj(jt) + joint_pos_embed,
 // xk = proj_j2v_dim(jf) + j2v_K_embed, xv = jf) followed by the fold.  jf_out [B,J,64] may be null (only the joint stream reads it).
@@ -2114,10 +2108,10 @@ extern "C" int pmce_vertex_ca_f32(const float* xq, const float* vt, const float*
 }
 
 // ffn_img: the FFN's pre-made LDS image of the f16 form (pmce_ffn_pack_f16; null = made by every workgroup from W1 / W2)
-extern "C" int pmce_adaln_mlp_pk_f32(const float* xin, const float* GB, int gb_stride, int inst, const float* W1,
-                                     const float* b1, const float* W2, const float* b2, float* yout, const float* Wc,
-                                     const float* bc, const float* vt_in, float* vt_out, int B, int split_f16,
-                                     const float* ffn_img, hipStream_t stream) {
+extern "C" int pmce_adaln_mlp_f32(const float* xin, const float* GB, int gb_stride, int inst, const float* W1,
+                                  const float* b1, const float* W2, const float* b2, float* yout, const float* Wc,
+                                  const float* bc, const float* vt_in, float* vt_out, int B, int split_f16,
+                                  const float* ffn_img, hipStream_t stream) {
   PMCE_REQUIRE(xin && GB && W1 && b1 && W2 && b2 && (yout || vt_out), "adaln_mlp: null pointer");
   PMCE_REQUIRE(!vt_out || (Wc && bc && vt_in), "adaln_mlp: coordinate head needs Wc, bc, vt_in");
   const size_t lds = (size_t)(256 * LDW64 + 64 * LDW256 + 256 + 64 + 32 + 256) * sizeof(float);
@@ -2133,33 +2127,28 @@ extern "C" int pmce_adaln_mlp_pk_f32(const float* xin, const float* GB, int gb_s
   }
   return pmce_check_launch("adaln_mlp");
 }
-extern "C" int pmce_adaln_mlp_f32(const float* xin, const float* GB, int gb_stride, int inst, const float* W1,
-                                  const float* b1, const float* W2, const float* b2, float* yout, const float* Wc,
-                                  const float* bc, const float* vt_in, float* vt_out, int B, hipStream_t stream) {
-  return pmce_adaln_mlp_pk_f32(xin, GB, gb_stride, inst, W1, b1, W2, b2, yout, Wc, bc, vt_in, vt_out, B, 0, nullptr, stream);
-}
 
 // split_f16 != 0: the FFN AND the cross-attention in the three-product f16 form - ffn_img (pmce_ffn_pack_f16; null = converted per
-// workgroup from W1 / W2) and ca_img (required: pmce_ca_fold_img_f32's / pmce_joint_prep_f32's image of the folded operands; Kf / s0 /
+// workgroup from W1 / W2) and ca_img (required: pmce_ca_fold_f32's / pmce_joint_prep_f32's image of the folded operands; Kf / s0 /
 // Vf are then not read and may be null).  J > 23: the two-launch fp32-attention form through `scratch` (needs Kf / s0 / Vf).
-extern "C" int pmce_vertex_ca_mlp_pk_f32(const float* xq, const float* vt, const float* Wv3, const float* Eq, const float* Kf,
-                                         const float* s0, const float* Vf, const float* bp, const float* GB, int gb_stride,
-                                         int inst, const float* W1, const float* b1, const float* W2, const float* b2,
-                                         float* yout, float* scratch, int B, int J, int split_f16, const float* ffn_img,
-                                         const float* ca_img, hipStream_t stream) {
+extern "C" int pmce_vertex_ca_mlp_f32(const float* xq, const float* vt, const float* Wv3, const float* Eq, const float* Kf,
+                                      const float* s0, const float* Vf, const float* bp, const float* GB, int gb_stride,
+                                      int inst, const float* W1, const float* b1, const float* W2, const float* b2,
+                                      float* yout, float* scratch, int B, int J, int split_f16, const float* ffn_img,
+                                      const float* ca_img, hipStream_t stream) {
   PMCE_REQUIRE((xq || (vt && Wv3 && Eq)) && bp && GB && W1 && b1 && W2 && b2 && yout, "vertex_ca_mlp: null pointer");
   PMCE_REQUIRE(J >= 1 && J <= 32 && B > 0, "vertex_ca_mlp: J must be in 1..32");
   if (J > 23) {  // one clip's folded operands no longer fit beside the FFN weights: the two-launch form
     PMCE_REQUIRE(scratch && Kf && s0 && Vf, "vertex_ca_mlp: J > 23 needs Kf / s0 / Vf and a [B,431,64] scratch buffer");
     PMCE_TRY(pmce_vertex_ca_f32(xq, vt, Wv3, Eq, Kf, s0, Vf, bp, scratch, B, J, stream));
-    return pmce_adaln_mlp_pk_f32(scratch, GB, gb_stride, inst, W1, b1, W2, b2, yout, nullptr, nullptr, nullptr, nullptr, B, split_f16,
-                                 ffn_img, stream);
+    return pmce_adaln_mlp_f32(scratch, GB, gb_stride, inst, W1, b1, W2, b2, yout, nullptr, nullptr, nullptr, nullptr, B, split_f16,
+                              ffn_img, stream);
   }
   const size_t lds = (size_t)(256 * LDW64 + 64 * LDW256 + 256 + 64 + 32 + CA_IMG_FLOATS(J)) * sizeof(float);
   static std::atomic<unsigned long long> attr{0}, attr_s{0};
   const int g = 2 * B < 256 ? 2 * B : 256;
   if (split_f16) {
-    PMCE_REQUIRE(ca_img && (reinterpret_cast<uintptr_t>(ca_img) & 15) == 0, "vertex_ca_mlp: the split_f16 form needs the operands' image (pmce_ca_fold_img_f32)");
+    PMCE_REQUIRE(ca_img && (reinterpret_cast<uintptr_t>(ca_img) & 15) == 0, "vertex_ca_mlp: the split_f16 form needs the operands' image (pmce_ca_fold_f32)");
     PMCE_TRY(pmce_opt_in_lds((const void*)vertex_ca_mlp_kernel<true, CAM_WAVES>, 163840, attr_s, "vertex_ca_mlp"));
     hipLaunchKernelGGL((vertex_ca_mlp_kernel<true, CAM_WAVES>), dim3(g), dim3(64 * CAM_WAVES), lds, stream, xq, vt, Wv3, Eq, Kf, s0, Vf, bp, GB, gb_stride,
                        inst, W1, b1, W2, b2, yout, B, J, ffn_img, ca_img);
@@ -2170,13 +2159,6 @@ extern "C" int pmce_vertex_ca_mlp_pk_f32(const float* xq, const float* vt, const
                        inst, W1, b1, W2, b2, yout, B, J, nullptr, nullptr);
   }
   return pmce_check_launch("vertex_ca_mlp");
-}
-extern "C" int pmce_vertex_ca_mlp_f32(const float* xq, const float* vt, const float* Wv3, const float* Eq, const float* Kf,
-                                      const float* s0, const float* Vf, const float* bp, const float* GB, int gb_stride,
-                                      int inst, const float* W1, const float* b1, const float* W2, const float* b2, float* yout,
-                                      float* scratch, int B, int J, hipStream_t stream) {
-  return pmce_vertex_ca_mlp_pk_f32(xq, vt, Wv3, Eq, Kf, s0, Vf, bp, GB, gb_stride, inst, W1, b1, W2, b2, yout, scratch, B, J, 0, nullptr,
-                                   nullptr, stream);
 }
 
 extern "C" int pmce_adaln_qkv_f32(const float* xin, const float* GB, int gb_stride, int inst, const float* Wqkv,
@@ -2239,10 +2221,10 @@ extern "C" int pmce_tkv_pack_f16(const float* Wv2j, const float* Wk, const float
 }
 // tkv_img != null: the three 64 x 64 products in the three-product f16 form from the image of pmce_tkv_pack_f16(Wv2j, Wk, Wv) (Wv2j, Wk, Wv
 // themselves are then not read)
-extern "C" int pmce_tokens_kv_pk_f32(const float* xk, const float* xv, const float* vt, const float* Wv3, const float* Ev,
-                                     const float* Wv2j, const float* Ek, const float* GB, int gb_stride, int ik, int iv,
-                                     const float* Wk, const float* bk, const float* Wv, const float* bv, float* kv, int B,
-                                     const float* tkv_img, hipStream_t stream) {
+extern "C" int pmce_tokens_kv_f32(const float* xk, const float* xv, const float* vt, const float* Wv3, const float* Ev,
+                                  const float* Wv2j, const float* Ek, const float* GB, int gb_stride, int ik, int iv,
+                                  const float* Wk, const float* bk, const float* Wv, const float* bv, float* kv, int B,
+                                  const float* tkv_img, hipStream_t stream) {
   PMCE_REQUIRE(((xk && xv) || (vt && Wv3 && Ev && Ek && (Wv2j || tkv_img))) && GB && bk && bv && kv && ((Wk && Wv) || tkv_img),
                "tokens_kv: null pointer");
   if (tkv_img) {
@@ -2254,12 +2236,6 @@ extern "C" int pmce_tokens_kv_pk_f32(const float* xk, const float* xv, const flo
                        Wk, bk, Wv, bv, kv, B, nullptr);
   }
   return pmce_check_launch("tokens_kv");
-}
-extern "C" int pmce_tokens_kv_f32(const float* xk, const float* xv, const float* vt, const float* Wv3, const float* Ev,
-                                  const float* Wv2j, const float* Ek, const float* GB, int gb_stride, int ik, int iv,
-                                  const float* Wk, const float* bk, const float* Wv, const float* bv, float* kv, int B,
-                                  hipStream_t stream) {
-  return pmce_tokens_kv_pk_f32(xk, xv, vt, Wv3, Ev, Wv2j, Ek, GB, gb_stride, ik, iv, Wk, bk, Wv, bv, kv, B, nullptr, stream);
 }
 
 extern "C" int pmce_joint_stream_f32(const float* xq, const float* jQ, const float* kv, const float* GB, int gb_stride,
@@ -2280,15 +2256,12 @@ extern "C" int pmce_joint_stream_f32(const float* xq, const float* jQ, const flo
   return pmce_check_launch("joint_stream");
 }
 
-extern "C" int pmce_build_final_operand_pk_f32(const float* g, const float* vt, float* A, int B, int KP, int packed, hipStream_t stream) {
+extern "C" int pmce_build_final_operand_f32(const float* g, const float* vt, float* A, int B, int KP, int packed, hipStream_t stream) {
   PMCE_REQUIRE(g && vt && A && KP >= 2048 + NV * 3 && (!packed || KP % 16 == 0), "build_final_operand: bad args");
   const long long n = (long long)B * KP;
   if (packed) hipLaunchKernelGGL(build_final_operand_kernel<true>, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, stream, g, vt, A, B, KP);
   else hipLaunchKernelGGL(build_final_operand_kernel<false>, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, stream, g, vt, A, B, KP);
   return pmce_check_launch("build_final_operand");
-}
-extern "C" int pmce_build_final_operand_f32(const float* g, const float* vt, float* A, int B, int KP, hipStream_t stream) {
-  return pmce_build_final_operand_pk_f32(g, vt, A, B, KP, 0, stream);
 }
 
 extern "C" int pmce_j_regress_f32(const float* mesh, const int* indptr, const int* indices, const float* data, float* out,

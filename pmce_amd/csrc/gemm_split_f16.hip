@@ -677,48 +677,22 @@ static int gemm_split_any(const float* A, const float* Wp, const float* wscale, 
   return pmce_check_launch("gemm_nt_split_f16");
 }
 
-extern "C" int pmce_gemm_nt_split_f16(const float* A, const float* Wp, const float* wscale, const float* bias, const float* R,
-                                      float* C, int M, int N, int K, long long lda, long long ldc, int act, int a_packed,
-                                      hipStream_t stream) {
-  return gemm_split_any(A, Wp, wscale, bias, R, C, M, N, K, lda, ldc, act, a_packed, 0, 0, 0, 0, stream);
-}
-extern "C" int pmce_gemm_nt_split_f16_ex(const float* A, const float* Wp, const float* wscale, const float* bias, const float* R,
-                                         float* C, int M, int N, int K, long long lda, long long ldc, int act, int a_packed,
-                                         int c_packed, hipStream_t stream) {
-  return gemm_split_any(A, Wp, wscale, bias, R, C, M, N, K, lda, ldc, act, a_packed, c_packed, 0, 0, 0, stream);
-}
-extern "C" int pmce_gemm_nt_split_f16_rowmap(const float* A, const float* Wp, const float* wscale, const float* bias, float* C,
-                                             int M, int N, int K, long long lda, int c_div, long long c_lo, long long c_hi,
-                                             hipStream_t stream) {
-  PMCE_REQUIRE(c_div > 0, "gemm_split_rowmap: c_div must be positive");
-  return gemm_split_any(A, Wp, wscale, bias, nullptr, C, M, N, K, lda, N, 0, 0, 0, c_div, c_lo, c_hi, stream);
-}
-
-// Every form above on a weight in the BLOCKED layout (pmce_gemm_pack_split_f16_blk): rscale != null -> A is row-scaled (as _rs),
-// c_div > 0 -> mapped output rows (as _rowmap; ldc == N then), else as _ex.  What the model's launch sequences call.
-extern "C" int pmce_gemm_nt_split_f16_blk(const float* A, const float* rscale, const float* Wblk, const float* wscale, const float* bias,
-                                          const float* R, float* C, int M, int N, int K, long long lda, long long ldc, int act,
-                                          int a_packed, int c_packed, int c_div, long long c_lo, long long c_hi, hipStream_t stream) {
+// The product's one entry point.  rscale != null -> A is row-scaled (Ap / rscale from pmce_split_rows_scaled_f16: raw inputs of any finite
+// fp32 magnitude; C[m][n] = 2^e(m) 2^-s(n) (Ahi Whi + Ahi Wlo + Alo Whi) + bias[n]); c_div > 0 -> mapped output rows (ldc == N then);
+// w_blocked: the weight's layout (pmce_gemm_pack_split_f16's `blocked`; 1 is what the model's launch sequences pass).
+extern "C" int pmce_gemm_nt_split_f16(const float* A, const float* rscale, const float* Wp, int w_blocked, const float* wscale,
+                                      const float* bias, const float* R, float* C, int M, int N, int K, long long lda, long long ldc,
+                                      int act, int a_packed, int c_packed, int c_div, long long c_lo, long long c_hi, hipStream_t stream) {
   PMCE_REQUIRE(c_div >= 0 && (c_div == 0 || ldc == N), "gemm_split_blk: a row map needs ldc == N");
-  return gemm_split_any(A, Wblk, wscale, bias, R, C, M, N, K, lda, ldc, act, rscale ? 1 : a_packed, c_packed, c_div, c_lo, c_hi, stream,
-                        rscale, 1);
-}
-
-// Raw inputs (any finite fp32 magnitude): Ap / rscale from pmce_split_rows_scaled_f16.  C[m][n] = 2^e(m) 2^-s(n) (Ahi Whi + Ahi Wlo +
-// Alo Whi) + bias[n]; c_div > 0 maps the output rows like pmce_gemm_nt_split_f16_rowmap (ldc = N then).
-extern "C" int pmce_gemm_nt_split_f16_rs(const float* Ap, const float* rscale, const float* Wp, const float* wscale, const float* bias,
-                                         float* C, int M, int N, int K, long long ldc, int c_div, long long c_lo, long long c_hi,
-                                         hipStream_t stream) {
-  PMCE_REQUIRE(rscale, "gemm_split_rs: null rscale");
-  PMCE_REQUIRE(c_div >= 0 && (c_div == 0 || ldc == N), "gemm_split_rs: a row map needs ldc == N");
-  return gemm_split_any(Ap, Wp, wscale, bias, nullptr, C, M, N, K, K, ldc, 0, 1, 0, c_div, c_lo, c_hi, stream, rscale);
+  return gemm_split_any(A, Wp, wscale, bias, R, C, M, N, K, lda, ldc, act, rscale ? 1 : a_packed, c_packed, c_div, c_lo, c_hi, stream,
+                        rscale, w_blocked ? 1 : 0);
 }
 
 // A product with N = 256 and a residual whose result feeds a LayerNorm chain (the proj and fc2 products of a C = 256 lifter block,
 // reference PoseEstimation.py:26-28,84-85,91-92,101-106): with x = Ap W^T + bias + R,
 //   y1 = ln1_w ? LN(x; ln1_w, ln1_b, ln1_eps) : x ;   out1 = y1 (fp32 [M,256], may alias R; may be null)
 //   out2 = LN(y1; ln2_w, ln2_b, ln2_eps) written PRE-SPLIT (the next product's A; may be null)
-// - pmce_gemm_nt_split_f16_blk followed by pmce_ln_chain_ex_f32(out2_split = 1) in one launch (64 x 256 tiles: a workgroup owns whole
+// - pmce_gemm_nt_split_f16 followed by pmce_ln_chain_f32(out2_split = 1) in one launch (64 x 256 tiles: a workgroup owns whole
 // rows).  Ap pre-split [M,K]; W packed (w_blocked: the blocked layout); statistics two-pass in fp32 like pmce_ln_chain (a different
 // summation order: the results agree to the last bits, not bit for bit).
 extern "C" int pmce_gemm_nt_split_f16_ln(const float* Ap, const float* Wp, int w_blocked, const float* wscale, const float* bias,
@@ -775,23 +749,16 @@ __global__ __launch_bounds__(256) void split_pack_kernel(const float* __restrict
     }
   }
 }
-extern "C" int pmce_gemm_pack_split_f16(const float* W, int N, int K, int ldw, float* Wp, float* wscale, hipStream_t stream) {
-  PMCE_REQUIRE(W && Wp && wscale, "gemm_pack_split: null pointer");
-  PMCE_REQUIRE(N > 0 && K > 0 && K % 16 == 0 && ldw >= K, "gemm_pack_split: need N>0, K%%16==0, ldw>=K (N=%d K=%d ldw=%d)", N, K, ldw);
-  const int blocks = (N + 3) / 4 < 4096 ? (N + 3) / 4 : 4096;
-  hipLaunchKernelGGL(split_pack_kernel, dim3(blocks), dim3(256), 0, stream, W, N, K, ldw, reinterpret_cast<_Float16*>(Wp), wscale, 0);
-  return pmce_check_launch("gemm_pack_split_f16");
-}
-// The same planes in the BLOCKED layout [ceil(N/64)][K/16][64][16 hi | 16 lo] (Wp: ceil(N/64)*64*K floats of storage; rows past N are
-// not written and never contribute): what a tile fetches per k-tile is then contiguous 4 KB pieces.  A streamed weight (one that is
-// read once per launch from HBM: the final product's 278 MB, the GRU and AdaLN projections) otherwise arrives as 64-byte pieces one
-// weight row apart - a different DRAM page per piece.
-extern "C" int pmce_gemm_pack_split_f16_blk(const float* W, int N, int K, int ldw, float* Wp, float* wscale, hipStream_t stream) {
+// blocked != 0: the same planes in the BLOCKED layout [ceil(N/64)][K/16][64][16 hi | 16 lo] (Wp: ceil(N/64)*64*K floats of storage; rows
+// past N are not written and never contribute): what a tile fetches per k-tile is then contiguous 4 KB pieces.  A streamed weight (one
+// that is read once per launch from HBM: the final product's 278 MB, the GRU and AdaLN projections) otherwise arrives as 64-byte pieces
+// one weight row apart - a different DRAM page per piece.
+extern "C" int pmce_gemm_pack_split_f16(const float* W, int N, int K, int ldw, float* Wp, float* wscale, int blocked, hipStream_t stream) {
   PMCE_REQUIRE(W && Wp && wscale, "gemm_pack_split_blk: null pointer");
   PMCE_REQUIRE(N > 0 && K > 0 && K % 16 == 0 && ldw >= K, "gemm_pack_split_blk: need N>0, K%%16==0, ldw>=K (N=%d K=%d ldw=%d)", N, K, ldw);
   const int blocks = (N + 3) / 4 < 4096 ? (N + 3) / 4 : 4096;
-  hipLaunchKernelGGL(split_pack_kernel, dim3(blocks), dim3(256), 0, stream, W, N, K, ldw, reinterpret_cast<_Float16*>(Wp), wscale, 1);
-  return pmce_check_launch("gemm_pack_split_f16_blk");
+  hipLaunchKernelGGL(split_pack_kernel, dim3(blocks), dim3(256), 0, stream, W, N, K, ldw, reinterpret_cast<_Float16*>(Wp), wscale, blocked ? 1 : 0);
+  return pmce_check_launch("gemm_pack_split_f16");
 }
 
 // A[M][lda] fp32 -> Ap[M][K/16][2][16] f16: hi = rne16(a), lo = rne16((a - hi) * 2^11)

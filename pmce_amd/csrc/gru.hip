@@ -28,7 +28,7 @@ struct GruStepArgs {
   long long gi_rs, h_rs;
   int B, H;
   const float* wscale;    // SPLIT form: [2 * 3H] 2^-s per row of the packed W_hh (direction-major, as packed: pmce_gemm_pack_split_f16)
-  int wblk;               // SPLIT form: the packed W_hh is in the BLOCKED layout [3H / 64][H / 16][64 rows][16 hi | 16 lo] (pmce_gemm_pack_split_f16_blk): a
+  int wblk;               // SPLIT form: the packed W_hh is in the BLOCKED layout [3H / 64][H / 16][64 rows][16 hi | 16 lo] (pmce_gemm_pack_split_f16, blocked): a
                           // DMA instruction's 16 rows of a k-tile are 1 KB contiguous (8 full cache lines) instead of 16 half lines one weight row apart -
                           // with every CU streaming, the L2 -> LDS path delivers 58 instead of 30 B/clk per CU (scripts/microbench/dma_patterns.hip)
 };
@@ -552,25 +552,17 @@ extern "C" int pmce_gru_step_f32(const float* gi0, const float* gi1, const float
                                  long long gi_rs, long long h_rs, int B, int H, int ndir, hipStream_t stream) {
   return gru_step_any(gi0, gi1, whh0, whh1, nullptr, bhh0, bhh1, hp0, hp1, ho0, ho1, gi_rs, h_rs, B, H, ndir, stream);
 }
-// The same step with gh = h W_hh^T in the three-product f16 form: whh0 / whh1 are rows of ONE weight packed by
-// pmce_gemm_pack_split_f16 (K = H), wscale its scale pair.
+// The same step with gh = h W_hh^T in the three-product f16 form: whh0p / whh1p are rows of ONE weight packed by pmce_gemm_pack_split_f16
+// (K = H), wscale its scale pair.  w_blocked: the weight is in the blocked layout (both directions' rows packed in ONE call, N = 6H, or one
+// direction's 3H: a direction starts on a 64-row block either way) - what the model runs: a DMA instruction's rows are contiguous.  Same
+// numbers, bit for bit, in both layouts.
 extern "C" int pmce_gru_step_split_f32(const float* gi0, const float* gi1, const float* whh0p, const float* whh1p,
                                        const float* wscale, const float* bhh0, const float* bhh1, const float* hp0,
                                        const float* hp1, float* ho0, float* ho1, long long gi_rs, long long h_rs, int B, int H,
-                                       int ndir, hipStream_t stream) {
-  PMCE_REQUIRE(wscale, "gru_step_split: null wscale");
-  return gru_step_any(gi0, gi1, whh0p, whh1p, wscale, bhh0, bhh1, hp0, hp1, ho0, ho1, gi_rs, h_rs, B, H, ndir, stream);
-}
-
-// The same on a W_hh packed by pmce_gemm_pack_split_f16_blk (both directions' rows in ONE call, N = 6H, or one direction's 3H: a direction
-// starts on a 64-row block either way): what the model runs - a DMA instruction's rows are contiguous.  Same numbers, bit for bit.
-extern "C" int pmce_gru_step_split_blk_f32(const float* gi0, const float* gi1, const float* whh0b, const float* whh1b,
-                                           const float* wscale, const float* bhh0, const float* bhh1, const float* hp0,
-                                           const float* hp1, float* ho0, float* ho1, long long gi_rs, long long h_rs, int B, int H,
-                                           int ndir, hipStream_t stream) {
+                                       int ndir, int w_blocked, hipStream_t stream) {
   PMCE_REQUIRE(wscale, "gru_step_split_blk: null wscale");
   PMCE_REQUIRE(H % 64 == 0, "gru_step_split_blk: H must be a multiple of 64");
-  return gru_step_any(gi0, gi1, whh0b, whh1b, wscale, bhh0, bhh1, hp0, hp1, ho0, ho1, gi_rs, h_rs, B, H, ndir, stream, 1);
+  return gru_step_any(gi0, gi1, whh0p, whh1p, wscale, bhh0, bhh1, hp0, hp1, ho0, ho1, gi_rs, h_rs, B, H, ndir, stream, w_blocked ? 1 : 0);
 }
 
 // joints(m) = pose3d(mm) / 1000   (reference PMCE.py:18 — a true division, kept as one)

@@ -571,7 +571,7 @@ extern "C" int pmce_embed_tokens_f32(const float* pose2d, const float* E, const 
 }
 
 // The same followed by LayerNorm(w2, b2, eps2) of every token row in one launch: x = the tokens (fp32), xn = their LayerNorm (pre-split [row][C/16][16 hi |
-// 16 lo*2^11] f16 when xn_split) - pmce_embed_tokens_f32 + pmce_ln_chain_ex_f32(out2) without the round trip of the tokens.  C = 256 or 512.
+// 16 lo*2^11] f16 when xn_split) - pmce_embed_tokens_f32 + pmce_ln_chain_f32(out2) without the round trip of the tokens.  C = 256 or 512.
 extern "C" int pmce_embed_ln_f32(const float* pose2d, const float* E, const float* Wje, const float* bje, const float* spos, float* x,
                                  long long ntok, int J, int C, const float* w2, const float* b2, float eps2, float* xn, int xn_split,
                                  hipStream_t stream) {
@@ -590,9 +590,9 @@ extern "C" int pmce_embed_ln_f32(const float* pose2d, const float* E, const floa
   return pmce_check_launch("embed_ln");
 }
 
-extern "C" int pmce_ln_chain_ex_f32(const float* x, long long rows, int C, const float* w1, const float* b1, float eps1,
-                                    const float* add, int add_div, int add_mod, float* out1, const float* w2, const float* b2,
-                                    float eps2, float* out2, int out2_split, hipStream_t stream) {
+extern "C" int pmce_ln_chain_f32(const float* x, long long rows, int C, const float* w1, const float* b1, float eps1,
+                                 const float* add, int add_div, int add_mod, float* out1, const float* w2, const float* b2,
+                                 float eps2, float* out2, int out2_split, hipStream_t stream) {
   PMCE_REQUIRE(C == 256 || C == 512, "ln_chain: C must be 256 or 512 (got %d)", C);
   PMCE_REQUIRE(rows > 0 && (out1 || out2), "ln_chain: nothing to do");
   PMCE_REQUIRE(!out2 || (w2 && b2), "ln_chain: out2 needs w2/b2");
@@ -607,17 +607,12 @@ extern "C" int pmce_ln_chain_ex_f32(const float* x, long long rows, int C, const
                        out1, w2, b2, eps2, out2, nullptr, 0, out2_split);
   return pmce_check_launch("ln_chain");
 }
-extern "C" int pmce_ln_chain_f32(const float* x, long long rows, int C, const float* w1, const float* b1, float eps1,
-                                 const float* add, int add_div, int add_mod, float* out1, const float* w2, const float* b2,
-                                 float eps2, float* out2, hipStream_t stream) {
-  return pmce_ln_chain_ex_f32(x, rows, C, w1, b1, eps1, add, add_div, add_mod, out1, w2, b2, eps2, out2, 0, stream);
-}
 
 // Streaming: tokens of W windows from the per-frame table x0[L,J,C] (= norm_s(SpatialBlocks[0](embed)), window-independent):
 //   X[w,t,j,:] = x0[frame(w,t),j,:] + tpos[t,:]  (PoseEstimation.py:87-88) ;  XN = LN(X; w2,b2,eps2)  (TemporalBlocks[0].norm1)
-extern "C" int pmce_window_tokens_ex_f32(const float* x0, const int* win, const float* tpos, const float* w2, const float* b2,
-                                         float eps2, float* X, float* XN, int W, int L, int T, int J, int C, int xn_split,
-                                         hipStream_t stream) {
+extern "C" int pmce_window_tokens_f32(const float* x0, const int* win, const float* tpos, const float* w2, const float* b2,
+                                      float eps2, float* X, float* XN, int W, int L, int T, int J, int C, int xn_split,
+                                      hipStream_t stream) {
   PMCE_REQUIRE(C == 256 || C == 512, "window_tokens: C must be 256 or 512");
   PMCE_REQUIRE(x0 && win && tpos && w2 && b2 && X && XN && W > 0 && L > 0 && T > 0 && J > 0, "window_tokens: bad args");
   const long long rows = (long long)W * T * J;
@@ -630,14 +625,9 @@ extern "C" int pmce_window_tokens_ex_f32(const float* x0, const int* win, const 
                        w2, b2, eps2, XN, win, L, xn_split);
   return pmce_check_launch("window_tokens");
 }
-extern "C" int pmce_window_tokens_f32(const float* x0, const int* win, const float* tpos, const float* w2, const float* b2,
-                                      float eps2, float* X, float* XN, int W, int L, int T, int J, int C,
-                                      hipStream_t stream) {
-  return pmce_window_tokens_ex_f32(x0, win, tpos, w2, b2, eps2, X, XN, W, L, T, J, C, 0, stream);
-}
 
 // Streaming, the demo's middle-frame override (main/run_demo.py:340-344 overwrites frame T/2 of every window before the model sees it): the
-// W * J token rows (w, t_mid, j) of X / XN, already filled by pmce_window_tokens_ex_f32, are rewritten from a SECOND per-frame table x0_mid
+// W * J token rows (w, t_mid, j) of X / XN, already filled by pmce_window_tokens_f32, are rewritten from a SECOND per-frame table x0_mid
 // ("this frame as the middle of its window"):  X = x0_mid[m(w), j, :] + tpos[t_mid, :],  XN = LN(X; w2, b2, eps2),  m(w) = start + t_mid, or
 // start when start == end.  One wavefront per row with ln_chain_kernel's lane layout, loads, additions and LayerNorm: a window whose x0_mid
 // row equals its x0 row gets the bits it already had.
@@ -742,8 +732,8 @@ static int launch_seq_attention_pair(const float* qkv, float* out, int nseq, int
   return pmce_check_launch("seq_attention");
 }
 
-extern "C" int pmce_seq_attention_ex_f32(const float* qkv, float* out, int nseq, int N, int C, int seq_div, long long seq_lo,
-                                         long long seq_hi, long long tok_stride, int out_split, hipStream_t stream) {
+extern "C" int pmce_seq_attention_f32(const float* qkv, float* out, int nseq, int N, int C, int seq_div, long long seq_lo,
+                                      long long seq_hi, long long tok_stride, int out_split, hipStream_t stream) {
   PMCE_REQUIRE(C == 256 || C == 512, "seq_attention: C must be 256 or 512 (8 heads of 32/64)");
   PMCE_REQUIRE(N >= 1 && N <= 32 && nseq > 0, "seq_attention: N must be in 1..32 (got %d)", N);
   if (seq_div <= 0) seq_div = 0x7fffffff;
@@ -770,16 +760,12 @@ extern "C" int pmce_seq_attention_ex_f32(const float* qkv, float* out, int nseq,
   }
   return pmce_check_launch("seq_attention");
 }
-extern "C" int pmce_seq_attention_f32(const float* qkv, float* out, int nseq, int N, int C, int seq_div, long long seq_lo,
-                                      long long seq_hi, long long tok_stride, hipStream_t stream) {
-  return pmce_seq_attention_ex_f32(qkv, out, nseq, N, C, seq_div, seq_lo, seq_hi, tok_stride, 0, stream);
-}
 
 // prew != null: x holds the LAST TemporalBlock's output BEFORE its post-norm; the rows pass through LayerNorm(prew, preb, pre_eps) (norm_t,
 // PoseEstimation.py:92) on the way in - the head then needs no ln_chain launch (and no 2 x 143 MB round trip at B = 256, C = 512) in front of it.
-extern "C" int pmce_lifter_head_ex_f32(const float* x, const float* prew, const float* preb, float pre_eps, const float* lnw,
-                                       const float* lnb, const float* Wr, const float* br, const float* wf, const float* bf,
-                                       float* pose3d, int B, int T, int J, int C, hipStream_t stream) {
+extern "C" int pmce_lifter_head_f32(const float* x, const float* prew, const float* preb, float pre_eps, const float* lnw,
+                                    const float* lnb, const float* Wr, const float* br, const float* wf, const float* bf,
+                                    float* pose3d, int B, int T, int J, int C, hipStream_t stream) {
   PMCE_REQUIRE(C == 256 || C == 512, "lifter_head: C must be 256 or 512");
   PMCE_REQUIRE((prew == nullptr) == (preb == nullptr), "lifter_head: the pre-norm needs weight and bias");
   PMCE_REQUIRE(T > 0 && T <= 64, "lifter_head: 1..64 frames per clip");
@@ -790,9 +776,4 @@ extern "C" int pmce_lifter_head_ex_f32(const float* x, const float* prew, const 
   else
     hipLaunchKernelGGL((lifter_head_kernel<512>), dim3(grid), dim3(threads), 0, stream, x, lnw, lnb, Wr, br, wf, bf, pose3d, B, T, J, prew, preb, pre_eps);
   return pmce_check_launch("lifter_head");
-}
-extern "C" int pmce_lifter_head_f32(const float* x, const float* lnw, const float* lnb, const float* Wr, const float* br,
-                                    const float* wf, const float* bf, float* pose3d, int B, int T, int J, int C,
-                                    hipStream_t stream) {
-  return pmce_lifter_head_ex_f32(x, nullptr, nullptr, 0.f, lnw, lnb, Wr, br, wf, bf, pose3d, B, T, J, C, stream);
 }

@@ -10,6 +10,7 @@
 
 #include <stdlib.h>
 
+#include <functional>
 #include <memory>
 #include <string>
 #include <unordered_map>
@@ -52,6 +53,14 @@ struct SplitW {
 };
 struct LifterBlockSplit {
   SplitW qkv, proj, fc1, fc2;
+};
+// everything build_split_weights fills (pointers into the split arena; split_items lists them)
+struct SplitPlanes {
+  LifterBlockSplit sblk[2][8];
+  SplitW s_ie, s_wih0, s_wih1, s_whh0, s_whh1, s_ada, s_final;
+  const float* ffn_img[3][2];  // per vertex block: the LDS images of the two FFNs' f16 form (vca, vsa)
+  const float* qkv_img[3];     // per vertex block: the self-attention qkv weight's f16 form (vertex_sab)
+  const float* tkv_img;        // the joint<-vertex direction's three 64 x 64 weights (tokens_kv), block 3
 };
 struct VertexBlockW {  // vertex side of CoevoBlock k (+ the joint-side preparation every block needs)
   const float *joint_proj_w, *joint_proj_b, *joint_pos, *j2v_w, *j2v_b, *j2v_K, *vertx_proj_w, *Eq;
@@ -101,8 +110,7 @@ struct pmce_model {
   float* caller_arena = nullptr;       // set by pmce_model_set_split_arena, consumed by the next (re)build of the planes
   size_t caller_arena_bytes = 0;
   bool split_adopted = false;          // the planes came from another handle (pmce_model_share_split_weights): finalize keeps them
-  LifterBlockSplit sblk[2][8];
-  SplitW s_ie, s_wih0, s_wih1, s_whh0, s_whh1, s_ada, s_final;
+  SplitPlanes sp = {};
   // Below this many clips per call the products stay on the fp32 pipe (PMCE_SPLIT_MIN_BATCH at create).  Default 1 = never: with
   // the two-stream schedule in both modes the f16 form is faster at every batch size (B = 1: 1.57 ms against 1.85 ms at C = 512;
   // scripts/microbench/small_batch_modes.py).  With PMCE_SPLIT_OVERLAP=0 a threshold near 48 pays: a small batch is bound by its
@@ -112,9 +120,6 @@ struct pmce_model {
   // 3.4); the library therefore contains no packed-fp32 instruction at all (build.py), which makes its kernels safe next to each
   // other.  PMCE_SPLIT_OVERLAP=0 at create restores the strictly serial schedule of the split mode (diagnostic).
   bool split_overlap = true;
-  const float* ffn_img[3][2] = {};     // per vertex block: the LDS images of the two FFNs' f16 form (vca, vsa), in the split arena
-  const float* qkv_img[3] = {};        // per vertex block: the self-attention qkv weight's f16 form (vertex_sab)
-  const float* tkv_img = nullptr;      // the joint<-vertex direction's three 64 x 64 weights (tokens_kv), block 3
   bool split_now = false;  // decision for the call in progress (set by check_ws, the first thing every entry point does)
   // Sticky "a product of this model produced a non-finite value" word: 4 bytes of pinned host memory the device can write
   // (hipHostMalloc, mapped), so that reading it costs no synchronisation.  Set by the split-f16 products' epilogues (an activation
@@ -180,10 +185,10 @@ int ev_wait(hipStream_t s, hipEvent_t e, const char* what) {
   return PMCE_OK;
 }
 
-#define RUN(cls, call)             \
-  do {                             \
-    ProfScope _ps(m, cls, stream); \
-    PMCE_TRY(call);                \
+#define RUN(cls, s, call)     \
+  do {                        \
+    ProfScope _ps(m, cls, s); \
+    PMCE_TRY(call);           \
   } while (0)
 
 // Tensor names (what pmce_model_tensor_name enumerates) and, for each, the field of m->w it resolves into.
@@ -351,6 +356,20 @@ void carve_decoder(Carver& c, const pmce_model* m, int B, DecoderWs& w) {
   w.JM = c.take((size_t)B * 32 * 3);
 }
 
+struct Workspace {
+  LifterWs lw;
+  DecoderWs dw;
+  size_t bytes;  // what the two carves took
+};
+Workspace carve(const pmce_model* m, int B, void* base, size_t cap) {
+  Carver c(base, cap);
+  Workspace w;
+  carve_lifter(c, m, B, w.lw);
+  carve_decoder(c, m, B, w.dw);
+  w.bytes = c.off;
+  return w;
+}
+
 int gemm(const float* A, const float* W, const float* bias, const float* R, float* Cc, int M, int N, int K, long long lda,
          long long ldc, int act, hipStream_t s) {
   return pmce_gemm_nt_f32(A, W, bias, R, Cc, M, N, K, lda, K, ldc, act, 0, 0, 0, 0, 0, 0, 1, 0, 0, 0, 0, s);
@@ -359,15 +378,14 @@ int gemm(const float* A, const float* W, const float* bias, const float* R, floa
 int lgemm(const pmce_model* m, const float* A, const float* W, const SplitW& sw, const float* bias, const float* R, float* Cc,
           int M, int N, int K, long long lda, long long ldc, int act, hipStream_t s, int a_packed = 0, int c_packed = 0) {
   if (m->split_now && sw.wp)
-    return pmce_gemm_nt_split_f16_blk(A, nullptr, sw.wp, sw.scale, bias, R, Cc, M, N, K, lda, ldc, act, a_packed, c_packed, 0, 0, 0, s);
+    return pmce_gemm_nt_split_f16(A, nullptr, sw.wp, 1, sw.scale, bias, R, Cc, M, N, K, lda, ldc, act, a_packed, c_packed, 0, 0, 0, s);
   PMCE_REQUIRE(!a_packed && !c_packed, "lgemm: pre-split operands need the split-f16 form");
   return gemm(A, W, bias, R, Cc, M, N, K, lda, ldc, act, s);
 }
 // In the split-f16 form the producers of the lifter blocks' GEMM operands (LayerNorm -> XN, attention -> AO, fc1 -> Hid) write
 // them pre-split (hi | lo*2^11 f16 planes in the bytes of the fp32 row): the products then spend no vector work on splitting.
+// The decoder's token-local kernels run in the same form.
 inline int pk(const pmce_model* m) { return m->split_now ? 1 : 0; }
-// the decoder's token-local kernels in the same form
-inline int pkf(const pmce_model* m) { return m->split_now ? 1 : 0; }
 
 // ---- GraphormerNet.forward --------------------------------------------------------------------------------
 // Everything up to and including SpatialBlocks[0] is PER FRAME (its attention runs over the J joints of one frame,
@@ -399,42 +417,42 @@ int lifter_block_body(pmce_model* m, int kind, int i, long long M, int nframes, 
                       const PostNorm* post = nullptr) {
   const int J = m->J, C = m->C;
   const LifterBlockW& bw = m->w.blk[kind][i];
-  const LifterBlockSplit& sw = m->sblk[kind][i];
+  const LifterBlockSplit& sw = m->sp.sblk[kind][i];
   // split mode: the attention runs on the f16 matrix pipe too (seq_attention_mfma.hip; reads the fp32 q, k, v, writes AO pre-split)
   const int N_seq = kind == 0 ? J : T;
   const bool mfma_attn = m->split_now && pmce_seq_attention_split_supported(N_seq, C);
-  RUN(P_GEMM_LIFTER, lgemm(m, w.XN, bw.qkv_w, sw.qkv, bw.qkv_b, nullptr, w.QKV,
-                          (int)M, 3 * C, C, C, 3 * C, 0, stream, pk(m)));
+  RUN(P_GEMM_LIFTER, stream, lgemm(m, w.XN, bw.qkv_w, sw.qkv, bw.qkv_b, nullptr, w.QKV,
+                                   (int)M, 3 * C, C, C, 3 * C, 0, stream, pk(m)));
   if (kind == 0) {  // sequences = frames, tokens j contiguous                      (PoseEstimation.py:78,101)
-    if (mfma_attn) RUN(P_SEQ_ATTN, pmce_seq_attention_split_f16(w.QKV, w.AO, nframes, J, C, 0, J, 0, 1, stream));
-    else RUN(P_SEQ_ATTN, pmce_seq_attention_ex_f32(w.QKV, w.AO, nframes, J, C, 0, J, 0, 1, pk(m), stream));
+    if (mfma_attn) RUN(P_SEQ_ATTN, stream, pmce_seq_attention_split_f16(w.QKV, w.AO, nframes, J, C, 0, J, 0, 1, stream));
+    else RUN(P_SEQ_ATTN, stream, pmce_seq_attention_f32(w.QKV, w.AO, nframes, J, C, 0, J, 0, 1, pk(m), stream));
   } else {  // sequences = (b,j), tokens t at stride J                              (PoseEstimation.py:87,104)
-    if (mfma_attn) RUN(P_SEQ_ATTN, pmce_seq_attention_split_f16(w.QKV, w.AO, B * J, T, C, J, 1, (long long)T * J, J, stream));
-    else RUN(P_SEQ_ATTN, pmce_seq_attention_ex_f32(w.QKV, w.AO, B * J, T, C, J, 1, (long long)T * J, J, pk(m), stream));
+    if (mfma_attn) RUN(P_SEQ_ATTN, stream, pmce_seq_attention_split_f16(w.QKV, w.AO, B * J, T, C, J, 1, (long long)T * J, J, stream));
+    else RUN(P_SEQ_ATTN, stream, pmce_seq_attention_f32(w.QKV, w.AO, B * J, T, C, J, 1, (long long)T * J, J, pk(m), stream));
   }
   const bool fuse = ln_in_product(m) && sw.proj.wp && sw.fc2.wp;
   if (fuse) {  // x += proj(attn); XN = norm2(x)
-    RUN(P_GEMM_LIFTER, pmce_gemm_nt_split_f16_ln(w.AO, sw.proj.wp, 1, sw.proj.scale, bw.proj_b, w.X, (int)M, C, nullptr, nullptr, 0.f,
-                                                 w.X, bw.norm2_w, bw.norm2_b, 1e-6f, w.XN, stream));
+    RUN(P_GEMM_LIFTER, stream, pmce_gemm_nt_split_f16_ln(w.AO, sw.proj.wp, 1, sw.proj.scale, bw.proj_b, w.X, (int)M, C, nullptr, nullptr, 0.f,
+                                                         w.X, bw.norm2_w, bw.norm2_b, 1e-6f, w.XN, stream));
   } else {
-    RUN(P_GEMM_LIFTER, lgemm(m, w.AO, bw.proj_w, sw.proj, bw.proj_b, w.X, w.X, (int)M, C,
-                            C, C, C, 0, stream, pk(m)));
-    RUN(P_LN, pmce_ln_chain_ex_f32(w.X, M, C, nullptr, nullptr, 0.f, nullptr, 1, 1, nullptr, bw.norm2_w,
-                                   bw.norm2_b, 1e-6f, w.XN, pk(m), stream));
+    RUN(P_GEMM_LIFTER, stream, lgemm(m, w.AO, bw.proj_w, sw.proj, bw.proj_b, w.X, w.X, (int)M, C,
+                                     C, C, C, 0, stream, pk(m)));
+    RUN(P_LN, stream, pmce_ln_chain_f32(w.X, M, C, nullptr, nullptr, 0.f, nullptr, 1, 1, nullptr, bw.norm2_w,
+                                        bw.norm2_b, 1e-6f, w.XN, pk(m), stream));
   }
   float* Hid = w.QKV;
-  RUN(P_GEMM_LIFTER, lgemm(m, w.XN, bw.fc1_w, sw.fc1, bw.fc1_b, nullptr, Hid, (int)M,
-                          2 * C, C, C, 2 * C, 1, stream, pk(m), pk(m)));
+  RUN(P_GEMM_LIFTER, stream, lgemm(m, w.XN, bw.fc1_w, sw.fc1, bw.fc1_b, nullptr, Hid, (int)M,
+                                   2 * C, C, C, 2 * C, 1, stream, pk(m), pk(m)));
   if (fuse && post) {  // x = norm_s/t(x + fc2(h)); XN = next norm1(x)
-    RUN(P_GEMM_LIFTER, pmce_gemm_nt_split_f16_ln(Hid, sw.fc2.wp, 1, sw.fc2.scale, bw.fc2_b, w.X, (int)M, 2 * C, post->w1, post->b1, 1e-6f,
-                                                 w.X, post->w2, post->b2, 1e-6f, post->w2 ? w.XN : nullptr, stream));
+    RUN(P_GEMM_LIFTER, stream, pmce_gemm_nt_split_f16_ln(Hid, sw.fc2.wp, 1, sw.fc2.scale, bw.fc2_b, w.X, (int)M, 2 * C, post->w1, post->b1, 1e-6f,
+                                                         w.X, post->w2, post->b2, 1e-6f, post->w2 ? w.XN : nullptr, stream));
     return PMCE_OK;
   }
-  RUN(P_GEMM_LIFTER, lgemm(m, Hid, bw.fc2_w, sw.fc2, bw.fc2_b, w.X, w.X, (int)M, C,
-                          2 * C, 2 * C, C, 0, stream, pk(m)));
+  RUN(P_GEMM_LIFTER, stream, lgemm(m, Hid, bw.fc2_w, sw.fc2, bw.fc2_b, w.X, w.X, (int)M, C,
+                                   2 * C, 2 * C, C, 0, stream, pk(m)));
   if (post)
-    RUN(P_LN, pmce_ln_chain_ex_f32(w.X, M, C, post->w1, post->b1, 1e-6f, nullptr, J, T, w.X, post->w2, post->b2, 1e-6f,
-                                   post->w2 ? w.XN : nullptr, pk(m), stream));
+    RUN(P_LN, stream, pmce_ln_chain_f32(w.X, M, C, post->w1, post->b1, 1e-6f, nullptr, J, T, w.X, post->w2, post->b2, 1e-6f,
+                                        post->w2 ? w.XN : nullptr, pk(m), stream));
   return PMCE_OK;
 }
 
@@ -445,14 +463,14 @@ int lifter_block_body(pmce_model* m, int kind, int i, long long M, int nframes, 
 // operands (no split work in their k-loops).  Must run before the two branches fork.
 int prep_features(pmce_model* m, const float* img_feat, int nframes, LifterWs& w, hipStream_t stream) {
   if (!m->split_now) return PMCE_OK;
-  RUN(P_MISC, pmce_split_rows_scaled_f16(img_feat, nframes, F, F, w.FS, w.FR, stream));
+  RUN(P_MISC, stream, pmce_split_rows_scaled_f16(img_feat, nframes, F, F, w.FS, w.FR, stream));
   return PMCE_OK;
 }
 
 // a product on the row-scaled feature planes (optionally with mapped output rows)
 int rs_gemm(const pmce_model* m, const float* FS, const float* FR, const SplitW& sw, const float* bias, float* Cc, int M, int N,
             long long ldc, int c_div, long long c_lo, long long c_hi, hipStream_t s) {
-  return pmce_gemm_nt_split_f16_blk(FS, FR, sw.wp, sw.scale, bias, nullptr, Cc, M, N, F, F, ldc, 0, 1, 0, c_div, c_lo, c_hi, s);
+  return pmce_gemm_nt_split_f16(FS, FR, sw.wp, 1, sw.scale, bias, nullptr, Cc, M, N, F, F, ldc, 0, 1, 0, c_div, c_lo, c_hi, s);
 }
 
 // embedding + SpatialBlocks[0] over `nframes` frames; leaves the block output (before norm_s) in w.X
@@ -460,33 +478,23 @@ int lifter_frames(pmce_model* m, const float* pose2d, const float* img_feat, int
   const int J = m->J, C = m->C;
   const long long M = (long long)nframes * J;
   PMCE_REQUIRE(M < (1ll << 31), "lifter: too many tokens");
-  if (m->split_now && m->s_ie.wp)
-    RUN(P_GEMM_LIFTER, rs_gemm(m, w.FS, w.FR, m->s_ie, m->w.ie_b, w.E, nframes, C, C, 0, 0, 0, stream));
+  if (m->split_now && m->sp.s_ie.wp)
+    RUN(P_GEMM_LIFTER, stream, rs_gemm(m, w.FS, w.FR, m->sp.s_ie, m->w.ie_b, w.E, nframes, C, C, 0, 0, 0, stream));
   else
-    RUN(P_GEMM_LIFTER, lgemm(m, img_feat, m->w.ie_w, m->s_ie, m->w.ie_b, nullptr, w.E,
-                            nframes, C, F, F, C, 0, stream));
+    RUN(P_GEMM_LIFTER, stream, lgemm(m, img_feat, m->w.ie_w, m->sp.s_ie, m->w.ie_b, nullptr, w.E,
+                                     nframes, C, F, F, C, 0, stream));
   // tokens + SpatialBlocks[0].norm1 in one pass (the tokens do not travel to HBM and back between the two)
-  RUN(P_EMBED, pmce_embed_ln_f32(pose2d, w.E, m->w.je_w, m->w.je_b, m->w.spos, w.X, M, J, C, m->w.blk[0][0].norm1_w,
-                                 m->w.blk[0][0].norm1_b, 1e-6f, w.XN, pk(m), stream));
+  RUN(P_EMBED, stream, pmce_embed_ln_f32(pose2d, w.E, m->w.je_w, m->w.je_b, m->w.spos, w.X, M, J, C, m->w.blk[0][0].norm1_w,
+                                         m->w.blk[0][0].norm1_b, 1e-6f, w.XN, pk(m), stream));
   return lifter_block_body(m, 0, 0, M, nframes, 0, w, stream);
 }
 
 // post-norm of block (kind, i): norm_s / norm_t (shared across depth, eps 1e-6), + temporal_pos_embed after the first
 // spatial block, fused with the NEXT block's norm1
 int lifter_post_norm(pmce_model* m, int kind, int i, long long M, LifterWs& w, hipStream_t stream) {
-  const int J = m->J, C = m->C;
-  const float* nw = kind == 0 ? m->w.ns_w : m->w.nt_w;
-  const float* nb = kind == 0 ? m->w.ns_b : m->w.nt_b;
+  const PostNorm pn = post_norm_of(m, kind, i);
   const float* add = (kind == 0 && i == 0) ? m->w.tpos : nullptr;
-  const float *w2 = nullptr, *b2 = nullptr;
-  if (kind == 0) {
-    w2 = m->w.blk[1][i].norm1_w;
-    b2 = m->w.blk[1][i].norm1_b;
-  } else if (i + 1 < m->depth) {
-    w2 = m->w.blk[0][i + 1].norm1_w;
-    b2 = m->w.blk[0][i + 1].norm1_b;
-  }
-  RUN(P_LN, pmce_ln_chain_ex_f32(w.X, M, C, nw, nb, 1e-6f, add, J, T, w.X, w2, b2, 1e-6f, w2 ? w.XN : nullptr, pk(m), stream));
+  RUN(P_LN, stream, pmce_ln_chain_f32(w.X, M, m->C, pn.w1, pn.b1, 1e-6f, add, m->J, T, w.X, pn.w2, pn.b2, 1e-6f, pn.w2 ? w.XN : nullptr, pk(m), stream));
   return PMCE_OK;
 }
 
@@ -506,8 +514,8 @@ int lifter_rest(pmce_model* m, float* pose3d, int B, LifterWs& w, hipStream_t st
       PMCE_TRY(lifter_block_body(m, kind, i, M, B * T, B, w, stream, head_pre ? nullptr : &pn));
     }
   }
-  RUN(P_HEAD, pmce_lifter_head_ex_f32(w.X, head_pre ? m->w.nt_w : nullptr, head_pre ? m->w.nt_b : nullptr, 1e-6f, m->w.reg0_w, m->w.reg0_b,
-                                      m->w.reg1_w, m->w.reg1_b, m->w.fus_w, m->w.fus_b, pose3d, B, T, J, C, stream));
+  RUN(P_HEAD, stream, pmce_lifter_head_f32(w.X, head_pre ? m->w.nt_w : nullptr, head_pre ? m->w.nt_b : nullptr, 1e-6f, m->w.reg0_w, m->w.reg0_b,
+                                           m->w.reg1_w, m->w.reg1_b, m->w.fus_w, m->w.fus_b, pose3d, B, T, J, C, stream));
   return PMCE_OK;
 }
 
@@ -522,7 +530,7 @@ int lifter_impl(pmce_model* m, const float* pose2d, const float* img_feat, float
 int gru_layer(pmce_model* m, int layer, const float* gi_f, const float* gi_b, long long gi_rs, int t_f0, int t_b0,
               int nsteps_f, int nsteps_b, float* Y, int B, hipStream_t stream) {
   // direction 0 walks t = t_f0, t_f0+1, ...; direction 1 walks t = t_b0, t_b0-1, ...  Y is [T][B][2*GH].
-  const SplitW& sw = layer == 0 ? m->s_whh0 : m->s_whh1;
+  const SplitW& sw = layer == 0 ? m->sp.s_whh0 : m->sp.s_whh1;
   const bool split = m->split_now && sw.wp;
   const float* whh = split ? sw.wp : (layer == 0 ? m->w.whh0 : m->w.whh1);  // the packed rows keep the fp32 row stride
   const float* bhh = layer == 0 ? m->w.bhh0 : m->w.bhh1;
@@ -530,7 +538,7 @@ int gru_layer(pmce_model* m, int layer, const float* gi_f, const float* gi_b, lo
   auto step = [&](const float* gi0, const float* gi1, const float* w0, const float* w1, const float* b0, const float* b1,
                   const float* hp0, const float* hp1, float* ho0, float* ho1, int ndir) {
     const float* scale = split ? sw.scale + (w0 == whh ? 0 : 3 * GH) : nullptr;
-    return split ? pmce_gru_step_split_blk_f32(gi0, gi1, w0, w1, scale, b0, b1, hp0, hp1, ho0, ho1, gi_rs, 2 * GH, B, GH, ndir, stream)
+    return split ? pmce_gru_step_split_f32(gi0, gi1, w0, w1, scale, b0, b1, hp0, hp1, ho0, ho1, gi_rs, 2 * GH, B, GH, ndir, 1, stream)
                  : pmce_gru_step_f32(gi0, gi1, w0, w1, b0, b1, hp0, hp1, ho0, ho1, gi_rs, 2 * GH, B, GH, ndir, stream);
   };
   const long long YS = (long long)B * 2 * GH;
@@ -547,11 +555,11 @@ int gru_layer(pmce_model* m, int layer, const float* gi_f, const float* gi_b, lo
     const float* whh_b = whh + (long long)3 * GH * GH;
     const float* bhh_b = bhh + 3 * GH;
     if (af && ab)
-      RUN(P_GRU_STEP, step(gif, gib, whh, whh_b, bhh, bhh_b, hp_f, hp_b, ho_f, ho_b, 2));
+      RUN(P_GRU_STEP, stream, step(gif, gib, whh, whh_b, bhh, bhh_b, hp_f, hp_b, ho_f, ho_b, 2));
     else if (af)
-      RUN(P_GRU_STEP, step(gif, nullptr, whh, nullptr, bhh, nullptr, hp_f, nullptr, ho_f, nullptr, 1));
+      RUN(P_GRU_STEP, stream, step(gif, nullptr, whh, nullptr, bhh, nullptr, hp_f, nullptr, ho_f, nullptr, 1));
     else
-      RUN(P_GRU_STEP, step(gib, nullptr, whh_b, nullptr, bhh_b, nullptr, hp_b, nullptr, ho_b, nullptr, 1));
+      RUN(P_GRU_STEP, stream, step(gib, nullptr, whh_b, nullptr, bhh_b, nullptr, hp_b, nullptr, ho_b, nullptr, 1));
   }
   return PMCE_OK;
 }
@@ -565,12 +573,12 @@ int gru_part(pmce_model* m, const float* img_feat, const LifterWs& lw, int B, De
   // ---- bi-GRU over the 16 frames (CoevoDecoder.py:228); buffers are time-major [t][b][.] ----
   // layer 0 input projections for both directions in one product: rows (b,t) of img_feat -> rows (t,b) of GI0
   // (split mode: from the row-scaled planes of prep_features)
-  if (m->split_now && m->s_wih0.wp)
-    RUN(P_GEMM_GRU_IN, rs_gemm(m, lw.FS, lw.FR, m->s_wih0, m->w.bih0, w.GI0, B * T, 6 * GH, 6 * GH, T, (long long)B * 6 * GH, 6 * GH, stream));
+  if (m->split_now && m->sp.s_wih0.wp)
+    RUN(P_GEMM_GRU_IN, stream, rs_gemm(m, lw.FS, lw.FR, m->sp.s_wih0, m->w.bih0, w.GI0, B * T, 6 * GH, 6 * GH, T, (long long)B * 6 * GH, 6 * GH, stream));
   else
-    RUN(P_GEMM_GRU_IN, pmce_gemm_nt_f32(img_feat, m->w.wih0, m->w.bih0, nullptr, w.GI0, B * T,
-                                        6 * GH, F, F, F, 6 * GH, 0, 0, 0, 0, T, (long long)B * 6 * GH, 6 * GH, 1, 0, 0, 0, 0,
-                                        stream));
+    RUN(P_GEMM_GRU_IN, stream, pmce_gemm_nt_f32(img_feat, m->w.wih0, m->w.bih0, nullptr, w.GI0, B * T,
+                                                6 * GH, F, F, F, 6 * GH, 0, 0, 0, 0, T, (long long)B * 6 * GH, 6 * GH, 1, 0, 0, 0, 0,
+                                                stream));
   return gru_rest(m, B, w, stream);
 }
 
@@ -580,29 +588,29 @@ int gru_rest(pmce_model* m, int B, DecoderWs& w, hipStream_t stream) {
   // layer 1: only y[8] is consumed (CoevoDecoder.py:229,241-243) -> fwd needs t = 0..8, bwd t = 15..8.
   float* GI1f = w.GI1;
   float* GI1b = w.GI1 + (long long)9 * B * 3 * GH;
-  SplitW wih1_b = m->s_wih1;  // rows 3072.. of the packed weight (same row stride as the fp32 one) and of its per-row 2^-s
+  SplitW wih1_b = m->sp.s_wih1;  // rows 3072.. of the packed weight (same row stride as the fp32 one) and of its per-row 2^-s
   if (wih1_b.wp) {
     wih1_b.wp += (long long)3 * GH * 2 * GH;
     wih1_b.scale += 3 * GH;
   }
   // Split-f16 form (round 6): layer 0's output is split ONCE (34 MB at B = 256, one HBM-rate pass) instead of inside the two products' k-loops,
   // where splitting an fp32 operand costs 80 vector instructions per k-tile and wave - matrix time.  The same planes, the same results.
-  const bool y0_packed = m->split_now && m->s_wih1.wp;
+  const bool y0_packed = m->split_now && m->sp.s_wih1.wp;
   const float* y0 = w.Y0;
   if (y0_packed) {
-    RUN(P_GEMM_GRU_IN, pmce_split_rows_f16(w.Y0, (long long)T * B, 2 * GH, 2 * GH, w.Y0P, stream));
+    RUN(P_GEMM_GRU_IN, stream, pmce_split_rows_f16(w.Y0, (long long)T * B, 2 * GH, 2 * GH, w.Y0P, stream));
     y0 = w.Y0P;
   }
-  RUN(P_GEMM_GRU_IN, lgemm(m, y0, m->w.wih1, m->s_wih1, m->w.bih1, nullptr, GI1f, 9 * B, 3 * GH, 2 * GH, 2 * GH,
-                           3 * GH, 0, stream, y0_packed ? 1 : 0));
-  RUN(P_GEMM_GRU_IN, lgemm(m, y0 + (long long)8 * B * 2 * GH, m->w.wih1 + (long long)3 * GH * 2 * GH, wih1_b,
-                           m->w.bih1 + 3 * GH, nullptr, GI1b, 8 * B, 3 * GH, 2 * GH, 2 * GH, 3 * GH, 0, stream, y0_packed ? 1 : 0));
+  RUN(P_GEMM_GRU_IN, stream, lgemm(m, y0, m->w.wih1, m->sp.s_wih1, m->w.bih1, nullptr, GI1f, 9 * B, 3 * GH, 2 * GH, 2 * GH,
+                                   3 * GH, 0, stream, y0_packed ? 1 : 0));
+  RUN(P_GEMM_GRU_IN, stream, lgemm(m, y0 + (long long)8 * B * 2 * GH, m->w.wih1 + (long long)3 * GH * 2 * GH, wih1_b,
+                                   m->w.bih1 + 3 * GH, nullptr, GI1b, 8 * B, 3 * GH, 2 * GH, 2 * GH, 3 * GH, 0, stream, y0_packed ? 1 : 0));
   PMCE_TRY(gru_layer(m, 1, GI1f, GI1b, 3 * GH, 0, T - 1, 9, 8, w.Y1, B, stream));
   const float* g = w.Y1 + (long long)8 * B * 2 * GH;  // img_feat = y[seqlen // 2], [B, 2048]
 
   // ---- all live AdaLN gamma/beta in one product (CoevoDecoder.py:19-20,27-28) ----
-  RUN(P_GEMM_ADA, lgemm(m, g, m->w.ada_w, m->s_ada, m->w.ada_b, nullptr, w.GB, B, N_ADA * 128, 2 * GH, 2 * GH,
-                        N_ADA * 128, 0, stream));
+  RUN(P_GEMM_ADA, stream, lgemm(m, g, m->w.ada_w, m->sp.s_ada, m->w.ada_b, nullptr, w.GB, B, N_ADA * 128, 2 * GH, 2 * GH,
+                                N_ADA * 128, 0, stream));
   return PMCE_OK;
 }
 
@@ -614,12 +622,12 @@ int joint_prep(pmce_model* m, int k, const float* joints, int B, DecoderWs& w, h
   const int ib = (k - 1) * 6, gbs = N_ADA * 128;
   // one launch: joint embedding + fold.  The f16 form of the fused vertex kernel reads the operands' image only (J <= 23); the fp32
   // form (and the two-launch fallback beyond J = 23) the fp32 operands.  jf is read by the joint stream of block 3 only.
-  const bool image = pkf(m) && J <= 23;
-  RUN(P_CA_FOLD, pmce_joint_prep_f32(joints, v.joint_proj_w, v.joint_proj_b, v.joint_pos, v.j2v_w, v.j2v_b, v.j2v_K,
-                                     k == 3 ? w.JF[k - 1] : nullptr, w.GB, gbs, ib + 0, ib + 1, ib + 2, v.vca_wq_w, v.vca_wq_b, v.vca_wk_w,
-                                     v.vca_wk_b, v.vca_wv_w, v.vca_wv_b, v.vca_proj_w, image ? nullptr : w.KF[k - 1],
-                                     image ? nullptr : w.S0[k - 1], image ? nullptr : w.VF[k - 1], image ? w.CAI[k - 1] : nullptr, B, J,
-                                     stream));
+  const bool image = pk(m) && J <= 23;
+  RUN(P_CA_FOLD, stream, pmce_joint_prep_f32(joints, v.joint_proj_w, v.joint_proj_b, v.joint_pos, v.j2v_w, v.j2v_b, v.j2v_K,
+                                             k == 3 ? w.JF[k - 1] : nullptr, w.GB, gbs, ib + 0, ib + 1, ib + 2, v.vca_wq_w, v.vca_wq_b, v.vca_wk_w,
+                                             v.vca_wk_b, v.vca_wv_w, v.vca_wv_b, v.vca_proj_w, image ? nullptr : w.KF[k - 1],
+                                             image ? nullptr : w.S0[k - 1], image ? nullptr : w.VF[k - 1], image ? w.CAI[k - 1] : nullptr, B, J,
+                                             stream));
   return PMCE_OK;
 }
 
@@ -628,13 +636,13 @@ int joint_branch(pmce_model* m, const float* joints, const float* vt_in, float* 
                  hipStream_t stream) {
   const int J = m->J, gbs = N_ADA * 128;
   const JointBlockW& jw = m->w.jb;
-  RUN(P_TOKENS_KV, pmce_tokens_kv_pk_f32(nullptr, nullptr, vt_in, m->w.vb[2].vertx_proj_w, jw.Ev,
-                                         jw.v2j_w, jw.Ek, w.GB, gbs, 19, 20,
-                                         jw.jca_wk_w, jw.jca_wk_b, jw.jca_wv_w,
-                                         jw.jca_wv_b, w.KVJ, B, pkf(m) ? m->tkv_img : nullptr, stream));
+  RUN(P_TOKENS_KV, stream, pmce_tokens_kv_f32(nullptr, nullptr, vt_in, m->w.vb[2].vertx_proj_w, jw.Ev,
+                                              jw.v2j_w, jw.Ek, w.GB, gbs, 19, 20,
+                                              jw.jca_wk_w, jw.jca_wk_b, jw.jca_wv_w,
+                                              jw.jca_wv_b, w.KVJ, B, pk(m) ? m->sp.tkv_img : nullptr, stream));
   const int inst[4] = {18, 21, 22, 23};
-  RUN(P_JOINT_STREAM, pmce_joint_stream_f32(w.JF[2], jw.j_Q, w.KVJ, w.GB, gbs, jw.stream, inst, joints, nullptr,
-                                            cam_pose, B, J, 3, stream));
+  RUN(P_JOINT_STREAM, stream, pmce_joint_stream_f32(w.JF[2], jw.j_Q, w.KVJ, w.GB, gbs, jw.stream, inst, joints, nullptr,
+                                                    cam_pose, B, J, 3, stream));
   return PMCE_OK;
 }
 
@@ -645,19 +653,19 @@ int vertex_block(pmce_model* m, int k, const float* vt_cur, float* vt_next, int 
   const VertexBlockW& v = m->w.vb[k - 1];
   const int ib = (k - 1) * 6;  // AdaLN instances: vca.normq,normk,normv,norm2, vsa.norm1,norm2
   // CrossAttentionBlock (CoevoDecoder.py:82-87) in one launch (J > 23: the launcher's two-launch form through F1)
-  RUN(P_VERTEX_CA_MLP, pmce_vertex_ca_mlp_pk_f32(nullptr, vt_cur, v.vertx_proj_w, v.Eq, w.KF[k - 1], w.S0[k - 1], w.VF[k - 1],
-                                                 v.vca_proj_b, w.GB, gbs, ib + 3, v.vca_fc1_w, v.vca_fc1_b, v.vca_fc2_w,
-                                                 v.vca_fc2_b, w.F2, w.F1, B, J, pkf(m), m->ffn_img[k - 1][0], w.CAI[k - 1], stream));
-  if (pkf(m)) {  // AdaLN + qkv + attention + proj + residual in one launch (coevo.hip vertex_sab)
-    RUN(P_VERTEX_SA, pmce_vertex_sab_split_f32(w.F2, w.GB, gbs, ib + 4, m->qkv_img[k - 1], v.vsa_qkv_b, v.vsa_proj_w, v.vsa_proj_b, w.QKV,
-                                               w.F1, B, stream));
+  RUN(P_VERTEX_CA_MLP, stream, pmce_vertex_ca_mlp_f32(nullptr, vt_cur, v.vertx_proj_w, v.Eq, w.KF[k - 1], w.S0[k - 1], w.VF[k - 1],
+                                                      v.vca_proj_b, w.GB, gbs, ib + 3, v.vca_fc1_w, v.vca_fc1_b, v.vca_fc2_w,
+                                                      v.vca_fc2_b, w.F2, w.F1, B, J, pk(m), m->sp.ffn_img[k - 1][0], w.CAI[k - 1], stream));
+  if (pk(m)) {  // AdaLN + qkv + attention + proj + residual in one launch (coevo.hip vertex_sab)
+    RUN(P_VERTEX_SA, stream, pmce_vertex_sab_split_f32(w.F2, w.GB, gbs, ib + 4, m->sp.qkv_img[k - 1], v.vsa_qkv_b, v.vsa_proj_w, v.vsa_proj_b, w.QKV,
+                                                       w.F1, B, stream));
   } else {
-    RUN(P_ADALN_QKV, pmce_adaln_qkv_f32(w.F2, w.GB, gbs, ib + 4, v.vsa_qkv_w, v.vsa_qkv_b, w.QKV, B, stream));
-    RUN(P_VERTEX_SA, pmce_vertex_sa_f32(w.F2, w.QKV, v.vsa_proj_w, v.vsa_proj_b, w.F1, B, stream));
+    RUN(P_ADALN_QKV, stream, pmce_adaln_qkv_f32(w.F2, w.GB, gbs, ib + 4, v.vsa_qkv_w, v.vsa_qkv_b, w.QKV, B, stream));
+    RUN(P_VERTEX_SA, stream, pmce_vertex_sa_f32(w.F2, w.QKV, v.vsa_proj_w, v.vsa_proj_b, w.F1, B, stream));
   }
-  RUN(P_ADALN_MLP, pmce_adaln_mlp_pk_f32(w.F1, w.GB, gbs, ib + 5, v.vsa_fc1_w, v.vsa_fc1_b,
-                                         v.vsa_fc2_w, v.vsa_fc2_b, nullptr,
-                                         v.vcoor_w, v.vcoor_b, vt_cur, vt_next, B, pkf(m), m->ffn_img[k - 1][1], stream));
+  RUN(P_ADALN_MLP, stream, pmce_adaln_mlp_f32(w.F1, w.GB, gbs, ib + 5, v.vsa_fc1_w, v.vsa_fc1_b,
+                                              v.vsa_fc2_w, v.vsa_fc2_b, nullptr,
+                                              v.vcoor_w, v.vcoor_b, vt_cur, vt_next, B, pk(m), m->sp.ffn_img[k - 1][1], stream));
   return PMCE_OK;
 }
 
@@ -676,7 +684,7 @@ int coevo_part(pmce_model* m, const float* joints, float* cam_pose, float* cam_m
     PMCE_TRY(ev_record(m->ev_b, side, "coevo join b"));
   }
   // ---- vertex init (CoevoDecoder.py:232) ----
-  RUN(P_GATHER, pmce_vertex_init_gather_f32(joints, m->w.vj, w.VT[0], B, J, stream));
+  RUN(P_GATHER, stream, pmce_vertex_init_gather_f32(joints, m->w.vj, w.VT[0], B, J, stream));
   PMCE_TRY(joint_prep(m, 1, joints, B, w, stream));
   float* vt_cur = w.VT[0];
   for (int k = 1; k <= 3; ++k) {
@@ -702,15 +710,14 @@ int coevo_part(pmce_model* m, const float* joints, float* cam_pose, float* cam_m
   }
   // ---- 431 -> 6890 upsample conv + 3 residual Linear(2048->6890) as ONE product (CoevoDecoder.py:238-244) ----
   // (split mode: the operand is written pre-split - the product's k-loop spends no vector instruction on splitting it)
-  const int fa_packed = (m->split_now && m->s_final.wp) ? 1 : 0;
-  RUN(P_FINAL_OP, pmce_build_final_operand_pk_f32(g, vt_cur, w.FA, B, FINAL_K, fa_packed, stream));
-  RUN(P_GEMM_FINAL, lgemm(m, w.FA, m->w.final_w, m->s_final, m->w.final_b, nullptr, cam_mesh, B, NVF * 3, FINAL_K,
-                          FINAL_K, NVF * 3, 0, stream, fa_packed));
+  const int fa_packed = (m->split_now && m->sp.s_final.wp) ? 1 : 0;
+  RUN(P_FINAL_OP, stream, pmce_build_final_operand_f32(g, vt_cur, w.FA, B, FINAL_K, fa_packed, stream));
+  RUN(P_GEMM_FINAL, stream, lgemm(m, w.FA, m->w.final_w, m->sp.s_final, m->w.final_b, nullptr, cam_mesh, B, NVF * 3, FINAL_K,
+                                  FINAL_K, NVF * 3, 0, stream, fa_packed));
   if (side) PMCE_TRY(ev_wait(stream, m->ev_d, "coevo join d"));  // cam_pose is written by the side stream
   return PMCE_OK;
 }
 
-// second stream + fork/join events, created on first use
 // pmce_model_wait_lifter: the point of a forward after which only its decoder is left
 int mark_lifter_done(pmce_model* m, hipStream_t stream) {
   if (!m->ev_lifter && hipEventCreateWithFlags(&m->ev_lifter, hipEventDisableTiming) != hipSuccess) {
@@ -735,8 +742,9 @@ int fail_after_fork(pmce_model* m, hipStream_t stream, int rc) {
 // split-f16 form keeps the two-stream schedule; split_overlap = false (PMCE_SPLIT_OVERLAP=0) sends everything down one stream.
 bool two_streams(const pmce_model* m) { return m->concurrent && (!m->split_now || m->split_overlap); }
 
+// second stream + fork/join events of a call that forks, created on first use
 int ensure_side(pmce_model* m) {
-  if (m->side) return PMCE_OK;
+  if (m->side || !two_streams(m)) return PMCE_OK;
   int lo = 0, hi = 0;
   (void)hipDeviceGetStreamPriorityRange(&lo, &hi);
   bool ok = hipStreamCreateWithPriority(&m->side, hipStreamNonBlocking, hi) == hipSuccess;
@@ -756,23 +764,64 @@ namespace {
 // (Re)build the packed f16 planes of every large weight in model-owned memory, or drop them (fp32 mode).  A load-time step, like
 // the packing the host side does: runs on `stream` - the stream the caller produced the fp32 weights on (a torch side stream is
 // non-blocking: the null stream would NOT be ordered behind it) - and waits for that stream only.
-struct SplitItem { const float* w; int n, k; SplitW* dst; };
-size_t split_item_floats(int n, int k) { return ((((size_t)n + 63) & ~(size_t)63) * k) + (((size_t)n + 63) & ~(size_t)63); }  // planes (rows padded to the 64-row blocks of the blocked layout) + 2^-s per row
-size_t ffn_img_floats() { return ((size_t)pmce_ffn_image_floats() + 63) & ~(size_t)63; }  // one FFN's LDS image (coevo.hip), 256-byte granules
-size_t qkv_img_floats() { return ((size_t)pmce_qkv_image_floats() + 63) & ~(size_t)63; }
-size_t tkv_img_floats() { return ((size_t)pmce_tkv_image_floats() + 63) & ~(size_t)63; }
-// bytes of the planes of a model with / without lifter and decoder
-size_t split_bytes_for(int C, int depth, bool lifter, bool decoder) {
-  size_t f = 0;
+// One entry per thing the arena holds, in arena order: a weight's planes + its per-row 2^-s, or one of the decoder's three kinds of LDS image.
+struct SplitItem {
+  size_t floats;                                   // what it takes of the arena (256-byte granules)
+  std::function<int(float*, hipStream_t)> pack;  // fills them at the pointer given and records it in the model's SplitPlanes
+};
+// the planes of a model of (C, depth) with / without lifter and decoder: from the weights `w`, recorded in `sp`
+std::vector<SplitItem> split_items(const Weights& w, SplitPlanes& sp, int C, int depth, bool lifter, bool decoder) {
+  std::vector<SplitItem> items;
+  auto pad64 = [](size_t n) { return (n + 63) & ~(size_t)63; };
+  // every weight in the blocked layout (what a tile - or a GRU step's workgroup - fetches per k-tile is contiguous): rows padded to its 64-row blocks
+  auto weight = [&](const float* W, int n, int k, SplitW& dst) {
+    const size_t planes = pad64(n) * k;
+    items.push_back({planes + pad64(n), [=, &dst](float* p, hipStream_t s) {
+                       dst = {p, p + planes};
+                       return pmce_gemm_pack_split_f16(W, n, k, k, p, p + planes, 1, s);
+                     }});
+  };
+  auto image = [&](int floats, const float*& dst, std::function<int(float*, hipStream_t)> fill) {
+    items.push_back({pad64(floats), [=, &dst](float* p, hipStream_t s) {
+                       dst = p;
+                       return fill(p, s);
+                     }});
+  };
   if (lifter) {
-    f += split_item_floats(C, F);
-    f += 2 * (size_t)depth * (split_item_floats(3 * C, C) + split_item_floats(C, C) + split_item_floats(2 * C, C) + split_item_floats(C, 2 * C));
+    weight(w.ie_w, C, F, sp.s_ie);
+    for (int kind = 0; kind < 2; ++kind)
+      for (int i = 0; i < depth; ++i) {
+        const LifterBlockW& bw = w.blk[kind][i];
+        LifterBlockSplit& sw = sp.sblk[kind][i];
+        weight(bw.qkv_w, 3 * C, C, sw.qkv);
+        weight(bw.proj_w, C, C, sw.proj);
+        weight(bw.fc1_w, 2 * C, C, sw.fc1);
+        weight(bw.fc2_w, C, 2 * C, sw.fc2);
+      }
   }
-  if (decoder)
-    f += split_item_floats(6 * GH, F) + split_item_floats(6 * GH, 2 * GH) + 2 * split_item_floats(6 * GH, GH) +
-         split_item_floats(N_ADA * 128, 2 * GH) + split_item_floats(NVF * 3, FINAL_K) + 6 * ffn_img_floats() + 3 * qkv_img_floats() +
-         tkv_img_floats();
-  return f * sizeof(float);
+  if (decoder) {
+    weight(w.wih0, 6 * GH, F, sp.s_wih0);
+    weight(w.wih1, 6 * GH, 2 * GH, sp.s_wih1);
+    weight(w.whh0, 6 * GH, GH, sp.s_whh0);  // recurrent weights, both directions: gru_step's three-product form
+    weight(w.whh1, 6 * GH, GH, sp.s_whh1);
+    weight(w.ada_w, N_ADA * 128, 2 * GH, sp.s_ada);
+    weight(w.final_w, NVF * 3, FINAL_K, sp.s_final);
+    // the decoder FFNs' and qkv weights' LDS images (coevo.hip): every workgroup of their launches copies one (LDS-DMA) instead of converting
+    for (int k = 0; k < 3; ++k) {
+      const VertexBlockW& v = w.vb[k];
+      image(pmce_ffn_image_floats(), sp.ffn_img[k][0], [&v](float* p, hipStream_t s) { return pmce_ffn_pack_f16(v.vca_fc1_w, v.vca_fc2_w, p, s); });
+      image(pmce_ffn_image_floats(), sp.ffn_img[k][1], [&v](float* p, hipStream_t s) { return pmce_ffn_pack_f16(v.vsa_fc1_w, v.vsa_fc2_w, p, s); });
+      image(pmce_qkv_image_floats(), sp.qkv_img[k], [&v](float* p, hipStream_t s) { return pmce_qkv_pack_f16(v.vsa_qkv_w, p, s); });
+    }
+    const JointBlockW& j = w.jb;
+    image(pmce_tkv_image_floats(), sp.tkv_img, [&j](float* p, hipStream_t s) { return pmce_tkv_pack_f16(j.v2j_w, j.jca_wk_w, j.jca_wv_w, p, s); });
+  }
+  return items;
+}
+size_t split_floats(const std::vector<SplitItem>& items) {
+  size_t f = 0;
+  for (auto& it : items) f += it.floats;
+  return f;
 }
 int build_split_weights(pmce_model* m, hipStream_t stream) {
   if (m->split_adopted && m->split_gemm && m->split_arena) return PMCE_OK;  // another handle's planes of the same weights
@@ -781,39 +830,11 @@ int build_split_weights(pmce_model* m, hipStream_t stream) {
     (void)hipDeviceSynchronize();  // forwards in flight (any stream, any lane) may still read the old planes; not capturable
     m->split_arena.reset();        // frees them unless another handle shares them
   }
-  for (auto& kind : m->sblk)
-    for (auto& b : kind) b = LifterBlockSplit{};
-  m->s_ie = m->s_wih0 = m->s_wih1 = m->s_whh0 = m->s_whh1 = m->s_ada = m->s_final = SplitW{};
-  for (auto& b : m->ffn_img) b[0] = b[1] = nullptr;
-  for (auto& q : m->qkv_img) q = nullptr;
-  m->tkv_img = nullptr;
+  m->sp = {};
   if (!m->split_gemm) return PMCE_OK;
-  const int C = m->C;
-  std::vector<SplitItem> items;
-  if (m->has_lifter) {
-    items.push_back({m->w.ie_w, C, F, &m->s_ie});
-    for (int kind = 0; kind < 2; ++kind)
-      for (int i = 0; i < m->depth; ++i) {
-        const LifterBlockW& bw = m->w.blk[kind][i];
-        LifterBlockSplit& sw = m->sblk[kind][i];
-        items.push_back({bw.qkv_w, 3 * C, C, &sw.qkv});
-        items.push_back({bw.proj_w, C, C, &sw.proj});
-        items.push_back({bw.fc1_w, 2 * C, C, &sw.fc1});
-        items.push_back({bw.fc2_w, C, 2 * C, &sw.fc2});
-      }
-  }
-  if (m->has_decoder) {
-    items.push_back({m->w.wih0, 6 * GH, F, &m->s_wih0});
-    items.push_back({m->w.wih1, 6 * GH, 2 * GH, &m->s_wih1});
-    items.push_back({m->w.whh0, 6 * GH, GH, &m->s_whh0});  // recurrent weights, both directions: gru_step's three-product form
-    items.push_back({m->w.whh1, 6 * GH, GH, &m->s_whh1});
-    items.push_back({m->w.ada_w, N_ADA * 128, 2 * GH, &m->s_ada});
-    items.push_back({m->w.final_w, NVF * 3, FINAL_K, &m->s_final});
-  }
+  const std::vector<SplitItem> items = split_items(m->w, m->sp, m->C, m->depth, m->has_lifter, m->has_decoder);
   if (items.empty()) return PMCE_OK;
-  size_t floats = 0;
-  for (auto& it : items) floats += split_item_floats(it.n, it.k);
-  if (m->has_decoder) floats += 6 * ffn_img_floats() + 3 * qkv_img_floats() + tkv_img_floats();
+  const size_t floats = split_floats(items);
   if (m->caller_arena) {  // the caller's memory (its allocator, its lifetime): pmce_model_set_split_arena
     if (m->caller_arena_bytes < floats * sizeof(float)) {
       pmce_set_error("model_finalize: the split arena holds %zu bytes, the planes need %zu (pmce_model_split_bytes)", m->caller_arena_bytes,
@@ -834,31 +855,8 @@ int build_split_weights(pmce_model* m, hipStream_t stream) {
   }
   float* p = m->split_arena.get();
   for (auto& it : items) {
-    float* wp = p;
-    float* sc = p + ((((size_t)it.n + 63) & ~(size_t)63) * it.k);
-    p = wp + split_item_floats(it.n, it.k);
-    // every weight in the blocked layout (what a tile - or a GRU step's workgroup - fetches per k-tile is contiguous)
-    PMCE_TRY(pmce_gemm_pack_split_f16_blk(it.w, it.n, it.k, it.k, wp, sc, stream));
-    it.dst->wp = wp;
-    it.dst->scale = sc;
-  }
-  if (m->has_decoder)  // the decoder FFNs' and qkv weights' LDS images (coevo.hip): every workgroup of their launches copies one (LDS-DMA) instead of converting
-    for (int k = 0; k < 3; ++k) {
-      const VertexBlockW& v = m->w.vb[k];
-      PMCE_TRY(pmce_ffn_pack_f16(v.vca_fc1_w, v.vca_fc2_w, p, stream));
-      m->ffn_img[k][0] = p;
-      p += ffn_img_floats();
-      PMCE_TRY(pmce_ffn_pack_f16(v.vsa_fc1_w, v.vsa_fc2_w, p, stream));
-      m->ffn_img[k][1] = p;
-      p += ffn_img_floats();
-      PMCE_TRY(pmce_qkv_pack_f16(v.vsa_qkv_w, p, stream));
-      m->qkv_img[k] = p;
-      p += qkv_img_floats();
-    }
-  if (m->has_decoder) {
-    PMCE_TRY(pmce_tkv_pack_f16(m->w.jb.v2j_w, m->w.jb.jca_wk_w, m->w.jb.jca_wv_w, p, stream));
-    m->tkv_img = p;
-    p += tkv_img_floats();
+    PMCE_TRY(it.pack(p, stream));
+    p += it.floats;
   }
   if (hipStreamSynchronize(stream) != hipSuccess) {
     pmce_set_error("model_finalize: packing the split weights failed");
@@ -955,7 +953,8 @@ size_t pmce_model_split_bytes(const pmce_model* m) {
   bool lifter = false, decoder = false;
   for (auto& s : m->names)
     if (m->ptr.count(s)) (s.rfind("lifter.", 0) == 0 ? lifter : decoder) = true;
-  return split_bytes_for(m->C, m->depth, lifter, decoder);
+  SplitPlanes unused;
+  return split_floats(split_items(m->w, unused, m->C, m->depth, lifter, decoder)) * sizeof(float);
 }
 int pmce_model_set_split_arena(pmce_model* m, void* arena, size_t bytes) {
   PMCE_REQUIRE(m, "model_set_split_arena: null model");
@@ -1018,12 +1017,7 @@ int pmce_model_share_split_weights(pmce_model* dst, const pmce_model* src) {
   }
   if (!src->split_arena) return PMCE_OK;  // fp32 mode: nothing to share
   dst->split_arena = src->split_arena;
-  for (int k = 0; k < 2; ++k)
-    for (int i = 0; i < 8; ++i) dst->sblk[k][i] = src->sblk[k][i];
-  dst->s_ie = src->s_ie; dst->s_wih0 = src->s_wih0; dst->s_wih1 = src->s_wih1; dst->s_whh0 = src->s_whh0; dst->s_whh1 = src->s_whh1;
-  dst->s_ada = src->s_ada; dst->s_final = src->s_final;
-  for (int k = 0; k < 3; ++k) dst->ffn_img[k][0] = src->ffn_img[k][0], dst->ffn_img[k][1] = src->ffn_img[k][1], dst->qkv_img[k] = src->qkv_img[k];
-  dst->tkv_img = src->tkv_img;
+  dst->sp = src->sp;
   dst->split_gemm = true;
   dst->split_adopted = true;
   dst->oflow = src->oflow;  // lanes of one model report to one word
@@ -1062,24 +1056,19 @@ int pmce_model_get_overflow_policy(const pmce_model* m) { return m ? (m->strict_
 
 size_t pmce_model_workspace_bytes(const pmce_model* m, int batch) {
   if (!m || batch <= 0) return 0;
-  Carver c(nullptr, ~(size_t)0);
-  LifterWs lw;
-  DecoderWs dw;
-  carve_lifter(c, m, batch, lw);
-  carve_decoder(c, m, batch, dw);
-  return c.off + 256;
+  return carve(m, batch, nullptr, ~(size_t)0).bytes + 256;
 }
 
 long long pmce_model_workspace_offset(const pmce_model* m, int batch, const char* name) {
   if (!m || batch <= 0 || !name) return -1;
-  Carver c(nullptr, ~(size_t)0);
-  LifterWs lw;
-  DecoderWs dw;
-  carve_lifter(c, m, batch, lw);
-  carve_decoder(c, m, batch, dw);
+  const Workspace w = carve(m, batch, nullptr, ~(size_t)0);
+  const LifterWs& lw = w.lw;
+  const DecoderWs& dw = w.dw;
   const std::string n(name);
   const float* p = nullptr;
-  if (n == "X") p = lw.X;                                                  // lifter tokens [B,16,J,C]
+  // lifter tokens [B,16,J,C] after the last TemporalBlock: BEFORE its post-norm norm_t where the head carries that norm (lifter_rest's
+  // head_pre: C = 512, or the fp32 pipe), after it where the product's epilogue does (C = 256 in split mode)
+  if (n == "X") p = lw.X;
   else if (n == "Y0") p = dw.Y0;                                           // GRU layer-0 output [16,B,2048]
   else if (n == "Y1") p = dw.Y1;                                           // GRU layer-1 output [16,B,2048] (pruned steps unset)
   else if (n == "g") p = dw.Y1 + (long long)8 * batch * 2 * GH;            // y[8] [B,2048]
@@ -1093,15 +1082,6 @@ long long pmce_model_workspace_offset(const pmce_model* m, int batch, const char
   else return -1;
   return (long long)reinterpret_cast<uintptr_t>(p);  // the carver ran on a null base: the pointer value IS the offset
 }
-
-namespace {
-struct SinkGuard {  // the launchers of this thread report to the model's flag (and clock probe) only while one of its entry points runs
-  ~SinkGuard() {
-    pmce_set_overflow_sink(nullptr);
-    pmce_set_clock_sink(nullptr);
-  }
-};
-}  // namespace
 
 static int check_ws(pmce_model* m, int batch, void* ws, size_t ws_bytes) {
   PMCE_REQUIRE(m && m->finalized, "model not finalized (call pmce_model_finalize after registering all tensors)");
@@ -1119,39 +1099,47 @@ static int check_ws(pmce_model* m, int batch, void* ws, size_t ws_bytes) {
     return PMCE_ERR_WORKSPACE;
   }
   m->split_now = m->split_gemm && batch >= m->split_min_batch;  // arithmetic (and with it the stream schedule) of this call
-  pmce_set_overflow_sink(m->oflow.get());  // (thread-local; the entry point clears it again through its SinkGuard)
+  pmce_set_overflow_sink(m->oflow.get());  // (thread-local; the entry point's Call clears it again)
   pmce_set_clock_sink(m->clk);
   return PMCE_OK;
 }
 
+namespace {
+// What every entry point starts with: check_ws, then the carved workspace.  The launchers of this thread report to the model's flag (and
+// clock probe) only while the entry point runs.
+struct Call : Workspace {
+  int begin(pmce_model* m, int batch, void* ws, size_t ws_bytes) {
+    PMCE_TRY(check_ws(m, batch, ws, ws_bytes));
+    Workspace::operator=(carve(m, batch, ws, ws_bytes));
+    return PMCE_OK;
+  }
+  ~Call() {
+    pmce_set_overflow_sink(nullptr);
+    pmce_set_clock_sink(nullptr);
+  }
+};
+}  // namespace
+
 int pmce_lifter_forward(pmce_model* m, const float* pose2d, const float* img_feat, float* pose3d, int batch, void* ws,
                         size_t ws_bytes, pmce_stream_t stream) {
-  PMCE_TRY(check_ws(m, batch, ws, ws_bytes));
-  SinkGuard sink_guard;
+  Call c;
+  PMCE_TRY(c.begin(m, batch, ws, ws_bytes));
   PMCE_REQUIRE(m->has_lifter, "lifter_forward: lifter tensors not registered");
   PMCE_REQUIRE(pose2d && img_feat && pose3d, "lifter_forward: null pointer");
-  Carver c(ws, ws_bytes);
-  LifterWs lw;
-  carve_lifter(c, m, batch, lw);
-  PMCE_TRY(prep_features(m, img_feat, batch * T, lw, stream));
-  return lifter_impl(m, pose2d, img_feat, pose3d, batch, lw, stream);
+  PMCE_TRY(prep_features(m, img_feat, batch * T, c.lw, stream));
+  return lifter_impl(m, pose2d, img_feat, pose3d, batch, c.lw, stream);
 }
 
 int pmce_decoder_forward(pmce_model* m, const float* joints, const float* img_feat, float* cam_pose, float* cam_mesh,
                          int batch, void* ws, size_t ws_bytes, pmce_stream_t stream) {
-  PMCE_TRY(check_ws(m, batch, ws, ws_bytes));
-  SinkGuard sink_guard;
+  Call c;
+  PMCE_TRY(c.begin(m, batch, ws, ws_bytes));
   PMCE_REQUIRE(m->has_decoder, "decoder_forward: decoder tensors not registered");
   PMCE_REQUIRE(joints && img_feat && cam_pose && cam_mesh, "decoder_forward: null pointer");
-  Carver c(ws, ws_bytes);
-  LifterWs lw;
-  DecoderWs dw;
-  carve_lifter(c, m, batch, lw);
-  carve_decoder(c, m, batch, dw);
-  PMCE_TRY(prep_features(m, img_feat, batch * T, lw, stream));
-  PMCE_TRY(gru_part(m, img_feat, lw, batch, dw, stream));
-  if (two_streams(m)) PMCE_TRY(ensure_side(m));
-  const int rc = coevo_part(m, joints, cam_pose, cam_mesh, batch, dw, stream, two_streams(m) ? m->side : nullptr);
+  PMCE_TRY(prep_features(m, img_feat, batch * T, c.lw, stream));
+  PMCE_TRY(gru_part(m, img_feat, c.lw, batch, c.dw, stream));
+  PMCE_TRY(ensure_side(m));
+  const int rc = coevo_part(m, joints, cam_pose, cam_mesh, batch, c.dw, stream, two_streams(m) ? m->side : nullptr);
   return rc == PMCE_OK ? rc : fail_after_fork(m, stream, rc);
 }
 
@@ -1160,21 +1148,32 @@ int pmce_decoder_forward(pmce_model* m, const float* joints, const float* img_fe
 // live at inference), joint_out[B,J,3].  Operator-level entry for parity tests against the reference module's own outputs.
 int pmce_coevo_block_forward(pmce_model* m, int k, const float* joints, const float* vt_in, const float* g, float* vt_out,
                              float* joint_out, int batch, void* ws, size_t ws_bytes, pmce_stream_t stream) {
-  PMCE_TRY(check_ws(m, batch, ws, ws_bytes));
-  SinkGuard sink_guard;
+  Call c;
+  PMCE_TRY(c.begin(m, batch, ws, ws_bytes));
   PMCE_REQUIRE(m->has_decoder, "coevo_block_forward: decoder tensors not registered");
   PMCE_REQUIRE(k >= 1 && k <= 3, "coevo_block_forward: k must be 1, 2 or 3");
   PMCE_REQUIRE(joints && vt_in && g && vt_out, "coevo_block_forward: null pointer");
   PMCE_REQUIRE(!joint_out || k == 3, "coevo_block_forward: the joint stream is live in block 3 only (CoevoDecoder.py:235-237)");
-  Carver c(ws, ws_bytes);
-  LifterWs lw;
-  DecoderWs dw;
-  carve_lifter(c, m, batch, lw);
-  carve_decoder(c, m, batch, dw);
-  RUN(P_GEMM_ADA, lgemm(m, g, m->w.ada_w, m->s_ada, m->w.ada_b, nullptr, dw.GB, batch, N_ADA * 128, 2 * GH, 2 * GH, N_ADA * 128, 0, stream));
-  PMCE_TRY(joint_prep(m, k, joints, batch, dw, stream));
-  if (joint_out) PMCE_TRY(joint_branch(m, joints, vt_in, joint_out, batch, dw, stream));
-  return vertex_block(m, k, vt_in, vt_out, batch, dw, stream);
+  RUN(P_GEMM_ADA, stream, lgemm(m, g, m->w.ada_w, m->sp.s_ada, m->w.ada_b, nullptr, c.dw.GB, batch, N_ADA * 128, 2 * GH, 2 * GH, N_ADA * 128, 0, stream));
+  PMCE_TRY(joint_prep(m, k, joints, batch, c.dw, stream));
+  if (joint_out) PMCE_TRY(joint_branch(m, joints, vt_in, joint_out, batch, c.dw, stream));
+  return vertex_block(m, k, vt_in, vt_out, batch, c.dw, stream);
+}
+
+// What pmce_forward and pmce_stream_forward share, for B clips (windows) whose tokens are in lw.X / lw.XN (lifter_rest) and whose GRU
+// branch has been enqueued - on m->side behind ev_join when the call forks (`what` names the caller in that join's error text).
+static int forward_tail(pmce_model* m, float* cam_mesh, float* cam_pose, float* pose3d, float* pred_pose, int B, LifterWs& lw,
+                        DecoderWs& dw, hipStream_t stream, const char* what) {
+  const bool single = !two_streams(m);
+  PMCE_TRY(lifter_rest(m, pose3d, B, lw, stream));
+  // pose3d.reshape(-1, J, 3) / 1000  (PMCE.py:17-18)
+  RUN(P_MISC, stream, pmce_div_scalar_f32(pose3d, dw.JM, (long long)B * m->J * 3, 1000.0f, stream));
+  PMCE_TRY(mark_lifter_done(m, stream));
+  if (!single) PMCE_TRY(ev_wait(stream, m->ev_join, what));
+  PMCE_TRY(coevo_part(m, dw.JM, cam_pose, cam_mesh, B, dw, stream, single ? nullptr : m->side));
+  if (pred_pose)
+    RUN(P_JREG, stream, pmce_j_regress_f32(cam_mesh, m->jr_indptr, m->jr_indices, m->jr_data, pred_pose, B, m->jr_rows, NVF, 1000.0f, stream));
+  return PMCE_OK;
 }
 
 static int forward_impl(pmce_model* m, const float* pose2d, const float* img_feat, float* cam_mesh, float* cam_pose,
@@ -1192,65 +1191,45 @@ static int forward_impl(pmce_model* m, const float* pose2d, const float* img_fea
   } else {
     PMCE_TRY(gru_part(m, img_feat, lw, batch, dw, stream));
   }
-  PMCE_TRY(lifter_impl(m, pose2d, img_feat, pose3d, batch, lw, stream));
-  // pose3d.reshape(-1, J, 3) / 1000  (PMCE.py:17-18)
-  RUN(P_MISC, pmce_div_scalar_f32(pose3d, dw.JM, (long long)batch * m->J * 3, 1000.0f, stream));
-  PMCE_TRY(mark_lifter_done(m, stream));
-  if (!single) PMCE_TRY(ev_wait(stream, m->ev_join, "forward join"));
-  PMCE_TRY(coevo_part(m, dw.JM, cam_pose, cam_mesh, batch, dw, stream, single ? nullptr : m->side));
-  if (pred_pose)
-    RUN(P_JREG, pmce_j_regress_f32(cam_mesh, m->jr_indptr, m->jr_indices, m->jr_data, pred_pose, batch, m->jr_rows, NVF,
-                                   1000.0f, stream));
-  return PMCE_OK;
+  PMCE_TRY(lifter_frames(m, pose2d, img_feat, batch * T, lw, stream));
+  PMCE_TRY(lifter_post_norm(m, 0, 0, (long long)batch * T * m->J, lw, stream));
+  return forward_tail(m, cam_mesh, cam_pose, pose3d, pred_pose, batch, lw, dw, stream, "forward join");
 }
 
 int pmce_forward(pmce_model* m, const float* pose2d, const float* img_feat, float* cam_mesh, float* cam_pose,
                  float* pose3d, float* pred_pose, int batch, void* ws, size_t ws_bytes, pmce_stream_t stream) {
-  PMCE_TRY(check_ws(m, batch, ws, ws_bytes));
-  SinkGuard sink_guard;
+  Call c;
+  PMCE_TRY(c.begin(m, batch, ws, ws_bytes));
   PMCE_REQUIRE(m->has_lifter && m->has_decoder, "forward: needs both lifter and decoder tensors");
   PMCE_REQUIRE(pose2d && img_feat && cam_mesh && cam_pose && pose3d, "forward: null pointer");
   PMCE_REQUIRE(!pred_pose || (m->jr_indptr && m->jr_indices && m->jr_data && m->jr_rows > 0),
                "forward: pred_pose requested but no J_regressor registered (jreg.indptr/indices/data + rows)");
-  Carver c(ws, ws_bytes);
-  LifterWs lw;
-  DecoderWs dw;
-  carve_lifter(c, m, batch, lw);
-  carve_decoder(c, m, batch, dw);
-  if (two_streams(m)) PMCE_TRY(ensure_side(m));
-  const int rc = forward_impl(m, pose2d, img_feat, cam_mesh, cam_pose, pose3d, pred_pose, batch, lw, dw, stream);
+  PMCE_TRY(ensure_side(m));
+  const int rc = forward_impl(m, pose2d, img_feat, cam_mesh, cam_pose, pose3d, pred_pose, batch, c.lw, c.dw, stream);
   return rc == PMCE_OK ? rc : fail_after_fork(m, stream, rc);
 }
 
 // ---- streaming (stride-1 windows over one long sequence) -------------------------------------------
-int pmce_window_tokens_f32(const float* x0, const int* win, const float* tpos, const float* w2, const float* b2, float eps2,
-                           float* X, float* XN, int W, int L, int T, int J, int C, hipStream_t stream);
-int pmce_window_rows_f32(const float* src, const int* win, float* dst, int W, int L, int T, int ncols, hipStream_t stream);
-int pmce_window_mid_tokens_f32(const float* x0_mid, const int* win, const float* tpos, const float* w2, const float* b2, float eps2,
-                               float* X, float* XN, int W, int L, int T, int J, int C, int t_mid, int xn_split, hipStream_t stream);
-
 int pmce_stream_precompute(pmce_model* m, const float* pose2d_frames, const float* feat_frames, int L, float* x0, float* gi0,
                            void* ws, size_t ws_bytes, pmce_stream_t stream) {
   PMCE_REQUIRE(L > 0, "stream_precompute: L must be positive");
   const int bf = (L + T - 1) / T;  // the per-frame pass needs the workspace of ceil(L/16) clips
-  PMCE_TRY(check_ws(m, bf, ws, ws_bytes));
-  SinkGuard sink_guard;
+  Call c;
+  PMCE_TRY(c.begin(m, bf, ws, ws_bytes));
+  LifterWs& lw = c.lw;
   PMCE_REQUIRE(m->has_lifter && m->has_decoder, "stream_precompute: needs both lifter and decoder tensors");
   PMCE_REQUIRE(pose2d_frames && feat_frames && x0 && gi0, "stream_precompute: null pointer");
-  Carver c(ws, ws_bytes);
-  LifterWs lw;
-  carve_lifter(c, m, bf, lw);
   // window-independent lifter work: embedding + SpatialBlocks[0] + norm_s, once per frame (PoseEstimation.py:78-85)
   PMCE_TRY(prep_features(m, feat_frames, L, lw, stream));
   PMCE_TRY(lifter_frames(m, pose2d_frames, feat_frames, L, lw, stream));
-  RUN(P_LN, pmce_ln_chain_f32(lw.X, (long long)L * m->J, m->C, m->w.ns_w, m->w.ns_b, 1e-6f,
-                              nullptr, 1, 1, x0, nullptr, nullptr, 0.f, nullptr, stream));
+  RUN(P_LN, stream, pmce_ln_chain_f32(lw.X, (long long)L * m->J, m->C, m->w.ns_w, m->w.ns_b, 1e-6f,
+                                      nullptr, 1, 1, x0, nullptr, nullptr, 0.f, nullptr, 0, stream));
   // window-independent GRU work: layer-0 input projections of both directions, once per frame (CoevoDecoder.py:216-221)
-  if (m->split_now && m->s_wih0.wp)
-    RUN(P_GEMM_GRU_IN, rs_gemm(m, lw.FS, lw.FR, m->s_wih0, m->w.bih0, gi0, L, 6 * GH, 6 * GH, 0, 0, 0, stream));
+  if (m->split_now && m->sp.s_wih0.wp)
+    RUN(P_GEMM_GRU_IN, stream, rs_gemm(m, lw.FS, lw.FR, m->sp.s_wih0, m->w.bih0, gi0, L, 6 * GH, 6 * GH, 0, 0, 0, stream));
   else
-    RUN(P_GEMM_GRU_IN, lgemm(m, feat_frames, m->w.wih0, m->s_wih0, m->w.bih0, nullptr, gi0, L, 6 * GH, F, F, 6 * GH,
-                             0, stream));
+    RUN(P_GEMM_GRU_IN, stream, lgemm(m, feat_frames, m->w.wih0, m->sp.s_wih0, m->w.bih0, nullptr, gi0, L, 6 * GH, F, F, 6 * GH,
+                                     0, stream));
   return PMCE_OK;
 }
 
@@ -1264,46 +1243,28 @@ static int stream_forward_impl(pmce_model* m, const float* x0, const float* x0_m
     PMCE_TRY(ev_record(m->ev_fork, stream, "stream_forward fork"));
     PMCE_TRY(ev_wait(m->side, m->ev_fork, "stream_forward fork"));
   }
-  {
-    hipStream_t stream_save = stream;
-    stream = gs;  // RUN() launches on `stream`
-    RUN(P_MISC, pmce_window_rows_f32(gi0, win, dw.GI0, W, L, T, 6 * GH, stream));
-    stream = stream_save;
-  }
+  RUN(P_MISC, gs, pmce_window_rows_f32(gi0, win, dw.GI0, W, L, T, 6 * GH, gs));
   PMCE_TRY(gru_rest(m, W, dw, gs));
   if (!single) PMCE_TRY(ev_record(m->ev_join, m->side, "stream_forward join"));
-  RUN(P_LN, pmce_window_tokens_ex_f32(x0, win, m->w.tpos, m->w.blk[1][0].norm1_w, m->w.blk[1][0].norm1_b, 1e-6f, lw.X, lw.XN, W, L,
-                                   T, m->J, m->C, pk(m), stream));
+  RUN(P_LN, stream, pmce_window_tokens_f32(x0, win, m->w.tpos, m->w.blk[1][0].norm1_w, m->w.blk[1][0].norm1_b, 1e-6f, lw.X, lw.XN, W, L,
+                                           T, m->J, m->C, pk(m), stream));
   if (x0_mid)
-    RUN(P_LN, pmce_window_mid_tokens_f32(x0_mid, win, m->w.tpos, m->w.blk[1][0].norm1_w, m->w.blk[1][0].norm1_b, 1e-6f, lw.X, lw.XN, W,
-                                         L, T, m->J, m->C, T / 2, pk(m), stream));
-  PMCE_TRY(lifter_rest(m, pose3d, W, lw, stream));
-  RUN(P_MISC, pmce_div_scalar_f32(pose3d, dw.JM, (long long)W * m->J * 3, 1000.0f, stream));
-  PMCE_TRY(mark_lifter_done(m, stream));
-  if (!single) PMCE_TRY(ev_wait(stream, m->ev_join, "stream_forward join"));
-  PMCE_TRY(coevo_part(m, dw.JM, cam_pose, cam_mesh, W, dw, stream, single ? nullptr : m->side));
-  if (pred_pose)
-    RUN(P_JREG, pmce_j_regress_f32(cam_mesh, m->jr_indptr, m->jr_indices, m->jr_data, pred_pose, W, m->jr_rows, NVF, 1000.0f,
-                                   stream));
-  return PMCE_OK;
+    RUN(P_LN, stream, pmce_window_mid_tokens_f32(x0_mid, win, m->w.tpos, m->w.blk[1][0].norm1_w, m->w.blk[1][0].norm1_b, 1e-6f, lw.X, lw.XN, W,
+                                                 L, T, m->J, m->C, T / 2, pk(m), stream));
+  return forward_tail(m, cam_mesh, cam_pose, pose3d, pred_pose, W, lw, dw, stream, "stream_forward join");
 }
 
 static int stream_forward_entry(pmce_model* m, const float* x0, const float* x0_mid, const float* gi0, const int* win, int W, int L,
                                 float* cam_mesh, float* cam_pose, float* pose3d, float* pred_pose, void* ws, size_t ws_bytes,
                                 pmce_stream_t stream) {
-  PMCE_TRY(check_ws(m, W, ws, ws_bytes));
-  SinkGuard sink_guard;
+  Call c;
+  PMCE_TRY(c.begin(m, W, ws, ws_bytes));
   PMCE_REQUIRE(m->has_lifter && m->has_decoder, "stream_forward: needs both lifter and decoder tensors");
   PMCE_REQUIRE(x0 && gi0 && win && cam_mesh && cam_pose && pose3d && L > 0, "stream_forward: null pointer");
   PMCE_REQUIRE(!pred_pose || (m->jr_indptr && m->jr_indices && m->jr_data && m->jr_rows > 0),
                "stream_forward: no J_regressor registered");
-  Carver c(ws, ws_bytes);
-  LifterWs lw;
-  DecoderWs dw;
-  carve_lifter(c, m, W, lw);
-  carve_decoder(c, m, W, dw);
-  if (two_streams(m)) PMCE_TRY(ensure_side(m));
-  const int rc = stream_forward_impl(m, x0, x0_mid, gi0, win, W, L, cam_mesh, cam_pose, pose3d, pred_pose, lw, dw, stream);
+  PMCE_TRY(ensure_side(m));
+  const int rc = stream_forward_impl(m, x0, x0_mid, gi0, win, W, L, cam_mesh, cam_pose, pose3d, pred_pose, c.lw, c.dw, stream);
   return rc == PMCE_OK ? rc : fail_after_fork(m, stream, rc);
 }
 

@@ -42,7 +42,7 @@ def pack_split_f16(W):
     N, K = W.shape
     Wp = torch.empty(N, K, device=W.device, dtype=torch.float32)
     wscale = torch.empty(N, device=W.device, dtype=torch.float32)
-    _lib.check(lib.pmce_gemm_pack_split_f16(P(W), N, K, K, P(Wp), P(wscale), _st()), "gemm_pack_split_f16")
+    _lib.check(lib.pmce_gemm_pack_split_f16(P(W), N, K, K, P(Wp), P(wscale), 0, _st()), "gemm_pack_split_f16")
     return Wp, wscale
 
 
@@ -54,20 +54,25 @@ def pack_split_f16_blk(W):
     Np = (N + 63) // 64 * 64
     Wp = torch.zeros(Np, K, device=W.device, dtype=torch.float32)
     ws = torch.empty(N, device=W.device, dtype=torch.float32)
-    _lib.check(lib.pmce_gemm_pack_split_f16_blk(P(W), N, K, K, P(Wp), P(ws), _st()), "gemm_pack_split_f16_blk")
+    _lib.check(lib.pmce_gemm_pack_split_f16(P(W), N, K, K, P(Wp), P(ws), 1, _st()), "gemm_pack_split_f16")
     return Wp, ws, N
 
 
-def gemm_nt_split_blk(A, Wblk, wscale, N, bias=None, residual=None, act=0, a_packed=False, c_packed=False, rscale=None, rowmap=None, out=None):
-    """Every form of the three-product GEMM on a blocked weight (pmce_gemm_nt_split_f16_blk)."""
+def _gemm_nt_split(A, Wp, blocked, wscale, N, bias=None, residual=None, act=0, a_packed=False, c_packed=False, rscale=None, rowmap=None, out=None):
+    """pmce_gemm_nt_split_f16: every form of the three-product GEMM, on a row-major or a blocked weight."""
     lib = _lib.load()
     M, K = A.shape
     if out is None:
         out = torch.empty(M, N, device=A.device, dtype=torch.float32)
     cd, lo, hi = rowmap if rowmap else (0, 0, 0)
-    _lib.check(lib.pmce_gemm_nt_split_f16_blk(P(A), P(rscale), P(Wblk), P(wscale), P(bias), P(residual), P(out), M, N, K, K, N, act,
-                                              1 if a_packed else 0, 1 if c_packed else 0, cd, lo, hi, _st()), "gemm_nt_split_blk")
+    _lib.check(lib.pmce_gemm_nt_split_f16(P(A), P(rscale), P(Wp), 1 if blocked else 0, P(wscale), P(bias), P(residual), P(out), M, N, K, K, N, act,
+                                          1 if a_packed else 0, 1 if c_packed else 0, cd, lo, hi, _st()), "gemm_nt_split")
     return out
+
+
+def gemm_nt_split_blk(A, Wblk, wscale, N, bias=None, residual=None, act=0, a_packed=False, c_packed=False, rscale=None, rowmap=None, out=None):
+    """Every form of the three-product GEMM on a blocked weight."""
+    return _gemm_nt_split(A, Wblk, True, wscale, N, bias, residual, act, a_packed, c_packed, rscale, rowmap, out)
 
 
 def gemm_nt_split_ln(Ap, Wp, wscale, bias, residual, ln1=None, ln2=None, blocked=True, want_out1=True):
@@ -95,16 +100,8 @@ def split_rows_f16(A):
 
 
 def gemm_nt_split(A, Wp, wscale, bias=None, residual=None, act=0, out=None, a_packed=False, c_packed=False):
-    """gemm_nt on the f16 matrix pipe (three-product split, fp32 accumulate): fp32 in, fp32 out, fp32 accuracy."""
-    lib = _lib.load()
-    A = _c(A)
-    M, K = A.shape
-    N = Wp.shape[0]
-    if out is None:
-        out = torch.empty(M, N, device=A.device, dtype=torch.float32)
-    _lib.check(lib.pmce_gemm_nt_split_f16_ex(P(A), P(Wp), P(wscale), P(bias), P(residual), P(out), M, N, K, K, N, act,
-                                             1 if a_packed else 0, 1 if c_packed else 0, _st()), "gemm_nt_split")
-    return out
+    """gemm_nt on the f16 matrix pipe (three-product split, fp32 accumulate): fp32 in, fp32 out, fp32 accuracy.  Row-major weight."""
+    return _gemm_nt_split(_c(A), Wp, False, wscale, Wp.shape[0], bias, residual, act, a_packed, c_packed, out=out)
 
 
 def split_rows_scaled_f16(A):
@@ -119,17 +116,9 @@ def split_rows_scaled_f16(A):
 
 
 def gemm_nt_split_rs(Ap, rscale, Wp, wscale, bias=None, out=None, rowmap=None):
-    """The three-product f16 GEMM on a row-scaled packed A (raw inputs: img_feat).  rowmap = (c_div, c_lo, c_hi) maps output rows.
-    K >= 128 (include/pmce_hip.h at pmce_gemm_nt_split_f16_rs)."""
-    lib = _lib.load()
-    M, K = Ap.shape
-    N = Wp.shape[0]
-    if out is None:
-        out = torch.empty(M, N, device=Ap.device, dtype=torch.float32)
-    cd, lo, hi = rowmap if rowmap else (0, 0, 0)
-    _lib.check(lib.pmce_gemm_nt_split_f16_rs(P(Ap), P(rscale), P(Wp), P(wscale), P(bias), P(out), M, N, K, N, cd, lo, hi, _st()),
-               "gemm_nt_split_rs")
-    return out
+    """The three-product f16 GEMM on a row-scaled packed A (raw inputs: img_feat) and a row-major weight.  rowmap = (c_div, c_lo, c_hi) maps
+    output rows.  K >= 128 (include/pmce_hip.h at pmce_gemm_nt_split_f16)."""
+    return _gemm_nt_split(Ap, Wp, False, wscale, Wp.shape[0], bias, a_packed=True, rscale=rscale, rowmap=rowmap, out=out)
 
 
 def gru_step_split(gi, whh, bhh, h_prev, blocked=True):
@@ -145,8 +134,8 @@ def gru_step_split(gi, whh, bhh, h_prev, blocked=True):
         Wp, wscale = pack_split_f16(whh)
     hp = None if h_prev is None else _c(h_prev)
     out = torch.empty(B, H, device=gi.device, dtype=torch.float32)
-    _lib.check((lib.pmce_gru_step_split_blk_f32 if blocked else lib.pmce_gru_step_split_f32)(P(gi), None, P(Wp), None, P(wscale), P(bhh), None, P(hp), None, P(out), None, 3 * H, H, B, H, 1,
-                                           _st()), "gru_step_split")
+    _lib.check(lib.pmce_gru_step_split_f32(P(gi), None, P(Wp), None, P(wscale), P(bhh), None, P(hp), None, P(out), None, 3 * H, H, B, H, 1,
+                                           1 if blocked else 0, _st()), "gru_step_split")
     return out
 
 
@@ -157,8 +146,8 @@ def ln_chain(x, w1=None, b1=None, eps1=1e-6, add=None, add_div=1, add_mod=1, wan
     rows, Cc = x.shape
     out1 = torch.empty_like(x) if want_out1 else None
     out2 = torch.empty_like(x) if w2 is not None else None
-    _lib.check(lib.pmce_ln_chain_ex_f32(P(x), rows, Cc, P(w1), P(b1), eps1, P(add), add_div, add_mod, P(out1), P(w2), P(b2), eps2,
-                                        P(out2), 1 if out2_split else 0, _st()), "ln_chain")
+    _lib.check(lib.pmce_ln_chain_f32(P(x), rows, Cc, P(w1), P(b1), eps1, P(add), add_div, add_mod, P(out1), P(w2), P(b2), eps2,
+                                     P(out2), 1 if out2_split else 0, _st()), "ln_chain")
     return out1, out2
 
 
@@ -191,8 +180,8 @@ def lifter_head(x, lnw, lnb, Wr, br, wf, bf, B, T, J, pre=None):
     Cc = x.shape[1]
     out = torch.empty(B, J, 3, device=x.device, dtype=torch.float32)
     pw, pb, pe = (_c(pre[0]), _c(pre[1]), float(pre[2])) if pre is not None else (None, None, 0.0)
-    _lib.check(lib.pmce_lifter_head_ex_f32(P(_c(x)), P(pw), P(pb), pe, P(_c(lnw)), P(_c(lnb)), P(_c(Wr)), P(_c(br)), P(_c(wf)), P(_c(bf)), P(out),
-                                           B, T, J, Cc, _st()), "lifter_head")
+    _lib.check(lib.pmce_lifter_head_f32(P(_c(x)), P(pw), P(pb), pe, P(_c(lnw)), P(_c(lnb)), P(_c(Wr)), P(_c(br)), P(_c(wf)), P(_c(bf)), P(out),
+                                        B, T, J, Cc, _st()), "lifter_head")
     return out
 
 
@@ -200,8 +189,8 @@ def seq_attention(qkv, nseq, N, Cc, seq_div, seq_lo, seq_hi, tok_stride, out_spl
     lib = _lib.load()
     qkv = _c(qkv)
     out = torch.empty(qkv.shape[0], Cc, device=qkv.device, dtype=torch.float32)
-    _lib.check(lib.pmce_seq_attention_ex_f32(P(qkv), P(out), nseq, N, Cc, seq_div, seq_lo, seq_hi, tok_stride,
-                                             1 if out_split else 0, _st()), "seq_attention")
+    _lib.check(lib.pmce_seq_attention_f32(P(qkv), P(out), nseq, N, Cc, seq_div, seq_lo, seq_hi, tok_stride,
+                                          1 if out_split else 0, _st()), "seq_attention")
     return out
 
 
@@ -256,7 +245,7 @@ def cross_attn_vertex(xq, xk, xv, g, sd, p):
                                               "proj.weight", "proj.bias")}
     _lib.check(lib.pmce_ca_fold_f32(P(xk), P(xv), P(GB), GB.shape[1], 0, 1, 2, P(w["wq.weight"]), P(w["wq.bias"]),
                                     P(w["wk.weight"]), P(w["wk.bias"]), P(w["wv.weight"]), P(w["wv.bias"]),
-                                    P(w["proj.weight"]), P(Kf), P(s0), P(Vf), B, J, _st()), "ca_fold")
+                                    P(w["proj.weight"]), P(Kf), P(s0), P(Vf), None, B, J, _st()), "ca_fold")
     out = torch.empty_like(xq)
     _lib.check(lib.pmce_vertex_ca_f32(P(xq), None, None, None, P(Kf), P(s0), P(Vf), P(w["proj.bias"]), P(out), B, J, _st()),
                "vertex_ca")
@@ -292,16 +281,16 @@ def cross_attn_block_vertex(xq, xk, xv, g, sd, p, split_f16=False, packed=False)
     img = torch.empty(B, lib.pmce_ca_image_floats(), device=dev) if (split_f16 and J <= 23) else None
     w = {k: _c(sd[f"{p}.attn.{k}"]) for k in ("wq.weight", "wq.bias", "wk.weight", "wk.bias", "wv.weight", "wv.bias",
                                               "proj.weight", "proj.bias")}
-    _lib.check(lib.pmce_ca_fold_img_f32(P(xk), P(xv), P(GB), GB.shape[1], 0, 1, 2, P(w["wq.weight"]), P(w["wq.bias"]),
-                                        P(w["wk.weight"]), P(w["wk.bias"]), P(w["wv.weight"]), P(w["wv.bias"]),
-                                        P(w["proj.weight"]), P(Kf), P(s0), P(Vf), P(img), B, J, _st()), "ca_fold")
+    _lib.check(lib.pmce_ca_fold_f32(P(xk), P(xv), P(GB), GB.shape[1], 0, 1, 2, P(w["wq.weight"]), P(w["wq.bias"]),
+                                    P(w["wk.weight"]), P(w["wk.bias"]), P(w["wv.weight"]), P(w["wv.bias"]),
+                                    P(w["proj.weight"]), P(Kf), P(s0), P(Vf), P(img), B, J, _st()), "ca_fold")
     m = [_c(sd[p + k]) for k in (".mlp.fc1.weight", ".mlp.fc1.bias", ".mlp.fc2.weight", ".mlp.fc2.bias")]
     out = torch.empty_like(xq)
     scratch = torch.empty_like(xq) if J > 23 else None
     fimg = ffn_image(m[0], m[2]) if packed else None
-    _lib.check(lib.pmce_vertex_ca_mlp_pk_f32(P(xq), None, None, None, P(Kf), P(s0), P(Vf), P(w["proj.bias"]), P(GB), GB.shape[1],
-                                             3, P(m[0]), P(m[1]), P(m[2]), P(m[3]), P(out), P(scratch), B, J,
-                                             1 if split_f16 else 0, P(fimg), P(img), _st()), "vertex_ca_mlp")
+    _lib.check(lib.pmce_vertex_ca_mlp_f32(P(xq), None, None, None, P(Kf), P(s0), P(Vf), P(w["proj.bias"]), P(GB), GB.shape[1],
+                                          3, P(m[0]), P(m[1]), P(m[2]), P(m[3]), P(out), P(scratch), B, J,
+                                          1 if split_f16 else 0, P(fimg), P(img), _st()), "vertex_ca_mlp")
     return out
 
 
@@ -320,8 +309,8 @@ def adaln_mlp(x, g, sd, p_norm, p_mlp, coor=None, vt_in=None, want_features=True
         vt_in = _c(vt_in)
         vt_out = torch.empty_like(vt_in)
     img = ffn_image(w[0], w[2]) if packed else None
-    _lib.check(lib.pmce_adaln_mlp_pk_f32(P(x), P(GB), GB.shape[1], 0, P(w[0]), P(w[1]), P(w[2]), P(w[3]), P(y), P(Wc), P(bc),
-                                         P(vt_in), P(vt_out), B, 1 if split_f16 else 0, P(img), _st()), "adaln_mlp")
+    _lib.check(lib.pmce_adaln_mlp_f32(P(x), P(GB), GB.shape[1], 0, P(w[0]), P(w[1]), P(w[2]), P(w[3]), P(y), P(Wc), P(bc),
+                                      P(vt_in), P(vt_out), B, 1 if split_f16 else 0, P(img), _st()), "adaln_mlp")
     return y, vt_out
 
 
@@ -366,9 +355,9 @@ def joint_stream(xq, xk, xv, g, sd, blk, stage, jt=None, split_f16=False):
     if split_f16:   # (the generic form does not use proj_v2j_dim: any 64 x 64 weight fills the image's first slot)
         img = torch.empty(lib.pmce_tkv_image_floats(), device=xq.device)
         _lib.check(lib.pmce_tkv_pack_f16(P(Wk), P(Wk), P(Wv), P(img), _st()), "tkv_pack_f16")
-    _lib.check(lib.pmce_tokens_kv_pk_f32(P(xk), P(xv), None, None, None, None, None, P(GB), GB.shape[1], 1, 2,
-                                         P(Wk), P(_c(sd[ca + ".attn.wk.bias"])), P(Wv), P(_c(sd[ca + ".attn.wv.bias"])), P(kv), B,
-                                         P(img), _st()), "tokens_kv")
+    _lib.check(lib.pmce_tokens_kv_f32(P(xk), P(xv), None, None, None, None, None, P(GB), GB.shape[1], 1, 2,
+                                      P(Wk), P(_c(sd[ca + ".attn.wk.bias"])), P(Wv), P(_c(sd[ca + ".attn.wv.bias"])), P(kv), B,
+                                      P(img), _st()), "tokens_kv")
     names = [ca + ".attn.wq.weight", ca + ".attn.wq.bias", ca + ".attn.proj.weight", ca + ".attn.proj.bias",
              ca + ".mlp.fc1.weight", ca + ".mlp.fc1.bias", ca + ".mlp.fc2.weight", ca + ".mlp.fc2.bias",
              sa + ".attn.qkv.weight", sa + ".attn.qkv.bias", sa + ".attn.proj.weight", sa + ".attn.proj.bias",
@@ -430,7 +419,7 @@ def final_product(model, vt, g):
     B = vt.shape[0]
     KP = eng.packed["dec.final.weight"].shape[1]
     A = torch.empty(B, KP, device=vt.device, dtype=torch.float32)
-    _lib.check(lib.pmce_build_final_operand_f32(P(g), P(vt), P(A), B, KP, _st()), "build_final_operand")
+    _lib.check(lib.pmce_build_final_operand_f32(P(g), P(vt), P(A), B, KP, 0, _st()), "build_final_operand")
     return gemm_nt(A, eng.packed["dec.final.weight"], eng.packed["dec.final.bias"]).reshape(B, 6890, 3)
 
 

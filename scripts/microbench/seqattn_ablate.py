@@ -26,7 +26,7 @@ for v in "ABCDE":
     assert r.returncode == 0, r.stderr[-2000:]
     lib = C.CDLL(f"{d}/lib.so")
     vp, i, l = C.c_void_p, C.c_int, C.c_longlong
-    lib.pmce_seq_attention_f32.argtypes = [vp, vp, i, i, i, i, l, l, l, vp]
+    lib.pmce_seq_attention_f32.argtypes = [vp, vp, i, i, i, i, l, l, l, i, vp]
     libs[v] = lib
 dev = torch.device("cuda:0")
 desc = {"A": "full", "B": "no key loop", "C": "one key", "D": "no K/V staging", "E": "no store"}
@@ -37,7 +37,7 @@ for name, args in (("spatial", (B * T, J, Cc, 0, J, 0, 1)), ("temporal", (B * J,
     best = {v: 1e9 for v in libs}
     for rnd in range(3):
         for v, lib in libs.items():
-            call = lambda i: lib.pmce_seq_attention_f32(qkvs[i % 3].data_ptr(), outs[i % 3].data_ptr(), *args, st)
+            call = lambda i: lib.pmce_seq_attention_f32(qkvs[i % 3].data_ptr(), outs[i % 3].data_ptr(), *args, 0, st)
             assert call(0) == 0; torch.cuda.synchronize()
             e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
             e0.record()

@@ -23,8 +23,8 @@ A = torch.randn(M, K, device=dev); W = torch.randn(N, K, device=dev) * K ** -0.5
 Wp, ws = ops.pack_split_f16(W)
 outg = torch.empty(M, N, device=dev)
 def gemm_split(m=M):
-    _lib.check(lib.pmce_gemm_nt_split_f16(_lib.ptr(A), _lib.ptr(Wp), _lib.ptr(ws), _lib.ptr(b), None, _lib.ptr(outg), m, N, K, K, N, 0, 0,
-                                          C.c_void_p(s2.cuda_stream)))
+    _lib.check(lib.pmce_gemm_nt_split_f16(_lib.ptr(A), None, _lib.ptr(Wp), 0, _lib.ptr(ws), _lib.ptr(b), None, _lib.ptr(outg), m, N, K, K, N,
+                                          0, 0, 0, 0, 0, 0, C.c_void_p(s2.cuda_stream)))
 def gemm_f32(m=M):
     _lib.check(lib.pmce_gemm_nt_f32(_lib.ptr(A), _lib.ptr(W), _lib.ptr(b), None, _lib.ptr(outg), m, N, K, K, K, N, 0, 0, 0, 0, 0, 0, 0, 1,
                                     0, 0, 0, 0, C.c_void_p(s2.cuda_stream)))
@@ -50,8 +50,8 @@ lnw = torch.randn(Cc, device=dev); lnb = torch.randn(Cc, device=dev)
 Wr = torch.randn(3, Cc, device=dev); br = torch.randn(3, device=dev); wf = torch.randn(T, device=dev); bf = torch.randn(1, device=dev)
 def head():
     out = torch.empty(B, J, 3, device=dev)
-    _lib.check(lib.pmce_lifter_head_f32(_lib.ptr(X), _lib.ptr(lnw), _lib.ptr(lnb), _lib.ptr(Wr), _lib.ptr(br), _lib.ptr(wf), _lib.ptr(bf),
-                                        _lib.ptr(out), B, T, J, Cc, C.c_void_p(s1.cuda_stream)))
+    _lib.check(lib.pmce_lifter_head_f32(_lib.ptr(X), None, None, 0.0, _lib.ptr(lnw), _lib.ptr(lnb), _lib.ptr(Wr), _lib.ptr(br), _lib.ptr(wf),
+                                        _lib.ptr(bf), _lib.ptr(out), B, T, J, Cc, C.c_void_p(s1.cuda_stream)))
     return out
 ref = head(); torch.cuda.synchronize()
 for label, aggr in (("nothing", lambda: None), ("fp32 GEMM 64x3072x2048", lambda: gemm_f32(64)), ("split-f16 GEMM 64x3072x2048", lambda: gemm_split(64))):

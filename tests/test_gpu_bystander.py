@@ -37,7 +37,7 @@ def test_bystander_interference_report():
 
     def gemm_split():
         for _ in range(3):
-            _lib.check(lib.pmce_gemm_nt_split_f16(_lib.ptr(A), _lib.ptr(Wp), _lib.ptr(ws), _lib.ptr(b), None, _lib.ptr(outg), M, N, K, K, N, 0, 0, mx))
+            _lib.check(lib.pmce_gemm_nt_split_f16(_lib.ptr(A), None, _lib.ptr(Wp), 0, _lib.ptr(ws), _lib.ptr(b), None, _lib.ptr(outg), M, N, K, K, N, 0, 0, 0, 0, 0, 0, mx))
 
     def gemm_f32():
         for _ in range(3):

@@ -216,8 +216,8 @@ def test_gemm_split_row_map():
     b = rnd("gemm.rm.b", (N,)).to(dev())
     Wp, ws = ops.pack_split_f16(W)
     out = torch.zeros(Tn * B, N, device=dev())
-    _lib.check(lib.pmce_gemm_nt_split_f16_rowmap(_lib.ptr(A), _lib.ptr(Wp), _lib.ptr(ws), _lib.ptr(b), _lib.ptr(out), B * Tn, N, K, K,
-                                                 Tn, B * N, N, _lib.current_stream()))
+    _lib.check(lib.pmce_gemm_nt_split_f16(_lib.ptr(A), None, _lib.ptr(Wp), 0, _lib.ptr(ws), _lib.ptr(b), None, _lib.ptr(out), B * Tn, N, K, K, N,
+                                          0, 0, 0, Tn, B * N, N, _lib.current_stream()))
     ref = (A.double() @ W.double().t() + b.double()).reshape(B, Tn, N).permute(1, 0, 2).reshape(Tn * B, N)
     assert maxabs(out, ref) < 1e-5
 
@@ -664,8 +664,8 @@ def test_final_operand_pre_split_is_the_same_split():
     g = rnd("fin.g", (B, 2048)).to(dev())
     vt = rnd("fin.vt", (B, 431, 3)).to(dev())
     A = torch.empty(B, KP, device=dev()); Ap = torch.empty(B, KP, device=dev())
-    _lib.check(lib.pmce_build_final_operand_pk_f32(_lib.ptr(g), _lib.ptr(vt), _lib.ptr(A), B, KP, 0, _lib.current_stream()), "build_final_operand")
-    _lib.check(lib.pmce_build_final_operand_pk_f32(_lib.ptr(g), _lib.ptr(vt), _lib.ptr(Ap), B, KP, 1, _lib.current_stream()), "build_final_operand")
+    _lib.check(lib.pmce_build_final_operand_f32(_lib.ptr(g), _lib.ptr(vt), _lib.ptr(A), B, KP, 0, _lib.current_stream()), "build_final_operand")
+    _lib.check(lib.pmce_build_final_operand_f32(_lib.ptr(g), _lib.ptr(vt), _lib.ptr(Ap), B, KP, 1, _lib.current_stream()), "build_final_operand")
     assert torch.equal(ops.split_rows_f16(A).view(torch.int32), Ap.view(torch.int32))
     assert torch.equal(A[:, :2048], torch.relu(g)) and torch.equal(A[:, 2048:2048 + 1293], vt.reshape(B, -1)) and not A[:, 3341:].any()
 
@@ -800,7 +800,7 @@ def test_gemm_split_out_of_range_is_never_silently_finite():
 
 
 def test_gemm_split_row_scaled_inputs_of_any_magnitude():
-    """pmce_split_rows_scaled_f16 + pmce_gemm_nt_split_f16_rs (the raw-input products: imgfeat_embed, PoseEstimation.py:80; the GRU
+    """pmce_split_rows_scaled_f16 + pmce_gemm_nt_split_f16 with rscale (the raw-input products: imgfeat_embed, PoseEstimation.py:80; the GRU
     layer-0 input projection, CoevoDecoder.py:228 - the reference's Linear takes any fp32 value): rows of magnitude 1e-30 ... 1e30,
     rows mixing 1e5 with 1e-7, a zero row; every element against an fp64 product, next to the fp32 pipe's error on the same
     operands; with and without the output row map; inf / nan rows stay in their own rows."""
@@ -970,7 +970,7 @@ def test_gemm_split_layernorm_epilogue(M, K, case):
 @pytest.mark.parametrize("J,C,BT", [(17, 512, 37), (19, 256, 37), (17, 512, 1700), (17, 256, 5000), (19, 512, 9000)])
 def test_embed_ln_equals_embed_then_ln_chain(J, C, BT):
     """Round 6: the token embedding and SpatialBlocks[0].norm1 in ONE launch (pmce_embed_ln_f32: the tokens do not travel to HBM and back) against
-    pmce_embed_tokens_f32 followed by pmce_ln_chain_ex_f32 - tokens and LayerNorm bit for bit, fp32 and pre-split output - and against fp64.
+    pmce_embed_tokens_f32 followed by pmce_ln_chain_f32 - tokens and LayerNorm bit for bit, fp32 and pre-split output - and against fp64.
     The frame counts cover every way the kernel shares a frame's tokens among wavefronts: one token per wavefront (37 frames), 5, 2 and 1
     wavefronts per frame (1,700 / 5,000 / 9,000 frames; B = 256 clips are 4,096 frames: 2)."""
     from pmce_amd import ops
@@ -997,7 +997,7 @@ def test_embed_ln_equals_embed_then_ln_chain(J, C, BT):
 
 @pytest.mark.parametrize("J,C,T", [(17, 512, 16), (19, 256, 16), (17, 512, 5), (17, 256, 23)])
 def test_lifter_head_with_folded_post_norm(J, C, T):
-    """Round 6: the last TemporalBlock's post-norm (norm_t) inside the regression head (pmce_lifter_head_ex_f32) against pmce_ln_chain_f32(out1)
+    """Round 6: the last TemporalBlock's post-norm (norm_t) inside the regression head (pmce_lifter_head_f32, prew) against pmce_ln_chain_f32(out1)
     followed by the plain head - bit for bit - and against an fp64 evaluation of PoseEstimation.py:92,109-113."""
     from pmce_amd import ops
     B = 3      # (T = 16 is the path's clip length; 5 and 23 frames walk the kernel's partly filled and second group of sixteen rows)

@@ -66,13 +66,22 @@ def test_library_exports_every_declared_symbol(lib):
         assert hasattr(raw, name), f"{name} declared in include/pmce_hip.h but not exported"
     assert declared == set(_lib.PROTOTYPES), declared ^ set(_lib.PROTOTYPES)
     assert lib.pmce_version() == 100
+    # ... and the converse: every dynamic symbol the library defines whose unmangled name starts with pmce_ is declared in the header
+    # (the internal helpers are C++-mangled and do not match)
+    import subprocess
+    objdump = "/opt/rocm/lib/llvm/bin/llvm-objdump"
+    if not osp.exists(objdump):
+        pytest.skip("llvm-objdump not available")
+    table = subprocess.run([objdump, "-T", _lib.LIB_PATH], check=True, capture_output=True, text=True).stdout
+    exported = {f[-1] for f in (l.split() for l in table.splitlines()) if len(f) >= 4 and "*UND*" not in f and f[-1].startswith("pmce_")}
+    assert exported == declared, exported ^ declared
 
 
 def test_argument_validation_without_gpu(lib):
     from pmce_amd import _lib
     rc = lib.pmce_gemm_nt_f32(1, 1, None, None, 1, 8, 8, 33, 33, 36, 8, 0, 0, 0, 0, 0, 0, 0, 1, 0, 0, 0, 0, None)
     assert rc == -1 and "K%32" in _lib.last_error()
-    rc = lib.pmce_seq_attention_f32(1, 1, 4, 40, 256, 0, 1, 0, 1, None)
+    rc = lib.pmce_seq_attention_f32(1, 1, 4, 40, 256, 0, 1, 0, 1, 0, None)
     assert rc == -1 and "1..32" in _lib.last_error()
     assert lib.pmce_seq_attention_split_supported(17, 512) == 1 and lib.pmce_seq_attention_split_supported(16, 256) == 1
     assert lib.pmce_seq_attention_split_supported(24, 512) == 0 and lib.pmce_seq_attention_split_supported(17, 384) == 0
