@@ -378,7 +378,7 @@ __global__ __launch_bounds__(448, 4) void vertex_ca_kernel(const float* __restri
   if (tid < 64) sS0[tid] = s0[(long long)b * 64 + tid];
   // normalise (gamma/beta are folded into Kf/s0)
   float n[32];
-  {
+  {  // (slots_mean_inv_std of common.hpp, written out: through the function hipcc allocates this kernel's registers differently)
     float s = 0.f;
 #pragma unroll
     for (int i = 0; i < 32; ++i) s += x[i];
@@ -515,7 +515,7 @@ __device__ __forceinline__ void split_slots8(const float* x_, tl_f16x8& hi, tl_f
 #pragma unroll
   for (int e = 0; e < 8; ++e) hi[e] = (_Float16)x[e];
 #pragma unroll
-  for (int e = 0; e < 8; ++e) lo[e] = (_Float16)((x[e] - (float)hi[e]) * 2048.0f);
+  for (int e = 0; e < 8; ++e) lo[e] = lo_plane_plain(x[e], hi[e]);
 }
 
 // the same with lo at its true magnitude (for operands that carry their own power of two).  lo = rne16(x - hi) is one mixed-precision
@@ -814,20 +814,14 @@ __global__ __launch_bounds__(64 * NW) void vertex_ca_mlp_kernel(const float* __r
     const bool valid = v < NV;
     const long long tok = (long long)b * NV + (valid ? v : NV - 1);
     // ---- cross-attention (vertex_ca_kernel) ----
+    // (The fp32 stage is vertex_ca_kernel's under the compact row mapping, and stays written out in both kernels, as do the masked softmax and
+    // the query-token load: as functions over the row mapping hipcc chose other integer address arithmetic and more registers in both.  The
+    // f16 stage's softmax differs in itself: its scores are rescaled on the way in, its probabilities carry 2^10 and are pinned.)
     if constexpr (!F16) {
       float n[32];
       {
-        float s = 0.f;
-#pragma unroll
-        for (int i = 0; i < 32; ++i) s += x[i];
-        const float mean = pair_sum(s) * (1.0f / 64.0f);
-        float ss = 0.f;
-#pragma unroll
-        for (int i = 0; i < 32; ++i) {
-          const float d = x[i] - mean;
-          ss += d * d;
-        }
-        const float inv = 1.0f / (sqrtf(pair_sum(ss) * (1.0f / 63.0f)) + 1e-6f);
+        float mean, inv;
+        slots_mean_inv_std(x, mean, inv);
 #pragma unroll
         for (int i = 0; i < 32; ++i) n[i] = (x[i] - mean) * inv;
       }
@@ -900,17 +894,9 @@ __global__ __launch_bounds__(64 * NW) void vertex_ca_mlp_kernel(const float* __r
       const float kscale = sS0[64], vscale = sS0[65];
       tl_f16x8 nhi[4], nlo[4];
       {
-        float s = 0.f;
-#pragma unroll
-        for (int i = 0; i < 32; ++i) s += x[i];
-        const float mean = pair_sum(s) * (1.0f / 64.0f);
-        float ss = 0.f;
-#pragma unroll
-        for (int i = 0; i < 32; ++i) {
-          const float d = x[i] - mean;
-          ss += d * d;
-        }
-        const float inv = (1.0f / (sqrtf(pair_sum(ss) * (1.0f / 63.0f)) + 1e-6f)) * 1024.0f;
+        float mean, inv1;
+        slots_mean_inv_std(x, mean, inv1);
+        const float inv = inv1 * 1024.0f;
         float n[32];
 #pragma unroll
         for (int i = 0; i < 32; ++i) n[i] = pinned((x[i] - mean) * inv);  // ONE fp32 value for both planes (common.hpp)
@@ -2018,7 +2004,7 @@ __global__ __launch_bounds__(256) void build_final_operand_kernel(const float* _
     _Float16* row = reinterpret_cast<_Float16*>(A + (long long)b * KP);
     const _Float16 h = (_Float16)v;
     row[(k >> 4) * 32 + (k & 15)] = h;
-    row[(k >> 4) * 32 + 16 + (k & 15)] = (_Float16)((v - (float)h) * 2048.0f);
+    row[(k >> 4) * 32 + 16 + (k & 15)] = lo_plane_plain(v, h);
   } else {
     A[idx] = v;
   }

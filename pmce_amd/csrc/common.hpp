@@ -163,9 +163,12 @@ __device__ __forceinline__ void stage_weight(float* __restrict__ dst, const floa
   }
 }
 
-// LDS-DMA (buffer_load_dwordx4 ... lds): 64 lanes x 16 B from per-lane buffer offsets straight into LDS at M0 + lane * 16 - no VGPR round
-// trip, no ds_write.  hipcc does not count these loads: whoever reads the destination first issues lds_dma_wait() (s_waitcnt vmcnt(0))
-// and, across waves, a barrier.  (M0 is compiler-reserved: saved and restored inside the statement.)
+// LDS-DMA (buffer_load_dwordx4 ... lds): one wave instruction moves 64 lanes x 16 B from per-lane buffer offsets straight into LDS at
+// M0 + lane * 16 - no VGPR round trip, no ds_write.  Buffer form: descriptor on the operand, a 32-bit per-lane byte offset that a caller
+// keeps fixed for a whole tile, the k-tile's byte offset in soffset - a k-loop spends no vector instruction on addresses.  hipcc neither
+// counts nor waits for these loads: whoever reads the destination first issues wait_vm<N>() (s_waitcnt vmcnt(N): all but the wave's N
+// youngest loads, DMAs and stores have landed; lds_dma_wait() = all) and, across waves, a barrier.  (M0 is compiler-reserved: saved and
+// restored inside the statement.)
 __device__ __forceinline__ void lds_dma16(__amdgpu_buffer_rsrc_t rsrc, unsigned voff, int soff, unsigned lds_wave_base) {
   unsigned keep;
   asm volatile(
@@ -174,7 +177,22 @@ __device__ __forceinline__ void lds_dma16(__amdgpu_buffer_rsrc_t rsrc, unsigned 
       : "v"(voff), "s"(rsrc), "s"(lds_wave_base), "s"(soff)
       : "memory");
 }
-__device__ __forceinline__ void lds_dma_wait() { asm volatile("s_waitcnt vmcnt(0)" ::: "memory"); }
+// The same with the LDS destination as base + compile-time offset - what the split GEMM's k-loop issues (round 6): ONE base scalar per stage
+// instead of one live scalar per instruction (the compiler had parked those in VGPR lanes and fetched each with a v_readlane per k-tile -
+// vector instructions, which cost matrix time on this chip).
+__device__ __forceinline__ void sdma16o(__amdgpu_buffer_rsrc_t rsrc, unsigned voff, int soff, unsigned lds_base, int imm) {
+  unsigned keep;
+  asm volatile(
+      "s_mov_b32 %0, m0\n\ts_add_u32 m0, %3, %5\n\ts_nop 0\n\tbuffer_load_dwordx4 %1, %2, %4 offen lds\n\ts_mov_b32 m0, %0"
+      : "=&s"(keep)
+      : "v"(voff), "s"(rsrc), "s"(lds_base), "s"(soff), "n"(imm)
+      : "memory", "scc");
+}
+template <int N>
+__device__ __forceinline__ void wait_vm() {
+  asm volatile("s_waitcnt vmcnt(%0)" ::"n"(N) : "memory");
+}
+__device__ __forceinline__ void lds_dma_wait() { wait_vm<0>(); }
 // Linear copy of `kib` KiB (16-byte aligned source, LDS destination) by LDS-DMA: every wave instruction moves 1 KiB, the waves take the
 // 1 KiB pieces round-robin and issue all of theirs back to back (<= 63 per wave: the counter's range).  lds_dma_wait + barrier before use.
 __device__ __forceinline__ void lds_dma_copy(float* lds_dst, const float* src, int kib, int wave, int nwaves, int lane) {
@@ -184,10 +202,29 @@ __device__ __forceinline__ void lds_dma_copy(float* lds_dst, const float* src, i
   for (int c = w0; c < kib; c += nwaves) lds_dma16(rsrc, (unsigned)(c * 1024 + lane * 16), 0, base + (unsigned)c * 1024u);
 }
 
-// Four consecutive channels c..c+3 (c % 4 == 0) of a row, written in the pre-split operand layout of the three-product f16 GEMM
-// (gemm_split_f16.hip): per 16-wide k-tile 16 f16 "hi" then 16 f16 "lo * 2^11".  `row` is the row's start (the packed row takes
-// the bytes of the fp32 row).
 typedef _Float16 f16x4 __attribute__((ext_vector_type(4)));
+typedef _Float16 f16x8 __attribute__((ext_vector_type(8)));
+
+// The two-term split of the three-product f16 GEMM (gemm_split_f16.hip): fp32 x -> f16 planes hi = rne16(x), lo = rne16((x - hi) * 2^11).
+// Two spellings, and every site keeps the one it has: they agree bit for bit for every x whose hi is finite (x - hi and the products by
+// 2^11 are exact in fp32 then), and differ where hi overflows.
+// Both take hi = (_Float16)x from the caller: the vector helpers convert all their elements before the first lo, and the instruction
+// order that hipcc emits follows the source's.
+// The plain form: conversion back, subtraction, multiplication.
+__device__ __forceinline__ _Float16 lo_plane_plain(float x, _Float16 hi) { return (_Float16)((x - (float)hi) * 2048.0f); }
+// The fused form: ONE fused multiply-add on the f16 itself (v_fma_mix_f32: no separate f16 -> f32 conversion, no separate
+// subtraction) - for the kernels bound by vector issue (the matrix-pipe attention: 980 vector instructions per head and unit against 24
+// matrix instructions, the splits a third of them; the split GEMM's pre-split epilogue).
+__device__ __forceinline__ _Float16 lo_plane(float x, _Float16 hi) { return (_Float16)fmaf((float)hi, -2048.0f, x * 2048.0f); }
+// eight values at once, plain form
+__device__ __forceinline__ void split8(const f32x4& x0, const f32x4& x1, f16x8& hi, f16x8& lo) {
+  const float v[8] = {x0.x, x0.y, x0.z, x0.w, x1.x, x1.y, x1.z, x1.w};
+#pragma unroll
+  for (int e = 0; e < 8; ++e) hi[e] = (_Float16)v[e];
+#pragma unroll
+  for (int e = 0; e < 8; ++e) lo[e] = lo_plane_plain(v[e], hi[e]);
+}
+
 // A COMPUTED value that is about to be split into its (hi, lo) f16 planes goes through this first.  Under -ffp-contract=fast hipcc
 // folds the arithmetic that produced v into each conversion on its own: hi = v_fma_mixlo_f16(a, b) (ONE rounding, of the exact
 // product) in one place and v_cvt_f16_f32 of the fp32-rounded a*b in another.  When rne32(a*b) is an f16 tie the two disagree by
@@ -197,21 +234,24 @@ __device__ __forceinline__ float pinned(float v) {
   asm volatile("" : "+v"(v));
   return v;
 }
+// Four consecutive channels c..c+3 (c % 4 == 0) of a row, written in the pre-split operand layout of the three-product f16 GEMM
+// (gemm_split_f16.hip): per 16-wide k-tile 16 f16 "hi" then 16 f16 "lo * 2^11".  `row` is the row's start (the packed row takes
+// the bytes of the fp32 row).
 __device__ __forceinline__ void store4_split_f16(float* __restrict__ row, int c, const f32x4& v_) {
   f16x4 hi, lo;
   const f32x4 v = {pinned(v_[0]), pinned(v_[1]), pinned(v_[2]), pinned(v_[3])};
 #pragma unroll
   for (int e = 0; e < 4; ++e) hi[e] = (_Float16)v[e];
 #pragma unroll
-  for (int e = 0; e < 4; ++e) lo[e] = (_Float16)((v[e] - (float)hi[e]) * 2048.0f);
+  for (int e = 0; e < 4; ++e) lo[e] = lo_plane_plain(v[e], hi[e]);
   _Float16* p = reinterpret_cast<_Float16*>(row) + (c >> 4) * 32 + (c & 15);
   *reinterpret_cast<f16x4*>(p) = hi;
   *reinterpret_cast<f16x4*>(p + 16) = lo;
 }
 
-// AdaLayerNorm on a slot-layout token (reference CoevoDecoder.py:23-29): unbiased std, eps on the std.
-// gb points at this clip's [gamma(64) | beta(64)] for the instance.
-__device__ __forceinline__ void adaln_slots(const float* x, float* y, const float* __restrict__ gb, int hb) {
+// The statistics of AdaLayerNorm on a slot-layout token (reference CoevoDecoder.py:23-29): the mean over the lane pair's 64 channels and
+// 1 / (unbiased std + eps), eps on the std.
+__device__ __forceinline__ void slots_mean_inv_std(const float* x, float& mean_, float& inv_) {
   float s = 0.f;
 #pragma unroll
   for (int i = 0; i < 32; ++i) s += x[i];
@@ -223,7 +263,13 @@ __device__ __forceinline__ void adaln_slots(const float* x, float* y, const floa
     ss += d * d;
   }
   const float var = pair_sum(ss) * (1.0f / 63.0f);
-  const float inv = 1.0f / (sqrtf(var) + 1e-6f);
+  mean_ = mean;
+  inv_ = 1.0f / (sqrtf(var) + 1e-6f);
+}
+// AdaLayerNorm on a slot-layout token.  gb points at this clip's [gamma(64) | beta(64)] for the instance.
+__device__ __forceinline__ void adaln_slots(const float* x, float* y, const float* __restrict__ gb, int hb) {
+  float mean, inv;
+  slots_mean_inv_std(x, mean, inv);
 #pragma unroll
   for (int q = 0; q < 8; ++q) {
     const f32x4 g = *reinterpret_cast<const f32x4*>(gb + 8 * q + 4 * hb);

@@ -56,19 +56,6 @@ struct PendingEpi {  // the finished-but-not-yet-stored tile (all fields wave-un
   bool valid;
 };
 
-// LDS-DMA: one wave instruction moves 64 x 16 B from per-lane buffer offsets straight into LDS at M0 + lane*16 (no
-// VGPR round trip, no ds_write).  Buffer form: descriptor on the operand, a 32-bit per-lane byte offset that is fixed
-// for a whole tile, the k-tile's byte offset in soffset - the k-loop spends no vector instruction on addresses.
-// hipcc neither counts nor waits for it: the k-loop drains it with an explicit s_waitcnt vmcnt(0) ahead of its
-// barrier.  M0 is compiler-reserved, hence saved/restored inside the statement.
-__device__ __forceinline__ void dma16(__amdgpu_buffer_rsrc_t rsrc, unsigned voff, int soff, unsigned lds_wave_base) {
-  unsigned keep;
-  asm volatile(
-      "s_mov_b32 %0, m0\n\ts_mov_b32 m0, %3\n\ts_nop 0\n\tbuffer_load_dwordx4 %1, %2, %4 offen lds\n\ts_mov_b32 m0, %0"
-      : "=&s"(keep)
-      : "v"(voff), "s"(rsrc), "s"(lds_wave_base), "s"(soff)
-      : "memory");
-}
 __device__ __forceinline__ unsigned lds_addr(const float* p) {
   return (unsigned)(uintptr_t)(const __attribute__((address_space(3))) float*)p;
 }
@@ -151,12 +138,12 @@ __global__ __launch_bounds__(256, 2) void gemm_nt_kernel(GemmParams p) {
   auto gdma = [&](int kt, int buf) {  // k-tile kt of the pointed-at tile -> LDS buffer `buf`
     const int ko = kt * 128;  // bytes
 #pragma unroll
-    for (int i = 0; i < LA; ++i) dma16(rsrc_a, aoff[i], ko, lds_a + (buf * BM + 32 * i) * (LD * 4));
+    for (int i = 0; i < LA; ++i) lds_dma16(rsrc_a, aoff[i], ko, lds_a + (buf * BM + 32 * i) * (LD * 4));
 #pragma unroll
-    for (int i = 0; i < LB; ++i) dma16(rsrc_w, boff[i], ko, lds_b + (buf * BN + 32 * i) * (LD * 4));
+    for (int i = 0; i < LB; ++i) lds_dma16(rsrc_w, boff[i], ko, lds_b + (buf * BN + 32 * i) * (LD * 4));
   };
   auto dma_wait_and_sync = [&]() {
-    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+    lds_dma_wait();
     __syncthreads();
   };
 

@@ -1,9 +1,7 @@
-// Shared pieces of the three-product f16 GEMM kernels (gemm_split_f16.hip: the 4-wave tiles; gemm_split_ws.hip: the
-// wave-specialised 192x256 tile).  Arithmetic and operand layout: see the header of gemm_split_f16.hip.
+// Shared pieces of the three-product f16 GEMM kernels (gemm_split_f16.hip: the persistent 4-wave tiles; gemm_split_small.hip: the
+// small-grid form) and of the matrix-pipe attention.  Arithmetic and operand layout: see the header of gemm_split_f16.hip.
 #pragma once
 #include "common.hpp"
-
-typedef _Float16 f16x8 __attribute__((ext_vector_type(8)));
 
 struct SplitParams {
   const float* A;       // fp32 [M][lda], or packed planes [M][K/16][16 hi | 16 lo*2^11] f16 (APACK)
@@ -31,37 +29,6 @@ struct SplitParams {
   float *out1, *out2;
 };
 
-// LDS-DMA: 64 lanes x 16 B from per-lane buffer offsets into LDS at M0 + lane*16 (see gemm_f32.hip)
-__device__ __forceinline__ void sdma16(__amdgpu_buffer_rsrc_t rsrc, unsigned voff, int soff, unsigned lds_wave_base) {
-  unsigned keep;
-  asm volatile(
-      "s_mov_b32 %0, m0\n\ts_mov_b32 m0, %3\n\ts_nop 0\n\tbuffer_load_dwordx4 %1, %2, %4 offen lds\n\ts_mov_b32 m0, %0"
-      : "=&s"(keep)
-      : "v"(voff), "s"(rsrc), "s"(lds_wave_base), "s"(soff)
-      : "memory");
-}
-
-// The same with the LDS destination as base + compile-time offset - what the k-loop issues (round 6): ONE base scalar per stage instead of one live
-// scalar per instruction (the compiler had parked those in VGPR lanes and fetched each with a v_readlane per k-tile - vector instructions, which cost
-// matrix time on this chip).
-__device__ __forceinline__ void sdma16o(__amdgpu_buffer_rsrc_t rsrc, unsigned voff, int soff, unsigned lds_base, int imm) {
-  unsigned keep;
-  asm volatile(
-      "s_mov_b32 %0, m0\n\ts_add_u32 m0, %3, %5\n\ts_nop 0\n\tbuffer_load_dwordx4 %1, %2, %4 offen lds\n\ts_mov_b32 m0, %0"
-      : "=&s"(keep)
-      : "v"(voff), "s"(rsrc), "s"(lds_base), "s"(soff), "n"(imm)
-      : "memory", "scc");
-}
-
-// fp32 -> (hi, lo * 2^11) f16
-__device__ __forceinline__ void split8(const f32x4& x0, const f32x4& x1, f16x8& hi, f16x8& lo) {
-  const float v[8] = {x0.x, x0.y, x0.z, x0.w, x1.x, x1.y, x1.z, x1.w};
-#pragma unroll
-  for (int e = 0; e < 8; ++e) hi[e] = (_Float16)v[e];
-#pragma unroll
-  for (int e = 0; e < 8; ++e) lo[e] = (_Float16)((v[e] - (float)hi[e]) * 2048.0f);
-}
-
 // 1 / x for x = 2^e, e in [-126, 126], exactly: the exponent field mirrored around the bias
 __device__ __forceinline__ float pow2_recip(float x) { return __uint_as_float(0x7f000000u - __float_as_uint(x)); }
 
@@ -80,19 +47,11 @@ __device__ __forceinline__ unsigned split_pack_exchange(float x, unsigned perm_s
   typedef _Float16 h2_t __attribute__((ext_vector_type(2)));
   const _Float16 h = (_Float16)x;
   bad = bad || __builtin_amdgcn_classh(h, 0x207);  // inf / nan: also a finite x beyond f16's 65504 - the next product could not read it
-  // (x - h) * 2^11 as ONE fused multiply-add on the f16 itself (v_fma_mix: no separate conversion and subtraction): x - h and the products by
-  // 2^11 are exact in fp32, so the fused form has the bits of the three-instruction form
-  const _Float16 l = (_Float16)fmaf((float)h, -2048.0f, x * 2048.0f);
+  const _Float16 l = lo_plane(x, h);  // the fused form: same bits as the plain one for every x whose hi is finite
   const unsigned w = __builtin_bit_cast(unsigned, h2_t{h, l});
   const unsigned nbr = (unsigned)__builtin_amdgcn_update_dpp(0, (int)w, 0xB1, 0xf, 0xf, true);  // lane ^ 1
   return __builtin_amdgcn_perm(nbr, w, perm_sel);
 }
-
-template <int N>
-__device__ __forceinline__ void wait_vm() {
-  asm volatile("s_waitcnt vmcnt(%0)" ::"n"(N) : "memory");
-}
-
 
 // gemm_split_small.hip: the small-grid form (one 64 x 128 tile per workgroup, eight waves, at most one round of workgroups)
 bool pmce_gemm_split_small_applies(int M, int N, int K, int act, bool apack, bool opack, bool res, bool rs);

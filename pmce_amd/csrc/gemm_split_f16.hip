@@ -159,10 +159,10 @@ __global__ __launch_bounds__(256, 2) void gemm_split_kernel(SplitParams p) {
   set_ptrs(i_mb, i_nb);
   auto issue_next = [&]() {
     if (i_kt == 0) {  // the tile's bias and 2^-s slices: 64 lanes x 4 floats each
-      if (p.bias && wave == 0) sdma16(rsrc_b, (unsigned)lane * 16u, i_nb * 4, lds0 + NS * SF * 4 + i_par * 2048);
-      if (wave == 1) sdma16(rsrc_s, (unsigned)lane * 16u, i_nb * 4, lds0 + NS * SF * 4 + i_par * 2048 + 1024);
+      if (p.bias && wave == 0) lds_dma16(rsrc_b, (unsigned)lane * 16u, i_nb * 4, lds0 + NS * SF * 4 + i_par * 2048);
+      if (wave == 1) lds_dma16(rsrc_s, (unsigned)lane * 16u, i_nb * 4, lds0 + NS * SF * 4 + i_par * 2048 + 1024);
       if constexpr (RS)  // and its BM row scales (behind the two slice pairs)
-        if (wave == 2) sdma16(rsrc_rs, (unsigned)lane * 16u, i_mb * 4, lds0 + NS * SF * 4 + 4096 + i_par * 1024);
+        if (wave == 2) lds_dma16(rsrc_rs, (unsigned)lane * 16u, i_mb * 4, lds0 + NS * SF * 4 + 4096 + i_par * 1024);
       i_par ^= 1;
     }
     issue(i_kt, i_stage);
@@ -769,7 +769,7 @@ __global__ void split_rows_kernel(const float* __restrict__ A, long long M, int 
     const int k = (int)(i % K);
     const float a = A[m * lda + k];
     const _Float16 hi = (_Float16)a;
-    const _Float16 lo = (_Float16)((a - (float)hi) * 2048.0f);
+    const _Float16 lo = lo_plane_plain(a, hi);
     _Float16* row = Ap + (m * K + (k / 16) * 16) * 2;
     row[k % 16] = hi;
     row[16 + k % 16] = lo;
@@ -815,7 +815,7 @@ __global__ __launch_bounds__(256) void split_rows_scaled_kernel(const float* __r
 #pragma unroll
       for (int i = 0; i < 4; ++i) hi[i] = (_Float16)a[i];
 #pragma unroll
-      for (int i = 0; i < 4; ++i) lo[i] = (_Float16)((a[i] - (float)hi[i]) * 2048.0f);
+      for (int i = 0; i < 4; ++i) lo[i] = lo_plane_plain(a[i], hi[i]);
       _Float16* q = out + (k >> 4) * 32 + (k & 15);
       *reinterpret_cast<f16x4*>(q) = hi;
       *reinterpret_cast<f16x4*>(q + 16) = lo;

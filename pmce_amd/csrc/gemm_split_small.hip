@@ -99,7 +99,7 @@ __global__ __launch_bounds__(128 * NWN) void gemm_split_small_kernel(SplitParams
   auto issue_next = [&]() {
 #pragma unroll
     for (int q = 0; q < DPW; ++q)
-      sdma16(d_is_a[q] ? rsrc_a : rsrc_w, doff[q], dk0[q] + 2 * i_s * dks[q], lds0 + i_slot * (S_SF * 4) + dlds[q]);
+      lds_dma16(d_is_a[q] ? rsrc_a : rsrc_w, doff[q], dk0[q] + 2 * i_s * dks[q], lds0 + i_slot * (S_SF * 4) + dlds[q]);
     ++i_s;
     i_slot = i_slot + 1 == S_NS ? 0 : i_slot + 1;
   };

@@ -33,15 +33,15 @@ struct GruStepArgs {
                           // with every CU streaming, the L2 -> LDS path delivers 58 instead of 30 B/clk per CU (scripts/microbench/dma_patterns.hip)
 };
 
-typedef _Float16 gru_f16x8 __attribute__((ext_vector_type(8)));
-
-__device__ __forceinline__ void gru_dma16(__amdgpu_buffer_rsrc_t rsrc, unsigned voff, int soff, unsigned lds_wave_base) {
-  unsigned keep;  // M0 is compiler-reserved: saved and restored inside the statement
-  asm volatile(
-      "s_mov_b32 %0, m0\n\ts_mov_b32 m0, %3\n\ts_nop 0\n\tbuffer_load_dwordx4 %1, %2, %4 offen lds\n\ts_mov_b32 m0, %0"
-      : "=&s"(keep)
-      : "v"(voff), "s"(rsrc), "s"(lds_wave_base), "s"(soff)
-      : "memory");
+// The gate update of one (batch row, unit): gi_* = the input projections (b_ih included), gh_* = the row of h W_hh^T, bh_* = b_hh, h = the
+// unit's previous state.  Returns h'.  ONE copy for the two split-f16 step kernels, which a test requires to agree bit for bit; the fp32
+// step keeps the same four lines written out (through this function hipcc allocates its registers differently).
+__device__ __forceinline__ float gru_gate_update(float gi_r, float gi_z, float gi_n, float gh_r, float gh_z, float gh_n, float bh_r,
+                                                 float bh_z, float bh_n, float h) {
+  const float rr = sigmoidf_acc(gi_r + (gh_r + bh_r));
+  const float zz = sigmoidf_acc(gi_z + (gh_z + bh_z));
+  const float nn = tanhf(gi_n + rr * (gh_n + bh_n));
+  return (1.0f - zz) * nn + zz * h;
 }
 
 // fp32 pipe (the split mode's step is gru_step_v2_kernel below).  NQ = 4 K-slices per workgroup: 8 waves (two per SIMD: one wave's
@@ -114,9 +114,9 @@ __global__ __launch_bounds__(512) void gru_step_kernel(GruStepArgs a) {
       const int soff = (kq * Kq + kt * KS) * 4;
       const unsigned dst = lds_wave + (kt & 1) * STAGE;
 #pragma unroll
-      for (int i = 0; i < NA; ++i) gru_dma16(rsrc_h, hoff[i], soff, dst + i * 1024);
+      for (int i = 0; i < NA; ++i) lds_dma16(rsrc_h, hoff[i], soff, dst + i * 1024);
 #pragma unroll
-      for (int i = 0; i < NW; ++i) gru_dma16(rsrc_w, woff[i], soff, dst + 32 * ROWB + i * 1024);
+      for (int i = 0; i < NW; ++i) lds_dma16(rsrc_w, woff[i], soff, dst + 32 * ROWB + i * 1024);
     };
     const int nk = Kq / KS;
     const float* my = smem + wave * (2 * STAGE / 4);
@@ -126,9 +126,9 @@ __global__ __launch_bounds__(512) void gru_step_kernel(GruStepArgs a) {
       if (kt + 1 < nk) {
         dma_stage(kt + 1);
         // all but the NA+NW just issued: stage kt has landed
-        asm volatile("s_waitcnt vmcnt(8)" ::: "memory");
+        wait_vm<NA + NW>();
       } else {
-        asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+        wait_vm<0>();
       }
       const float* As = my + (kt & 1) * (STAGE / 4) + n0 * KS;
       const float* Bs = my + (kt & 1) * (STAGE / 4) + 32 * KS + n0 * KS;
@@ -202,10 +202,10 @@ __global__ __launch_bounds__(512) void gru_step_kernel(GruStepArgs a) {
 
 // ------------------------------------------------------------------------------------------------------
 // Round 4: the split-f16 step with the operand traffic cut by a third and a deeper ring.  Same tile (64 batch rows x 32 units x
-// {r, z, n}), same 8 waves = 2 row blocks x 4 K-quarters, same arithmetic and summation order as gru_step_kernel<4, true> - results
-// are bit-identical - but the two row-block waves of a K-quarter no longer stage PRIVATE copies of the quarter's 96 W_hh rows (each
-// fetched them: 1.04 MB per workgroup and step for 0.65 MB of operands, and with two 8 KB stages per wave the 16 k-tiles were 16
-// exposed round trips - the step's 21-24 us were the fill, `scripts/microbench/gru_ablate.py`).  Here a K-quarter owns ONE ring of
+// {r, z, n}), same 8 waves = 2 row blocks x 4 K-quarters, same order of k-tiles and of meeting the K-quarters as
+// gru_step_kernel (whose split-f16 instantiation this replaced, bit for bit) - but the two row-block waves of a K-quarter no longer stage PRIVATE
+// copies of the quarter's 96 W_hh rows (each fetched them: 1.04 MB per workgroup and step for 0.65 MB of operands, and with two 8 KB
+// stages per wave the 16 k-tiles were 16 exposed round trips - the step's 21-24 us were the fill).  Here a K-quarter owns ONE ring of
 // three 10 KB stages [64 h rows | 96 W rows] x 64 B; each of its two waves DMAs its own 32 h rows and HALF of the W rows (5 instead
 // of 8 instructions per k-tile), two k-tiles are in flight behind the one being multiplied, and one workgroup barrier per k-tile
 // makes the partner's half visible (8 waves, two per SIMD: the barrier is cheap next to a round trip).  120 KB of LDS.
@@ -272,9 +272,9 @@ __global__ __launch_bounds__(512) void gru_step_v2_kernel(GruStepArgs a) {
       const int soff = (kq * Kq + kt * 16) * 4, soff_w = (kq * (Kq / 16) + kt) * wks;
       const unsigned dst = lds_q + (kt % NS) * STAGE;
 #pragma unroll
-      for (int i = 0; i < 2; ++i) gru_dma16(rsrc_h, hoff[i], soff, dst + (32 * rb + 16 * i) * 64);
+      for (int i = 0; i < 2; ++i) lds_dma16(rsrc_h, hoff[i], soff, dst + (32 * rb + 16 * i) * 64);
 #pragma unroll
-      for (int i = 0; i < 3; ++i) gru_dma16(rsrc_w, woff[i], soff_w, dst + (64 + 48 * rb + 16 * i) * 64);
+      for (int i = 0; i < 3; ++i) lds_dma16(rsrc_w, woff[i], soff_w, dst + (64 + 48 * rb + 16 * i) * 64);
     };
     const int nk = Kq / 16;
     const float* ring = smem + kq * (NS * STAGE / 4);
@@ -283,8 +283,8 @@ __global__ __launch_bounds__(512) void gru_step_v2_kernel(GruStepArgs a) {
     dma_stage(1);
     for (int kt = 0; kt < nk; ++kt) {
       // k-tile kt has landed when at most the 5 DMAs of tile kt + 1 are still in flight (in-order completion)
-      if (kt + 1 < nk) asm volatile("s_waitcnt vmcnt(5)" ::: "memory");
-      else asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+      if (kt + 1 < nk) wait_vm<5>();
+      else wait_vm<0>();
       __syncthreads();  // the partner's half of tile kt is in LDS; every wave is done reading tile kt - 1
       if (kt + 2 < nk) dma_stage(kt + 2);  // into the stage tile kt - 1 occupied
       const float* st = ring + (kt % NS) * (STAGE / 4);
@@ -293,16 +293,16 @@ __global__ __launch_bounds__(512) void gru_step_v2_kernel(GruStepArgs a) {
       const f32x4 x0 = *reinterpret_cast<const f32x4*>(As + 4 * ((2 * hb) ^ swz));      // k = 8 hb + [0, 4)
       const f32x4 x1 = *reinterpret_cast<const f32x4*>(As + 4 * ((2 * hb + 1) ^ swz));  // k = 8 hb + [4, 8)
       const float xv[8] = {x0.x, x0.y, x0.z, x0.w, x1.x, x1.y, x1.z, x1.w};
-      gru_f16x8 ahi, alo;
+      f16x8 ahi, alo;
 #pragma unroll
       for (int e = 0; e < 8; ++e) ahi[e] = (_Float16)xv[e];
 #pragma unroll
-      for (int e = 0; e < 8; ++e) alo[e] = (_Float16)((xv[e] - (float)ahi[e]) * 2048.0f);
-      gru_f16x8 whi[3], wlo[3], wh2[3];
+      for (int e = 0; e < 8; ++e) alo[e] = lo_plane_plain(xv[e], ahi[e]);
+      f16x8 whi[3], wlo[3], wh2[3];
 #pragma unroll
       for (int g = 0; g < 3; ++g) {
-        whi[g] = *reinterpret_cast<const gru_f16x8*>(Bs + g * 32 * 16 + 4 * (hb ^ swz));        // hi plane, k = 8 hb + [0, 8)
-        wlo[g] = *reinterpret_cast<const gru_f16x8*>(Bs + g * 32 * 16 + 4 * ((2 + hb) ^ swz));  // lo plane
+        whi[g] = *reinterpret_cast<const f16x8*>(Bs + g * 32 * 16 + 4 * (hb ^ swz));        // hi plane, k = 8 hb + [0, 8)
+        wlo[g] = *reinterpret_cast<const f16x8*>(Bs + g * 32 * 16 + 4 * ((2 + hb) ^ swz));  // lo plane
         wh2[g] = whi[g] * (_Float16)0.00048828125f;
       }
 #pragma unroll
@@ -361,12 +361,7 @@ __global__ __launch_bounds__(512) void gru_step_v2_kernel(GruStepArgs a) {
     an *= wd_n;
     const int r = RW * kq + q;
     const int m = m0 + rb * 32 + (r & 3) + 8 * (r >> 2) + 4 * hb;
-    if (m < a.B) {
-      const float rr = sigmoidf_acc(gir[q] + (ar + bhr));
-      const float zz = sigmoidf_acc(giz[q] + (az + bhz));
-      const float nn = tanhf(gin[q] + rr * (an + bhn));
-      ho[(long long)m * a.h_rs + u] = (1.0f - zz) * nn + zz * hpv[q];
-    }
+    if (m < a.B) ho[(long long)m * a.h_rs + u] = gru_gate_update(gir[q], giz[q], gin[q], ar, az, an, bhr, bhz, bhn, hpv[q]);
   }
 }
 
@@ -449,9 +444,9 @@ __global__ __launch_bounds__(256) void gru_step_small_kernel(GruStepArgs a) {
       const int soff = (kq * Kq + kt * 16) * 4, soff_w = (kq * (Kq / 16) + kt) * wks;
       const unsigned dst = lds_q + (kt % NS) * STAGE;
 #pragma unroll
-      for (int i = 0; i < 2 * NT; ++i) gru_dma16(rsrc_h, hoff[i], soff, dst + 16 * i * 64);
+      for (int i = 0; i < 2 * NT; ++i) lds_dma16(rsrc_h, hoff[i], soff, dst + 16 * i * 64);
 #pragma unroll
-      for (int i = 0; i < 2; ++i) gru_dma16(rsrc_w, woff[i], soff_w, dst + (32 * NT + 16 * i) * 64);
+      for (int i = 0; i < 2; ++i) lds_dma16(rsrc_w, woff[i], soff_w, dst + (32 * NT + 16 * i) * 64);
     };
     const int nk = Kq / 16;
     const float* ring = smem + kq * (NS * STAGE / 4);
@@ -459,15 +454,15 @@ __global__ __launch_bounds__(256) void gru_step_small_kernel(GruStepArgs a) {
     for (int kt = 0; kt < NS - 1 && kt < nk; ++kt) dma_stage(kt);
     for (int kt = 0; kt < nk; ++kt) {
       // tile kt has landed when at most the NS - 2 tiles issued after it are in flight (in-order completion); the tail waits for all
-      if (kt + NS - 2 < nk) asm volatile("s_waitcnt vmcnt(%0)" ::"n"((NS - 2) * NI) : "memory");
-      else asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+      if (kt + NS - 2 < nk) wait_vm<(NS - 2) * NI>();
+      else wait_vm<0>();
       if (kt + NS - 1 < nk) dma_stage(kt + NS - 1);  // into the stage tile kt - 1 occupied (its fragment reads were issued an iteration ago)
       const float* st = ring + (kt % NS) * (STAGE / 4);
       const float* Bs = st + (32 * NT + n0) * 16;
-      const gru_f16x8 whi = *reinterpret_cast<const gru_f16x8*>(Bs + 4 * (hb ^ swz));        // hi plane, k = 8 hb + [0, 8)
-      const gru_f16x8 wlo = *reinterpret_cast<const gru_f16x8*>(Bs + 4 * ((2 + hb) ^ swz));  // lo plane
-      const gru_f16x8 wh2 = whi * (_Float16)0.00048828125f;
-      gru_f16x8 ahi[NT], alo[NT];
+      const f16x8 whi = *reinterpret_cast<const f16x8*>(Bs + 4 * (hb ^ swz));        // hi plane, k = 8 hb + [0, 8)
+      const f16x8 wlo = *reinterpret_cast<const f16x8*>(Bs + 4 * ((2 + hb) ^ swz));  // lo plane
+      const f16x8 wh2 = whi * (_Float16)0.00048828125f;
+      f16x8 ahi[NT], alo[NT];
 #pragma unroll
       for (int nt = 0; nt < NT; ++nt) {
         const float* As = st + (32 * nt + n0) * 16;
@@ -477,7 +472,7 @@ __global__ __launch_bounds__(256) void gru_step_small_kernel(GruStepArgs a) {
 #pragma unroll
         for (int e = 0; e < 8; ++e) ahi[nt][e] = (_Float16)xv[e];
 #pragma unroll
-        for (int e = 0; e < 8; ++e) alo[nt][e] = (_Float16)((xv[e] - (float)ahi[nt][e]) * 2048.0f);
+        for (int e = 0; e < 8; ++e) alo[nt][e] = lo_plane_plain(xv[e], ahi[nt][e]);
       }
 #pragma unroll
       for (int nt = 0; nt < NT; ++nt) acc[nt] = __builtin_amdgcn_mfma_f32_32x32x16_f16(ahi[nt], whi, acc[nt], 0, 0, 0);
@@ -517,10 +512,7 @@ __global__ __launch_bounds__(256) void gru_step_small_kernel(GruStepArgs a) {
     const int m = 32 * nt + gm;
     if (m < a.B) {
       const float ar = fin[nt][0] * wd_r, az = fin[nt][1] * wd_z, an = fin[nt][2] * wd_n;
-      const float rr = sigmoidf_acc(gir[nt] + (ar + bhr));
-      const float zz = sigmoidf_acc(giz[nt] + (az + bhz));
-      const float nn = tanhf(gin[nt] + rr * (an + bhn));
-      ho[(long long)m * a.h_rs + gu] = (1.0f - zz) * nn + zz * hpv[nt];
+      ho[(long long)m * a.h_rs + gu] = gru_gate_update(gir[nt], giz[nt], gin[nt], ar, az, an, bhr, bhz, bhn, hpv[nt]);
     }
   }
 }

@@ -41,9 +41,9 @@ __global__ __launch_bounds__(256) void embed_tokens_kernel(const float* __restri
 //   out1 = y1 (if out1) ;  out2 = LN(y1; w2,b2,eps2) (if out2)
 // covers norm_s/norm_t (shared across depth, eps 1e-6, :38,84,92) fused with the NEXT block's norm1/norm2.
 // ------------------------------------------------------------------------------------------------------
+// mean and 1 / sqrt(biased variance + eps) of the row a wavefront holds as v[C / 64]
 template <int C>
-__device__ __forceinline__ void ln_regs(float* v, const float* __restrict__ w, const float* __restrict__ b, float eps,
-                                        int lane) {
+__device__ __forceinline__ void ln_stats(const float* v, float eps, float& mean_, float& inv_) {
   constexpr int NV = C / 64;
   float s = 0.f;
 #pragma unroll
@@ -57,8 +57,16 @@ __device__ __forceinline__ void ln_regs(float* v, const float* __restrict__ w, c
   }
   const float var = wave_sum(ss) * (1.0f / C);
   const float inv = 1.0f / sqrtf(var + eps);
+  mean_ = mean;
+  inv_ = inv;
+}
+template <int C>
+__device__ __forceinline__ void ln_regs(float* v, const float* __restrict__ w, const float* __restrict__ b, float eps,
+                                        int lane) {
+  float mean, inv;
+  ln_stats<C>(v, eps, mean, inv);
 #pragma unroll
-  for (int i4 = 0; i4 < NV / 4; ++i4) {
+  for (int i4 = 0; i4 < C / 256; ++i4) {
     const int c = i4 * 256 + lane * 4;
     const f32x4 wv = *reinterpret_cast<const f32x4*>(w + c);
     const f32x4 bv = *reinterpret_cast<const f32x4*>(b + c);
@@ -71,21 +79,10 @@ __device__ __forceinline__ void ln_regs(float* v, const float* __restrict__ w, c
 // per row, the parameters are more vector-cache traffic than the row itself).  The same operations in the same order: the same bits.
 template <int C>
 __device__ __forceinline__ void ln_regs_pre(float* v, const float* wreg, const float* breg, float eps) {
-  constexpr int NV = C / 64;
-  float s = 0.f;
+  float mean, inv;
+  ln_stats<C>(v, eps, mean, inv);
 #pragma unroll
-  for (int i = 0; i < NV; ++i) s += v[i];
-  const float mean = wave_sum(s) * (1.0f / C);
-  float ss = 0.f;
-#pragma unroll
-  for (int i = 0; i < NV; ++i) {
-    const float d = v[i] - mean;
-    ss += d * d;
-  }
-  const float var = wave_sum(ss) * (1.0f / C);
-  const float inv = 1.0f / sqrtf(var + eps);
-#pragma unroll
-  for (int i = 0; i < NV; ++i) v[i] = (v[i] - mean) * inv * wreg[i] + breg[i];
+  for (int i = 0; i < C / 64; ++i) v[i] = (v[i] - mean) * inv * wreg[i] + breg[i];
 }
 // this lane's channels (256 i4 + 4 lane + [0, 4)) of a per-channel vector
 template <int C>
@@ -98,8 +95,14 @@ __device__ __forceinline__ void lane_channels(const float* __restrict__ p, int l
   }
 }
 
-// Optional window gather (streaming): with win != nullptr, output row (w*T + t)*J + j reads input row
-// frame(w,t)*J + j, frame = win[2w] + t (or win[2w] when win[2w] == win[2w+1]: a single frame repeated).
+// Streaming: the frame that position t of window w shows: win[2w] + t, or win[2w] when win[2w] == win[2w+1] (a single frame repeated),
+// clamped to the L frames there are.
+__device__ __forceinline__ int window_frame(const int* __restrict__ win, long long w, int t, int L) {
+  const int s0 = win[2 * w], e0 = win[2 * w + 1];
+  return min(max(s0 == e0 ? s0 : s0 + t, 0), L - 1);
+}
+
+// Optional window gather (streaming): with win != nullptr, output row (w*T + t)*J + j reads input row window_frame(w,t)*J + j.
 template <int C>
 __global__ __launch_bounds__(256) void ln_chain_kernel(const float* __restrict__ x, long long rows,
                                                        const float* __restrict__ w1, const float* __restrict__ b1,
@@ -115,10 +118,7 @@ __global__ __launch_bounds__(256) void ln_chain_kernel(const float* __restrict__
   if (win) {  // add_div = J, add_mod = T in this mode
     const long long wt = row / add_div;
     const int j = (int)(row % add_div), t = (int)(wt % add_mod);
-    const long long w = wt / add_mod;
-    const int s0 = win[2 * w], e0 = win[2 * w + 1];
-    const int fr = min(max(s0 == e0 ? s0 : s0 + t, 0), nframes - 1);
-    src = (long long)fr * add_div + j;
+    src = (long long)window_frame(win, wt / add_mod, t, nframes) * add_div + j;
   }
   float v[NV];
 #pragma unroll
@@ -561,6 +561,13 @@ __global__ __launch_bounds__(256) void lifter_head_kernel(const float* __restric
 // ------------------------------------------------------------------------------------------------------
 // C-ABI launchers
 // ------------------------------------------------------------------------------------------------------
+// the row kernels exist for C = 256 and C = 512 (the caller has checked C), four wavefronts per workgroup
+#define PMCE_LAUNCH_C(kernel, C_, grid, stream, ...)                                          \
+  do {                                                                                        \
+    if ((C_) == 256) hipLaunchKernelGGL((kernel<256>), dim3(grid), dim3(256), 0, stream, __VA_ARGS__); \
+    else hipLaunchKernelGGL((kernel<512>), dim3(grid), dim3(256), 0, stream, __VA_ARGS__);    \
+  } while (0)
+
 extern "C" int pmce_embed_tokens_f32(const float* pose2d, const float* E, const float* Wje, const float* bje,
                                      const float* spos, float* x, long long ntok, int J, int C, hipStream_t stream) {
   PMCE_REQUIRE(C % 4 == 0 && J > 0 && ntok > 0, "embed_tokens: bad shape");
@@ -583,10 +590,7 @@ extern "C" int pmce_embed_ln_f32(const float* pose2d, const float* E, const floa
   long long wpf = (8192 + nframes - 1) / nframes;
   wpf = wpf < 1 ? 1 : (wpf > J ? J : wpf);
   const unsigned grid = (unsigned)((nframes * wpf + 3) / 4);
-  if (C == 256)
-    hipLaunchKernelGGL((embed_ln_kernel<256>), dim3(grid), dim3(256), 0, stream, pose2d, E, Wje, bje, spos, x, nframes, J, w2, b2, eps2, xn, xn_split, (int)wpf);
-  else
-    hipLaunchKernelGGL((embed_ln_kernel<512>), dim3(grid), dim3(256), 0, stream, pose2d, E, Wje, bje, spos, x, nframes, J, w2, b2, eps2, xn, xn_split, (int)wpf);
+  PMCE_LAUNCH_C(embed_ln_kernel, C, grid, stream, pose2d, E, Wje, bje, spos, x, nframes, J, w2, b2, eps2, xn, xn_split, (int)wpf);
   return pmce_check_launch("embed_ln");
 }
 
@@ -599,12 +603,7 @@ extern "C" int pmce_ln_chain_f32(const float* x, long long rows, int C, const fl
   if (add_div <= 0) add_div = 1;
   if (add_mod <= 0) add_mod = 1;
   const unsigned grid = (unsigned)((rows + 3) / 4);
-  if (C == 256)
-    hipLaunchKernelGGL((ln_chain_kernel<256>), dim3(grid), dim3(256), 0, stream, x, rows, w1, b1, eps1, add, add_div, add_mod,
-                       out1, w2, b2, eps2, out2, nullptr, 0, out2_split);
-  else
-    hipLaunchKernelGGL((ln_chain_kernel<512>), dim3(grid), dim3(256), 0, stream, x, rows, w1, b1, eps1, add, add_div, add_mod,
-                       out1, w2, b2, eps2, out2, nullptr, 0, out2_split);
+  PMCE_LAUNCH_C(ln_chain_kernel, C, grid, stream, x, rows, w1, b1, eps1, add, add_div, add_mod, out1, w2, b2, eps2, out2, nullptr, 0, out2_split);
   return pmce_check_launch("ln_chain");
 }
 
@@ -617,12 +616,7 @@ extern "C" int pmce_window_tokens_f32(const float* x0, const int* win, const flo
   PMCE_REQUIRE(x0 && win && tpos && w2 && b2 && X && XN && W > 0 && L > 0 && T > 0 && J > 0, "window_tokens: bad args");
   const long long rows = (long long)W * T * J;
   const unsigned grid = (unsigned)((rows + 3) / 4);
-  if (C == 256)
-    hipLaunchKernelGGL((ln_chain_kernel<256>), dim3(grid), dim3(256), 0, stream, x0, rows, nullptr, nullptr, 0.f, tpos, J, T, X,
-                       w2, b2, eps2, XN, win, L, xn_split);
-  else
-    hipLaunchKernelGGL((ln_chain_kernel<512>), dim3(grid), dim3(256), 0, stream, x0, rows, nullptr, nullptr, 0.f, tpos, J, T, X,
-                       w2, b2, eps2, XN, win, L, xn_split);
+  PMCE_LAUNCH_C(ln_chain_kernel, C, grid, stream, x0, rows, nullptr, nullptr, 0.f, tpos, J, T, X, w2, b2, eps2, XN, win, L, xn_split);
   return pmce_check_launch("window_tokens");
 }
 
@@ -643,9 +637,7 @@ __global__ __launch_bounds__(256) void window_mid_tokens_kernel(const float* __r
   if (r >= (long long)W * J) return;
   const long long w = r / J;
   const int j = (int)(r % J);
-  const int s0 = win[2 * w], e0 = win[2 * w + 1];
-  const int fr = min(max(s0 == e0 ? s0 : s0 + t_mid, 0), nframes - 1);
-  const long long src = (long long)fr * J + j, row = (w * T + t_mid) * J + j;
+  const long long src = (long long)window_frame(win, w, t_mid, nframes) * J + j, row = (w * T + t_mid) * J + j;
   float v[NV];
 #pragma unroll
   for (int i4 = 0; i4 < NV / 4; ++i4) {
@@ -686,12 +678,7 @@ extern "C" int pmce_window_mid_tokens_f32(const float* x0_mid, const int* win, c
                "window_mid_tokens: bad args");
   const long long rows = (long long)W * J;
   const unsigned grid = (unsigned)((rows + 3) / 4);
-  if (C == 256)
-    hipLaunchKernelGGL((window_mid_tokens_kernel<256>), dim3(grid), dim3(256), 0, stream, x0_mid, win, tpos, w2, b2, eps2, X, XN, W, L,
-                       T, J, t_mid, xn_split);
-  else
-    hipLaunchKernelGGL((window_mid_tokens_kernel<512>), dim3(grid), dim3(256), 0, stream, x0_mid, win, tpos, w2, b2, eps2, X, XN, W, L,
-                       T, J, t_mid, xn_split);
+  PMCE_LAUNCH_C(window_mid_tokens_kernel, C, grid, stream, x0_mid, win, tpos, w2, b2, eps2, X, XN, W, L, T, J, t_mid, xn_split);
   return pmce_check_launch("window_mid_tokens");
 }
 
@@ -701,7 +688,7 @@ __global__ __launch_bounds__(256) void window_rows_kernel(const float* __restric
   const int tw = blockIdx.x;  // t * W + w
   const int t = tw / W, w = tw % W;
   const int s0 = win[2 * w], e0 = win[2 * w + 1];
-  const int fr = min(max(s0 == e0 ? s0 : s0 + t, 0), L - 1);
+  const int fr = min(max(s0 == e0 ? s0 : s0 + t, 0), L - 1);  // (window_frame, written out: through the function hipcc orders this kernel's scalar code differently)
   const f32x4* s = reinterpret_cast<const f32x4*>(src + (long long)fr * ncols);
   f32x4* d = reinterpret_cast<f32x4*>(dst + (long long)tw * ncols);
   for (int i = threadIdx.x; i < ncols / 4; i += 256) d[i] = s[i];
@@ -770,10 +757,6 @@ extern "C" int pmce_lifter_head_f32(const float* x, const float* prew, const flo
   PMCE_REQUIRE((prew == nullptr) == (preb == nullptr), "lifter_head: the pre-norm needs weight and bias");
   PMCE_REQUIRE(T > 0 && T <= 64, "lifter_head: 1..64 frames per clip");
   const unsigned grid = (unsigned)(B * J);
-  const unsigned threads = 256u;
-  if (C == 256)
-    hipLaunchKernelGGL((lifter_head_kernel<256>), dim3(grid), dim3(threads), 0, stream, x, lnw, lnb, Wr, br, wf, bf, pose3d, B, T, J, prew, preb, pre_eps);
-  else
-    hipLaunchKernelGGL((lifter_head_kernel<512>), dim3(grid), dim3(threads), 0, stream, x, lnw, lnb, Wr, br, wf, bf, pose3d, B, T, J, prew, preb, pre_eps);
+  PMCE_LAUNCH_C(lifter_head_kernel, C, grid, stream, x, lnw, lnb, Wr, br, wf, bf, pose3d, B, T, J, prew, preb, pre_eps);
   return pmce_check_launch("lifter_head");
 }

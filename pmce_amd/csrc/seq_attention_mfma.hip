@@ -42,11 +42,7 @@
 
 namespace {
 
-// lo plane of x given hi = rne16(x): rne16((x - hi) * 2^11), written as ONE fused multiply-add on the f16 itself (v_fma_mix_f32: no separate
-// f16 -> f32 conversion, no separate subtraction).  x - hi is exact in fp32 (hi is x rounded to 11 bits), so is every product by 2^11, so
-// the fused form has the same bits as the three-instruction form - the kernel is bound by vector issue (980 vector instructions per head and
-// unit against 24 matrix instructions, 66 % of its time by the PMC counts), and the splits are a third of them.
-__device__ __forceinline__ _Float16 lo_plane(float x, _Float16 hi) { return (_Float16)fmaf((float)hi, -2048.0f, x * 2048.0f); }
+// split8 (common.hpp) in the fused form
 __device__ __forceinline__ void split8_fused(const f32x4& x0, const f32x4& x1, f16x8& hi, f16x8& lo) {
   const float v[8] = {x0.x, x0.y, x0.z, x0.w, x1.x, x1.y, x1.z, x1.w};
 #pragma unroll
@@ -102,7 +98,7 @@ __global__ __launch_bounds__(256, 2) void seq_attention_mfma_kernel(const float*
     for (int j = 0; j < DPW; ++j) {
       const int i = min(wave + 4 * j, 2 * N - 1);  // (a repeated instruction rewrites the same row with the same bytes)
       const int a = i / N, r = i - a * N;
-      sdma16(rsrc, (unsigned)lane * 16u, (int)((unsigned)r * tok_bytes + (unsigned)((a + 1) * C * 4 + g * 1024)), slot_base + (unsigned)(i * RS));
+      lds_dma16(rsrc, (unsigned)lane * 16u, (int)((unsigned)r * tok_bytes + (unsigned)((a + 1) * C * 4 + g * 1024)), slot_base + (unsigned)(i * RS));
     }
   };
   // this lane's part of Q of unit k: row rowc, per head and k-step the 8 channels 16 ks + 8 hb + [0, 8)
