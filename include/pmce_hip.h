@@ -473,6 +473,38 @@ int pmce_demo_targets_f32(const float* kp, int kp_stride, const int* win, float*
 /* pose_windows[W,T,J,2] (pmce_assemble_windows_f32's out_pose): row t_mid of every window replaced by mid_pose2d[W,J,2]. */
 int pmce_demo_override_mid_f32(float* pose_windows, const float* mid_pose2d, int W, int T, int J, int t_mid, pmce_stream_t stream);
 
+/* ---------------------------------------------------------------------------------------------------------
+ * The demo's mesh overlays (demo/renderer.py, main/run_demo.py:402-415): a batched triangle rasteriser with a z-buffer, smooth shading and
+ * the demo's compositing rule.  A job is one person in one frame: verts[N][V][3] (fp32, metres, the model's frame), cams[N][4] =
+ * (sx, sy, tx, ty) (pmce_camfit_*'s orig_cam), rotation[N][9] (row-major 3 x 3, applied to the reference's flipped mesh) or NULL.
+ *     u = (sx (x + tx) + 1) width / 2,  v = (sy (y + ty) + 1) height / 2  (origin top-left, y down),  depth = z, smaller is nearer.
+ * u, v are snapped to int32 with 8 sub-pixel bits; coverage is exact integer arithmetic on them: samples at pixel centres, top-left fill
+ * rule.  A triangle with a vertex beyond +-2^14 px is dropped.  Fragments with z outside [-1, 1] are discarded; the nearest survivor
+ * wins, equal z goes to the lowest face index; the result is the same bits every run.  Covered pixels of images[F][height][width][3]
+ * (uint8, updated in place) take clamp(emissive + (ambient + intensity / pi * sum_l max(0, n . l)) * base) per channel, 8-bit value
+ * floor(255 c + 0.5), n the interpolated, normalised vertex normal (area-weighted); every other pixel keeps its bits.
+ *   faces[n_faces][3] int32 (device); vf_offsets[V + 1], vf_faces[3 n_faces]: the vertex -> incident faces CSR (device; the order of a
+ *     vertex' list is the order its normal is summed in);
+ *   job_frame[N]: the frame of each job.  The persons of a frame are drawn as LAYERS: sched[N] lists the jobs layer by layer
+ *     (layer_offsets[n_layers + 1], first 0, last N), ascending distinct frames inside a layer.  depth_order = 0: a job paints over what
+ *     the earlier layers left in its frame (the reference's order); 1: depth test across the jobs of a frame (layers * faces < 2^31).
+ *     job_frame and sched are given twice, on the host (validated here) and on the device; layer_offsets on the host only;
+ *   material (host) = (base[3], emissive, ambient, intensity); lights (host) [n_lights <= 8][3]: unit vectors towards the light, model frame;
+ *   status[N] (device, out): bit 0 = a non-finite vertex, camera or rotation (the job draws nothing), bit 1 = a triangle dropped at the
+ *     guard band;  optional outputs (NULL = not wanted): xy_fixed[N][V][2] int32 the snapped coordinates, face_id[F][height][width]
+ *     int32 and depth[F][height][width] fp32, written where a pixel is drawn (the caller fills them beforehand);
+ *   workspace: 16-byte aligned device memory of at least pmce_render_workspace_bytes(N, V, width, height, 1) bytes; the frames are
+ *     processed in chunks of as many frames as fit (chunk_frames of the query = frames per chunk), with the same result whatever the chunk.
+ *     Its content on entry does not matter.  width, height <= 8192.  A frame is read and written only inside the rectangles of its jobs.
+ * The query returns 0 (and sets the error string) for arguments out of range. */
+size_t pmce_render_workspace_bytes(int n_jobs, int n_verts, int width, int height, int chunk_frames);
+int pmce_render_meshes(unsigned char* images, int n_frames, int width, int height, const float* verts, const float* cams,
+                       const float* rotation, int n_jobs, int n_verts, const int* faces, int n_faces, const int* vf_offsets,
+                       const int* vf_faces, const int* job_frame_host, const int* job_frame, const int* sched_host, const int* sched,
+                       const int* layer_offsets_host, int n_layers, const float* material, const float* lights, int n_lights,
+                       int cull_backfaces, int depth_order, int* status, int* xy_fixed, int* face_id, float* depth, void* workspace,
+                       size_t workspace_bytes, pmce_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -109,6 +109,10 @@ PROTOTYPES = {
     "pmce_camfit_f64": [_f, _f, _f, C.POINTER(C.c_int), _f, _f, _f, _f, _f, _f, _i, _i, _i, _i, _i, _d, _d, _d, _d, _s],
     "pmce_demo_targets_f32": [_f, _i, _f, _f, _f, _f, _f, _i, _i, _i, _i, _fl, _fl, _fl, _fl, _i, _i, _i, _i, _s],
     "pmce_demo_override_mid_f32": [_f, _f, _i, _i, _i, _i, _s],
+    "pmce_render_workspace_bytes": [_i, _i, _i, _i, _i],
+    "pmce_render_meshes": [_f, _i, _i, _i, _f, _f, _f, _i, _i, _f, _i, _f, _f, C.POINTER(C.c_int), _f, C.POINTER(C.c_int), _f,
+                           C.POINTER(C.c_int), _i, C.POINTER(C.c_float), C.POINTER(C.c_float), _i, _i, _i, _f, _f, _f, _f, C.c_void_p,
+                           C.c_size_t, _s],
 }
 _RESTYPES = {
     "pmce_last_error_string": C.c_char_p,
@@ -119,6 +123,7 @@ _RESTYPES = {
     "pmce_model_split_bytes": C.c_size_t,
     "pmce_model_workspace_offset": C.c_longlong,
     "pmce_vertex_sab_scratch_floats": C.c_longlong,
+    "pmce_render_workspace_bytes": C.c_size_t,
 }
 
 _lib = None

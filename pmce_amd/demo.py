@@ -4,6 +4,7 @@ in, what the demo saves per person out - ``pred_cam``, ``mesh``, ``bboxes`` (``f
     model.set_j_regressor(assets.load_j_regressor("coco"))
     out = demo.run_tracklet(model, keypoints[N,17,>=2], features[N,2048], img_wh=(1920, 1080))
     outs = demo.run_tracklets(model, [(kp_a, feat_a), (kp_b, feat_b)], img_wh=(1920, 1080))     # batches filled across people
+    video = demo.render_tracklets(outs, frames_u8, (1920, 1080), frame_ids=ids, renderer=render.Renderer(faces, (1920, 1080)))
 
 Per frame k the demo builds one window (``streaming.demo_window_list``), prepares the fit target from the window's middle frame
 (csrc/demo_prep.hip: add_pelvis_and_neck, get_bbox, process_bbox, j2d_processing), runs the model on the window and fits the
@@ -223,3 +224,45 @@ def frame_results(results: dict, frame_ids, num_frames: int):
         order = np.argsort([fd[k]["bbox"][1] for k in keys]) if keys else []
         out.append(OrderedDict((keys[i], fd[keys[i]]) for i in order))
     return out
+
+
+def tracklet_draw_order(bbox_tops, frame_ids):
+    """The order ``frame_results`` draws in, as job tables: bbox_tops[i] = bbox[:, 1] and frame_ids[i] of tracklet i (host arrays) ->
+    (frame_index int32[N], draw_order int64[N]) over the concatenated rows: inside a frame ``bbox[1]`` ascending, ties in tracklet order."""
+    fi = np.concatenate([np.asarray(f, dtype=np.int64) for f in frame_ids]) if len(frame_ids) else np.zeros(0, np.int64)
+    top = np.concatenate([np.asarray(t, dtype=np.float64) for t in bbox_tops]) if len(bbox_tops) else np.zeros(0)
+    if fi.shape != top.shape:
+        raise ValueError(f"{fi.size} frame ids for {top.size} rows")
+    by_top = np.argsort(top, kind="stable")
+    return fi.astype(np.int32), by_top[np.argsort(fi[by_top], kind="stable")]
+
+
+@torch.no_grad()
+def render_tracklets(results, frames, img_wh, frame_ids=None, renderer=None, order: str = "reference", inplace: bool = False):
+    """The demo's overlay video (main/run_demo.py:375-446) from ``run_tracklets``' outputs: results = list (or dict by person id) of dicts
+    with 'mesh' [N_i,V,3], 'orig_cam' [N_i,4], 'bboxes' [N_i,4]; frames uint8 [F,H,W,3]; frame_ids = per tracklet the frame of each row
+    (same container as results; None: the entry's own 'frame_ids', or rows 0..N_i-1).  renderer: a ``render.Renderer`` for ``img_wh``, or
+    a face array to make one from.  The persons of a frame are drawn in ``frame_results``' order (``bbox[1]`` ascending, ties in tracklet
+    order), each over the previous one (order "reference") or depth-tested against them ("depth").  Meshes, cameras and frames stay on
+    the device; the boxes' top edges (one number per row) are read back once to build the schedule.  -> the overlaid frames."""
+    from . import render as R
+    if renderer is None:
+        raise _lib.PmceError("render_tracklets needs renderer=: a render.Renderer, or the mesh's face array (SMPL's faces are not shipped)")
+    if not isinstance(renderer, R.Renderer):
+        renderer = R.Renderer(renderer, img_wh)
+    if (renderer.width, renderer.height) != (int(img_wh[0]), int(img_wh[1])):
+        raise _lib.PmceError(f"the renderer was made for {renderer.width} x {renderer.height}, img_wh is {tuple(img_wh)}")
+    keys = list(results.keys()) if isinstance(results, dict) else list(range(len(results)))
+    if not keys:
+        return frames if inplace else (frames.clone() if isinstance(frames, torch.Tensor) else np.array(frames))
+    ids = []
+    for k in keys:
+        d = results[k]
+        fid = frame_ids[k] if frame_ids is not None else d.get("frame_ids", np.arange(len(d["mesh"])))
+        if len(fid) != len(d["mesh"]):
+            raise ValueError(f"tracklet {k!r}: {len(fid)} frame ids for {len(d['mesh'])} rows")
+        ids.append(R._host(fid))
+    cat = lambda name: torch.cat([torch.as_tensor(results[k][name]) for k in keys])  # noqa: E731
+    tops = cat("bboxes")[:, 1].cpu().numpy()
+    frame_index, draw = tracklet_draw_order([tops], ids)
+    return renderer.render(frames, cat("mesh"), cat("orig_cam"), frame_index=frame_index, order=order, inplace=inplace, draw_order=draw)

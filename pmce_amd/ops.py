@@ -437,3 +437,32 @@ def j_regress(cam_mesh_m, j_regressor, scale=1000.0):
     _lib.check(lib.pmce_j_regress_f32(P(mesh), P(ip), P(ix), P(dt), P(out), B, jr.shape[0], mesh.shape[1], scale, _st()),
                "j_regress")
     return out
+
+
+def render_workspace_bytes(n_jobs, n_verts, width, height, chunk_frames=1):
+    """Bytes of workspace pmce_render_meshes needs to process ``chunk_frames`` frames per chunk (1 = the least it accepts)."""
+    b = int(_lib.load().pmce_render_workspace_bytes(int(n_jobs), int(n_verts), int(width), int(height), int(chunk_frames)))
+    if b == 0:
+        raise _lib.PmceError(f"render_workspace_bytes: {_lib.last_error()}")
+    return b
+
+
+def render_meshes(images, verts, cams, rotation, faces, vf_offsets, vf_faces, job_frame_host, job_frame, sched_host, sched,
+                  layer_offsets_host, material, lights, cull_backfaces, depth_order, status, xy_fixed, face_id, depth, workspace):
+    """pmce_render_meshes on the current stream, in place on images uint8 [F,H,W,3] (pmce_amd.render.Renderer prepares the tables: faces,
+    the vertex -> face CSR and the job tables on the device, the schedule int32 numpy arrays on the host, material float32[6] and
+    lights float32[K,3] on the host).  rotation, xy_fixed, face_id and depth may be None."""
+    lib = _lib.load()
+    F, H, W, _ = images.shape
+    N, V, _ = verts.shape
+    ip = lambda a: a.ctypes.data_as(C.POINTER(C.c_int))      # noqa: E731
+    fp = lambda a: a.ctypes.data_as(C.POINTER(C.c_float))    # noqa: E731
+    for a in (job_frame_host, sched_host, layer_offsets_host):
+        assert a.dtype == np.int32 and a.flags.c_contiguous
+    assert material.dtype == np.float32 and lights.dtype == np.float32 and images.dtype == torch.uint8
+    _lib.check(lib.pmce_render_meshes(P(images), F, W, H, P(verts), P(cams), P(rotation), N, V, P(faces), faces.shape[0], P(vf_offsets),
+                                      P(vf_faces), ip(job_frame_host), P(job_frame), ip(sched_host), P(sched), ip(layer_offsets_host),
+                                      len(layer_offsets_host) - 1, fp(material), fp(lights), len(lights), 1 if cull_backfaces else 0,
+                                      1 if depth_order else 0, P(status), P(xy_fixed), P(face_id), P(depth),
+                                      C.c_void_p(workspace.data_ptr()), workspace.numel(), _st()), "render_meshes")
+    return images
