@@ -188,6 +188,12 @@ int pmce_window_rows_f32(const float* src, const int* win, float* dst, int W, in
 int pmce_model_set_concurrency(pmce_model* m, int enable);
 int pmce_model_get_concurrency(const pmce_model* m);
 int pmce_model_get_split_overlap(const pmce_model* m);
+/* Temporal lifter blocks at C = 512 in split-f16 mode: qkv product + attention as one kernel (pmce_qkv_attention_fused_split_f16) instead of two
+ * launches with the fp32 [M,3C] tensor between them.  Bit-identical results either way.  mode 0 = never (A/B), 1 (default) = on grids where it is
+ * faster (large batches; small ones keep the two launches), 2 = always.  No environment variable; pipeline lanes inherit the owner's setting
+ * (pmce_model_share_split_weights). */
+int pmce_model_set_qkv_attention_fused(pmce_model* m, int mode);
+int pmce_model_get_qkv_attention_fused(const pmce_model* m);
 
 /* Staggering of several forwards in flight (one handle per lane, shared weights): makes `stream` wait until the pose
  * lifter of the last pmce_forward enqueued on `m` has finished, so that the next batch's lifter (long matrix-bound GEMMs)
@@ -289,6 +295,13 @@ int pmce_seq_attention_f32(const float* qkv, float* out, int nseq, int N, int C,
 int pmce_seq_attention_split_supported(int N, int C);
 int pmce_seq_attention_split_f16(const float* qkv, float* out_planes, int nseq, int N, int C, int seq_div, long long seq_lo,
                                  long long seq_hi, long long tok_stride, pmce_stream_t stream);
+/* Temporal block, C = 512, split-f16 form: AO = attention(XN Wqkv^T + b) in ONE kernel - what pmce_gemm_nt_split_f16 (a_packed, blocked weight)
+ * into fp32 qkv[M][3C] followed by pmce_seq_attention_split_f16(nseq = B*J, N = 16, seq_div = J, seq_lo = 1, seq_hi = 16*J, tok_stride = J) compute,
+ * bit for bit, without the qkv tensor.  xn_planes / out_planes: pre-split rows [B*16*J][C/16][16 hi | 16 lo*2^11] f16; Wp / wscale: the [3C][C]
+ * weight from pmce_gemm_pack_split_f16(blocked = 1); bias [3C] or NULL.  Sequences are the 16 frames of (clip, joint).  C must be 512.  A
+ * non-finite result sets overflow_word (device-visible) to 1; NULL = the calling thread's overflow sink, as the products and the attention use. */
+int pmce_qkv_attention_fused_split_f16(const float* xn_planes, const float* Wp, const float* wscale, const float* bias, float* out_planes, int B,
+                                       int J, int C, unsigned* overflow_word, pmce_stream_t stream);
 /* PoseEstimation.py:62-66,109-113 — LayerNorm(1e-5) + Linear(C->3) + Conv2d(T->1) frame fusion.
  * prew != NULL: x is the LAST TemporalBlock's output BEFORE its post-norm, and every row passes through LayerNorm(prew, preb, pre_eps) (norm_t,
  * PoseEstimation.py:92) on the way in - bit-identical to pmce_ln_chain_f32(out1) followed by the head on its result, without the launch and the

@@ -58,6 +58,8 @@ PROTOTYPES = {
     "pmce_model_get_split_min_batch": [C.c_void_p],
     "pmce_model_get_concurrency": [C.c_void_p],
     "pmce_model_get_split_overlap": [C.c_void_p],
+    "pmce_model_set_qkv_attention_fused": [C.c_void_p, _i],
+    "pmce_model_get_qkv_attention_fused": [C.c_void_p],
     "pmce_model_set_clock_probe": [C.c_void_p, C.c_void_p],
     "pmce_model_overflowed": [C.c_void_p],
     "pmce_model_clear_overflow": [C.c_void_p],
@@ -73,6 +75,7 @@ PROTOTYPES = {
     "pmce_seq_attention_f32": [_f, _f, _i, _i, _i, _i, _l, _l, _l, _i, _s],
     "pmce_seq_attention_split_supported": [_i, _i],
     "pmce_seq_attention_split_f16": [_f, _f, _i, _i, _i, _i, _l, _l, _l, _s],
+    "pmce_qkv_attention_fused_split_f16": [_f, _f, _f, _f, _f, _i, _i, _i, _f, _s],
     "pmce_gemm_split_set_tuning": [_i],
     "pmce_embed_tokens_f32": [_f, _f, _f, _f, _f, _f, _l, _i, _i, _s],
     "pmce_embed_ln_f32": [_f, _f, _f, _f, _f, _f, _l, _i, _i, _f, _f, _fl, _f, _i, _s],

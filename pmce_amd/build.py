@@ -23,11 +23,11 @@ _PACKED_AB = {f for f in os.environ.get("PMCE_PACKED_FP32_FILES", "").split(",")
 FILE_FLAGS = {src: ([] if src in _PACKED_AB else NO_PACKED_FP32) for src in SOURCES if src.endswith(".hip")}
 
 # The diagnostics library (NOT the product): the bystander kernels of the matrix-pipe interference report, which ARE packed-fp32 code on
-# purpose, and the f16-subnormal probe.  (The two experimental split-GEMM variants it carried until round 4 - wave-specialised 192x256,
+# purpose, the f16-subnormal probe and the operand-exchange probe of the matrix instruction (mfma_exchange.hip).  (The two experimental split-GEMM variants it carried until round 4 - wave-specialised 192x256,
 # 16x16x32 - are in the history: measured, not faster, profiles/r03_a_gemm_ws_*, r02_k_*.)
 DIAG_DIR = osp.join(HERE, "..", "scripts", "microbench")
 DIAG_LIB = osp.join(DIAG_DIR, "libpmce_diag.so")
-DIAG_SOURCES = ["dbg_victims.hip"]
+DIAG_SOURCES = ["dbg_victims.hip", "mfma_exchange.hip"]
 DIAG_FILE_FLAGS = {src: NO_PACKED_FP32 for src in DIAG_SOURCES if src != "dbg_victims.hip"}
 
 

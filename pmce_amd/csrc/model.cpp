@@ -19,6 +19,10 @@
 #include "common.hpp"
 #include "../../include/pmce_hip.h"
 
+#ifndef PMCE_QKV_ATTN_FUSED_DEFAULT
+#define PMCE_QKV_ATTN_FUSED_DEFAULT 1
+#endif
+
 namespace {
 
 constexpr int T = 16, F = 2048, NVC = 431, NVF = 6890, D = 64, GH = 1024;
@@ -120,6 +124,10 @@ struct pmce_model {
   // 3.4); the library therefore contains no packed-fp32 instruction at all (build.py), which makes its kernels safe next to each
   // other.  PMCE_SPLIT_OVERLAP=0 at create restores the strictly serial schedule of the split mode (diagnostic).
   bool split_overlap = true;
+  // Temporal blocks at C = 512 in split mode: the qkv product and the attention as ONE kernel (qkv_attention_fused.hip; the same bits as the two
+  // launches).  0 = never (the A/B switch), 1 = where it is faster - grids of at least kQkvFusedMinUnits work units - 2 = always (tests).
+  // (A/B builds of one source: -DPMCE_QKV_ATTN_FUSED_DEFAULT=0 through PMCE_EXTRA_HIPCC_FLAGS makes a library whose default is the two launches.)
+  int qkv_attn_fused = PMCE_QKV_ATTN_FUSED_DEFAULT;  // pmce_model_set_qkv_attention_fused
   bool split_now = false;  // decision for the call in progress (set by check_ws, the first thing every entry point does)
   // Sticky "a product of this model produced a non-finite value" word: 4 bytes of pinned host memory the device can write
   // (hipHostMalloc, mapped), so that reading it costs no synchronisation.  Set by the split-f16 products' epilogues (an activation
@@ -327,7 +335,7 @@ void carve_lifter(Carver& c, const pmce_model* m, int B, LifterWs& w) {
   w.E = c.take((size_t)B * T * C);
   w.X = c.take(M * C);
   w.XN = c.take(M * C);
-  w.QKV = c.take(M * 3 * C);  // also the MLP hidden [M,2C]
+  w.QKV = c.take(M * 3 * C);  // fp32 q, k, v of the two-launch attention (the fused temporal form does not write them); also the MLP hidden [M,2C]
   w.AO = c.take(M * C);
   w.FS = c.take((size_t)B * T * F);
   w.FR = c.take((size_t)B * T);
@@ -411,6 +419,17 @@ PostNorm post_norm_of(const pmce_model* m, int kind, int i) {
 // (pmce_gemm_nt_split_f16_ln) instead of a launch of its own that re-reads the row.  (C = 512: a 512-wide tile does not fit)
 inline bool ln_in_product(const pmce_model* m) { return m->split_now && m->C == 256; }
 
+// The fused qkv + attention kernel walks units of 8 sequences x 1 head on up to 512 persistent workgroups, each unit a serial chain of 32 k-tiles
+// and an attention phase that only the CU's other workgroup hides; the product alone picks smaller tiles and shorter chains on small grids.
+// Measured at operator level (profiles/qaf_op_level_by_batch.txt, two launches / fused, us): 136 units (B = 8) 25 / 45, 272 (B = 16) 41 / 48,
+// 408 (B = 24) 55 / 53, 544 (B = 32) 63 / 56, 1088 (B = 64) 121 / 92, 4352 (B = 256) 434 / 325.  The fused form is taken from a full grid on -
+// one unit per workgroup, B >= 31 at J = 17; smaller batches keep the two launches (B = 1 latency is untouched).
+constexpr int kQkvFusedMinUnits = 512;
+inline bool qkv_attn_fused_now(const pmce_model* m, int kind, int B) {
+  if (!(m->split_now && kind == 1 && m->C == 512 && T == 16 && m->qkv_attn_fused != 0)) return false;
+  return m->qkv_attn_fused == 2 || ((long long)B * m->J + 7) / 8 * 8 >= kQkvFusedMinUnits;
+}
+
 // attention + MLP of one block (pre-norm input in w.XN, residual stream in w.X); kind 0 spatial, 1 temporal.  post != nullptr: the
 // block's post-norm chain (without a position embedding) is part of this call - fused into fc2 where ln_in_product, a launch otherwise.
 int lifter_block_body(pmce_model* m, int kind, int i, long long M, int nframes, int B, LifterWs& w, hipStream_t stream,
@@ -421,14 +440,19 @@ int lifter_block_body(pmce_model* m, int kind, int i, long long M, int nframes, 
   // split mode: the attention runs on the f16 matrix pipe too (seq_attention_mfma.hip; reads the fp32 q, k, v, writes AO pre-split)
   const int N_seq = kind == 0 ? J : T;
   const bool mfma_attn = m->split_now && pmce_seq_attention_split_supported(N_seq, C);
-  RUN(P_GEMM_LIFTER, stream, lgemm(m, w.XN, bw.qkv_w, sw.qkv, bw.qkv_b, nullptr, w.QKV,
-                                   (int)M, 3 * C, C, C, 3 * C, 0, stream, pk(m)));
-  if (kind == 0) {  // sequences = frames, tokens j contiguous                      (PoseEstimation.py:78,101)
-    if (mfma_attn) RUN(P_SEQ_ATTN, stream, pmce_seq_attention_split_f16(w.QKV, w.AO, nframes, J, C, 0, J, 0, 1, stream));
-    else RUN(P_SEQ_ATTN, stream, pmce_seq_attention_f32(w.QKV, w.AO, nframes, J, C, 0, J, 0, 1, pk(m), stream));
-  } else {  // sequences = (b,j), tokens t at stride J                              (PoseEstimation.py:87,104)
-    if (mfma_attn) RUN(P_SEQ_ATTN, stream, pmce_seq_attention_split_f16(w.QKV, w.AO, B * J, T, C, J, 1, (long long)T * J, J, stream));
-    else RUN(P_SEQ_ATTN, stream, pmce_seq_attention_f32(w.QKV, w.AO, B * J, T, C, J, 1, (long long)T * J, J, pk(m), stream));
+  const bool fused_attn = sw.qkv.wp && qkv_attn_fused_now(m, kind, B);
+  if (fused_attn) {  // XN -> AO in one launch, timed with the products; w.QKV is not touched
+    RUN(P_GEMM_LIFTER, stream, pmce_qkv_attention_fused_split_f16(w.XN, sw.qkv.wp, sw.qkv.scale, bw.qkv_b, w.AO, B, J, C, nullptr, stream));
+  } else {
+    RUN(P_GEMM_LIFTER, stream, lgemm(m, w.XN, bw.qkv_w, sw.qkv, bw.qkv_b, nullptr, w.QKV,
+                                     (int)M, 3 * C, C, C, 3 * C, 0, stream, pk(m)));
+    if (kind == 0) {  // sequences = frames, tokens j contiguous                      (PoseEstimation.py:78,101)
+      if (mfma_attn) RUN(P_SEQ_ATTN, stream, pmce_seq_attention_split_f16(w.QKV, w.AO, nframes, J, C, 0, J, 0, 1, stream));
+      else RUN(P_SEQ_ATTN, stream, pmce_seq_attention_f32(w.QKV, w.AO, nframes, J, C, 0, J, 0, 1, pk(m), stream));
+    } else {  // sequences = (b,j), tokens t at stride J                              (PoseEstimation.py:87,104)
+      if (mfma_attn) RUN(P_SEQ_ATTN, stream, pmce_seq_attention_split_f16(w.QKV, w.AO, B * J, T, C, J, 1, (long long)T * J, J, stream));
+      else RUN(P_SEQ_ATTN, stream, pmce_seq_attention_f32(w.QKV, w.AO, B * J, T, C, J, 1, (long long)T * J, J, pk(m), stream));
+    }
   }
   const bool fuse = ln_in_product(m) && sw.proj.wp && sw.fc2.wp;
   if (fuse) {  // x += proj(attn); XN = norm2(x)
@@ -1023,6 +1047,7 @@ int pmce_model_share_split_weights(pmce_model* dst, const pmce_model* src) {
   dst->oflow = src->oflow;  // lanes of one model report to one word
   dst->strict_overflow = src->strict_overflow;  // ... and follow its policy and its small-batch threshold
   dst->split_min_batch = src->split_min_batch;
+  dst->qkv_attn_fused = src->qkv_attn_fused;
   return PMCE_OK;
 }
 int pmce_model_overflowed(const pmce_model* m) {
@@ -1051,6 +1076,12 @@ int pmce_model_set_split_min_batch(pmce_model* m, int clips) {
 // the values in force (their defaults come from the environment at create time: a caller that changes one temporarily restores THIS)
 int pmce_model_get_split_min_batch(const pmce_model* m) { return m ? m->split_min_batch : -1; }
 int pmce_model_get_concurrency(const pmce_model* m) { return m ? (m->concurrent ? 1 : 0) : -1; }
+int pmce_model_set_qkv_attention_fused(pmce_model* m, int mode) {
+  PMCE_REQUIRE(m && mode >= 0 && mode <= 2, "pmce_model_set_qkv_attention_fused: mode is 0 (off), 1 (where faster) or 2 (always)");
+  m->qkv_attn_fused = mode;
+  return PMCE_OK;
+}
+int pmce_model_get_qkv_attention_fused(const pmce_model* m) { return m ? m->qkv_attn_fused : -1; }
 int pmce_model_get_split_overlap(const pmce_model* m) { return m ? (m->split_overlap ? 1 : 0) : -1; }
 int pmce_model_get_overflow_policy(const pmce_model* m) { return m ? (m->strict_overflow ? 1 : 0) : -1; }
 

@@ -329,3 +329,7 @@ extern "C" int pmce_seq_attention_split_f16(const float* qkv, float* out, int ns
 #undef PMCE_ATTN_CASE
   return PMCE_OK;
 }
+
+// The temporal blocks' fused form (qkv product + this attention in one kernel) is part of this translation unit: it shares split8_fused
+// and spells the same softmax.
+#include "qkv_attention_fused.hip"

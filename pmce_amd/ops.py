@@ -204,6 +204,17 @@ def seq_attention_split(qkv, nseq, N, Cc, seq_div, seq_lo, seq_hi, tok_stride):
     return out
 
 
+def qkv_attention_fused(xn_planes, Wblk, wscale, bias, B, J, overflow_word=None):
+    """Temporal block at C = 512: pre-split XN [B*16*J, 512] -> pre-split attention output, one kernel (qkv_attention_fused.hip).
+    overflow_word: optional int32 device tensor of one element, set to 1 when a result is not finite."""
+    lib = _lib.load()
+    Cc = xn_planes.shape[1]
+    out = torch.empty_like(xn_planes)
+    _lib.check(lib.pmce_qkv_attention_fused_split_f16(P(xn_planes), P(Wblk), P(wscale), P(bias), P(out), B, J, Cc, P(overflow_word), _st()),
+               "qkv_attention_fused_split_f16")
+    return out
+
+
 def unsplit_rows_f16(Ap):
     """The fp32 values a packed (hi | lo*2^11) f16 buffer stands for (float64, exact): inverse of :func:`split_rows_f16`."""
     M, K = Ap.shape

@@ -185,6 +185,14 @@ class HipEngine:
         finally:
             self.set_split_min_batch(prev)
 
+    def set_qkv_attention_fused(self, mode: int):
+        """Temporal blocks at C = 512, split mode: 0 = qkv product and attention as two launches, 1 (default) = one fused kernel on the grids
+        where it is faster, 2 = always fused.  Same bits either way."""
+        _lib.check(self.lib.pmce_model_set_qkv_attention_fused(self.handle, int(mode)), "model_set_qkv_attention_fused")
+
+    def get_qkv_attention_fused(self) -> int:
+        return int(self.lib.pmce_model_get_qkv_attention_fused(self.handle))
+
     def set_concurrency(self, enable: bool):
         _lib.check(self.lib.pmce_model_set_concurrency(self.handle, 1 if enable else 0), "model_set_concurrency")
 

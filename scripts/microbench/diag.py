@@ -1,5 +1,5 @@
 """ctypes binding of scripts/microbench/libpmce_diag.so - the diagnostics library (pmce_amd.build.build_diag): the bystander / spinner
-kernels of the matrix-pipe interference report and the f16-subnormal probe.  Not part of the product."""
+kernels of the matrix-pipe interference report, the f16-subnormal probe and the operand-exchange probe.  Not part of the product."""
 import ctypes as C
 import os.path as osp
 import sys
@@ -14,6 +14,7 @@ PROTOTYPES = {
     "pmce_dbg_victim": [_i, _f, _i, _i, _f, _s],
     "pmce_dbg_mfma_spin": [_i, _f, _i, _i, _s],
     "pmce_dbg_mfma_subnormal": [_fl, _fl, _f, _s],
+    "pmce_dbg_mfma_exchange": [_f, _f, _f, _f, _f, _i, _s],
     "pmce_last_error_string": [],
 }
 _lib = None
