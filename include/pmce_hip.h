@@ -319,7 +319,10 @@ int pmce_gru_step_f32(const float* gi0, const float* gi1, const float* whh0, con
  * ONE weight packed by pmce_gemm_pack_split_f16 (K = H), wscale its scale pair, w_blocked its `blocked` (1 is what the model runs: the
  * 16 rows a DMA instruction fetches are 1 KB contiguous; whh0p / whh1p = the first row of each direction, a multiple of 64 rows apart).
  * B <= 64 runs a small-batch kernel (a workgroup per 8 hidden units: 256 workgroups whatever the batch), larger batches 64 rows x 32 units
- * per workgroup - same numbers, bit for bit, in both layouts and at every batch size. */
+ * per workgroup - same numbers, bit for bit, in both layouts, and for the same ROW INDEX at every batch size (this holds for pmce_gru_step_f32
+ * too).  The rounding of a row does depend on its place in its 32-row tile: gh is summed in four K-quarters, and the quarter (row >> 3) & 3
+ * adds the sum of the other three to its own.  Rows 32 apart get the same bits; the same clip at rows 0, 8, 16 and 24 gets results that agree
+ * to fp32 rounding (each within 5e-6 of the fp64 step, tests/test_gpu_gru.py), not bit for bit. */
 int pmce_gru_step_split_f32(const float* gi0, const float* gi1, const float* whh0p, const float* whh1p, const float* wscale,
                             const float* bhh0, const float* bhh1, const float* hp0, const float* hp1, float* ho0, float* ho1,
                             long long gi_rs, long long h_rs, int B, int H, int ndir, int w_blocked, pmce_stream_t stream);

@@ -172,13 +172,27 @@ def coevo_block(joint, vertx, g, sd, p, dtype=torch.float32):
     return joint_out, vertx_out
 
 
-def gru_bidir2(x_seq, sd, p, dtype=torch.float32):
+def gru_step(gi, w_hh, b_hh, h_prev=None, dtype=torch.float64):
+    """One nn.GRU time step of one direction (gate order r, z, n): gi[B,3H] = W_ih x + b_ih, w_hh[3H,H], b_hh[3H], h_prev[B,H] or None
+    (h = 0) -> h'[B,H] = (1 - z) * n + z * h with n = tanh(gi_n + r * (W_hn h + b_hn)).  Plain torch ops in ``dtype``."""
+    gi, w_hh, b_hh = gi.to(dtype), w_hh.to(dtype), b_hh.to(dtype)
+    H = w_hh.shape[1]
+    h = torch.zeros(gi.shape[0], H, dtype=dtype) if h_prev is None else h_prev.to(dtype)
+    gh = F.linear(h, w_hh, b_hh)
+    r = torch.sigmoid(gi[:, :H] + gh[:, :H])
+    z = torch.sigmoid(gi[:, H:2 * H] + gh[:, H:2 * H])
+    n = torch.tanh(gi[:, 2 * H:] + r * gh[:, 2 * H:])
+    return (1 - z) * n + z * h
+
+
+def gru_bidir2(x_seq, sd, p, dtype=torch.float32, return_layer0=False):
     """nn.GRU(2048,1024,bidirectional=True,num_layers=2), seq-first, h0 = 0 (CoevoDecoder.py:216-221,228).
     PyTorch gate order (r,z,n); n = tanh(W_in x + b_in + r*(W_hn h + b_hn)); h' = (1-z)*n + z*h.
-    x_seq[T,B,2048] -> y[T,B,2048] (top layer, fwd|bwd)."""
+    x_seq[T,B,2048] -> y[T,B,2048] (top layer, fwd|bwd); return_layer0: -> (y, layer 0's output [T,B,2048]).  The hidden size is the
+    weights' own."""
     Tn, B, _ = x_seq.shape
-    inp = x_seq
-    H = 1024
+    inp = x_seq.to(dtype)
+    layers = []
     for layer in (0, 1):
         outs = []
         for sfx in ("", "_reverse"):
@@ -187,20 +201,16 @@ def gru_bidir2(x_seq, sd, p, dtype=torch.float32):
             b_ih = _g(sd, f"{p}.bias_ih_l{layer}{sfx}", dtype)
             b_hh = _g(sd, f"{p}.bias_hh_l{layer}{sfx}", dtype)
             gi_all = F.linear(inp, w_ih, b_ih)                     # [T,B,3H]
-            h = torch.zeros(B, H, dtype=dtype)
+            h = None
             ys = [None] * Tn
             order = range(Tn) if sfx == "" else range(Tn - 1, -1, -1)
             for t in order:
-                gi = gi_all[t]
-                gh = F.linear(h, w_hh, b_hh)
-                r = torch.sigmoid(gi[:, :H] + gh[:, :H])
-                z = torch.sigmoid(gi[:, H:2 * H] + gh[:, H:2 * H])
-                n = torch.tanh(gi[:, 2 * H:] + r * gh[:, 2 * H:])
-                h = (1 - z) * n + z * h
+                h = gru_step(gi_all[t], w_hh, b_hh, h, dtype)
                 ys[t] = h
             outs.append(torch.stack(ys, 0))
         inp = torch.cat(outs, -1)
-    return inp
+        layers.append(inp)
+    return (layers[1], layers[0]) if return_layer0 else layers[1]
 
 
 def vertex_init_gather(joints, vj_relation):

@@ -374,7 +374,9 @@ __global__ __launch_bounds__(512) void gru_step_v2_kernel(GruStepArgs a) {
 // loop) of 8 / 5 stages of [32 NT h rows | 32 W rows] x 64 B, all but one stage in flight (112 / 96 KB per CU).  The arithmetic per output
 // element is gru_step_v2's, operation for operation - the same k-tiles in the same order per K-quarter, the quarters met in the same order
 // (the quarter that owns accumulator row r = the one v2's wave kq finishes) - so the result is bit-identical to it
-// (test_gru_step_small_batch_equals_v2): a clip's numbers do not depend on the batch it rode in.
+// (test_gru_step_small_batch_equals_v2): a clip's numbers at a given ROW INDEX do not depend on the size of the batch it rode in.  They do depend
+// on the row's place in its 32-row tile: the quarter kq = (row >> 3) & 3 adds the other three's sum to its own, so the same clip at rows 0, 8, 16
+// and 24 differs in the last bits; rows 32 apart agree bit for bit (tests/test_gpu_gru.py::test_place_in_the_batch).
 // ------------------------------------------------------------------------------------------------------
 template <int NT>
 __global__ __launch_bounds__(256) void gru_step_small_kernel(GruStepArgs a) {

@@ -139,6 +139,86 @@ def gru_step_split(gi, whh, bhh, h_prev, blocked=True):
     return out
 
 
+def _row_view(t, cols, what):
+    """(device pointer, row stride in floats) of a 2-D fp32 device view whose last dimension is contiguous (rows may be strided)."""
+    if not (t.is_cuda and t.dtype == torch.float32 and t.dim() == 2 and t.shape[1] == cols and t.stride(1) == 1):
+        raise ValueError(f"gru_step: {what} must be an fp32 device view [B, {cols}] with a contiguous last dimension")
+    if t.data_ptr() % 16 or (t.shape[0] > 1 and t.stride(0) % 4):
+        raise ValueError(f"gru_step: {what} rows must start on 16-byte boundaries (the kernels fetch h in 16-byte pieces)")
+    return C.c_void_p(t.data_ptr()), t.stride(0) if t.shape[0] > 1 else None
+
+
+def gru_step(gi, whh, bhh, h_prev, out, form="split", blocked=True, backward_only=False):
+    """One GRU time step through pmce_gru_step_f32 (form="f32") or pmce_gru_step_split_f32 (form="split"), in every shape model.cpp's
+    gru_layer calls them.  whh / bhh: one [3H, H] / [3H] tensor per direction (a list of one or two).  gi / h_prev / out: one 2-D view per
+    direction that runs ([B, 3H], [B, H], [B, H]; rows may be strided - a column block of a wider buffer -, the last dimension is
+    contiguous); h_prev, or either of its entries, may be None (h = 0).  The row strides come from the views: gi's and h_prev's / out's
+    must agree between the directions (and h_prev's with out's: the C entry takes ONE h_rs).  Writes `out` in place and returns it.
+
+    Two directions, split form: the stacked [6H, H] weight is packed in ONE pmce_gemm_pack_split_f16 call as the model packs it; direction 1
+    is that buffer + 3H * H floats and reads the second half of the one [6H] scale table.
+
+    backward_only (with two directions' weights): gi / h_prev / out are direction 1's alone and the call is ndir = 1 on direction 1's rows of
+    the stacked weight (split form: whh0p = packed + 3H * H floats, wscale + 3H) - gru_layer's backward-only branch."""
+    lib = _lib.load()
+    if form not in ("f32", "split"):
+        raise ValueError("gru_step: form must be 'f32' or 'split'")
+    whh, bhh = [_c(w) for w in whh], [_c(b) for b in bhh]
+    nw = len(whh)
+    if nw not in (1, 2) or len(bhh) != nw:
+        raise ValueError("gru_step: one or two directions")
+    if backward_only and nw != 2:
+        raise ValueError("gru_step: backward_only needs both directions' weights")
+    H = whh[0].shape[1]
+    if any(tuple(w.shape) != (3 * H, H) for w in whh) or any(tuple(b.shape) != (3 * H,) for b in bhh):
+        raise ValueError("gru_step: whh must be [3H, H] and bhh [3H] per direction")
+    ndir = 1 if backward_only else nw
+    as_list = lambda v: list(v) if isinstance(v, (list, tuple)) else [v]      # noqa: E731
+    gi, out = as_list(gi), as_list(out)
+    h_prev = [None] * ndir if h_prev is None else as_list(h_prev)
+    if not (len(gi) == len(out) == len(h_prev) == ndir):
+        raise ValueError(f"gru_step: gi, h_prev and out need one view per running direction ({ndir})")
+    B = gi[0].shape[0]
+    gp, hp, op, gi_rs, h_rs = [], [], [], set(), set()
+    for d in range(ndir):
+        if gi[d].shape[0] != B or out[d].shape[0] != B or (h_prev[d] is not None and h_prev[d].shape[0] != B):
+            raise ValueError("gru_step: every view has B rows")
+        p, s = _row_view(gi[d], 3 * H, "gi")
+        gp.append(p); gi_rs.add(s)
+        p, s = _row_view(out[d], H, "out")
+        op.append(p); h_rs.add(s)
+        if h_prev[d] is None:
+            hp.append(None)
+        else:
+            p, s = _row_view(h_prev[d], H, "h_prev")
+            hp.append(p); h_rs.add(s)
+    gi_rs.discard(None); h_rs.discard(None)           # (a single row has no stride of its own)
+    if len(gi_rs) > 1 or len(h_rs) > 1:
+        raise ValueError(f"gru_step: the directions' row strides differ (gi {sorted(gi_rs)}, h_prev / out {sorted(h_rs)})")
+    gi_rs = gi_rs.pop() if gi_rs else 3 * H
+    h_rs = h_rs.pop() if h_rs else H
+    gp, hp, op = (v + [None] * (2 - ndir) for v in (gp, hp, op))
+    fp = lambda t, off: C.c_void_p(t.data_ptr() + 4 * off)                    # noqa: E731
+    b0, b1 = (bhh[1], None) if backward_only else (bhh[0], bhh[1] if nw == 2 else None)
+    if form == "f32":
+        w0, w1 = (whh[1], None) if backward_only else (whh[0], whh[1] if nw == 2 else None)
+        _lib.check(lib.pmce_gru_step_f32(gp[0], gp[1], P(w0), P(w1), P(b0), P(b1), hp[0], hp[1], op[0], op[1], gi_rs, h_rs, B, H, ndir, _st()),
+                   "gru_step_f32")
+        return out if ndir == 2 else out[0]
+    W = torch.cat(whh, 0) if nw == 2 else whh[0]
+    if blocked:
+        Wp, wscale, _ = pack_split_f16_blk(W)
+    else:
+        Wp, wscale = pack_split_f16(W)
+    if backward_only:
+        w0, w1, sc = fp(Wp, 3 * H * H), None, fp(wscale, 3 * H)
+    else:
+        w0, w1, sc = P(Wp), (fp(Wp, 3 * H * H) if nw == 2 else None), P(wscale)
+    _lib.check(lib.pmce_gru_step_split_f32(gp[0], gp[1], w0, w1, sc, P(b0), P(b1), hp[0], hp[1], op[0], op[1], gi_rs, h_rs, B, H, ndir,
+                                           1 if blocked else 0, _st()), "gru_step_split")
+    return out if ndir == 2 else out[0]
+
+
 def ln_chain(x, w1=None, b1=None, eps1=1e-6, add=None, add_div=1, add_mod=1, want_out1=True, w2=None, b2=None, eps2=1e-6,
              out2_split=False):
     lib = _lib.load()

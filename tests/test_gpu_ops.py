@@ -672,7 +672,8 @@ def test_final_operand_pre_split_is_the_same_split():
 
 def test_gru_step_small_batch_equals_v2():
     """The small-batch GRU step (B <= 32: one batch tile per wave, B <= 64: two) against gru_step_v2 (B > 64) on the same rows: bit-identical -
-    a clip's hidden state does not depend on the batch it rode in - and both against the fp64 step (nn.GRU's formulas)."""
+    a clip's hidden state at a given row index does not depend on the size of the batch it rode in (its rounding does depend on the row's place in
+    its 32-row tile: test_gpu_gru.py::test_place_in_the_batch) - and both against the fp64 step (nn.GRU's formulas)."""
     from pmce_amd import ops
     g = torch.Generator().manual_seed(77)
     H = 1024
