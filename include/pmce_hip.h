@@ -521,6 +521,31 @@ int pmce_render_meshes(unsigned char* images, int n_frames, int width, int heigh
                        int cull_backfaces, int depth_order, int* status, int* xy_fixed, int* face_id, float* depth, void* workspace,
                        size_t workspace_bytes, pmce_stream_t stream);
 
+/* ---------------------------------------------------------------------------------------------------------
+ * Batched SMPL forward (reference smplpytorch SMPL_Layer.forward with center_idx = None, fp32): the ground-truth meshes of the evaluation
+ * from the datasets' SMPL fits.  Two launches on `stream` (pose kernel: one wave per sample; skinning kernel: 256 vertices x 16 samples
+ * per workgroup), no atomics, no synchronisation; a sample's result does not depend on the batch it is in.
+ *   model tables (device, prepared once by pmce_amd.smpl.SMPLModel):
+ *     v_template_t[3][V]; dirs_t[220][3][V] = the 10 shape directions, the 207 pose directions, three zero rows;
+ *     weights_t[24][V]; j_template[24][3] = J_regressor v_template and j_shapedirs[24][3][10] = J_regressor shapedirs (fp64 products
+ *     rounded to fp32); parents_host[24] (host): the kinematic tree, entry i > 0 in [0, i), entry 0 not read; n_joints must be 24;
+ *   pose[B][72] axis-angle, betas[B][10], trans[B][3] or NULL (zeros);
+ *   optional camera form (both or neither), data/Human36M/dataset.py:354-398: cam_R[B][3][3], cam_t[B][3] in mm - the root rotation
+ *     becomes cam_R R_0, betas are zeroed where any |beta| > 3, the translation becomes cam_R trans + cam_t / 1000 - J_0 + cam_R J_0.
+ *     A zero root pose gives cam_R itself (the reference divides 0 by 0 there);
+ *   sample_index[n] (device, int32, distinct entries in [0, B)) or NULL (then n == B): the rows this call computes, read and written
+ *     in place - one call per gender of a mixed batch.  An entry outside [0, B) is ignored;
+ *   verts_out[B][V][3], joints_out[B][24][3] = (x + trans) * scale - offset[b], offset[B][3] or NULL: scale = 1 without offset gives
+ *     the layer's metres, scale = 1000 with the root joint in mm gives data/PW3D/dataset.py:86,240;
+ *   workspace: 16-byte aligned device memory of at least pmce_smpl_workspace_bytes(B) bytes (rows indexed by sample).
+ * The query returns 0 (and sets the error string) for B < 1. */
+size_t pmce_smpl_workspace_bytes(int B);
+int pmce_smpl_forward(const float* v_template_t, const float* dirs_t, const float* weights_t, const float* j_template,
+                      const float* j_shapedirs, const int* parents_host, int n_joints, const float* pose, const float* betas,
+                      const float* trans, const float* cam_R, const float* cam_t, const int* sample_index, int n, float scale,
+                      const float* offset, float* verts_out, float* joints_out, void* workspace, size_t workspace_bytes, int B, int V,
+                      pmce_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -116,6 +116,9 @@ PROTOTYPES = {
     "pmce_render_meshes": [_f, _i, _i, _i, _f, _f, _f, _i, _i, _f, _i, _f, _f, C.POINTER(C.c_int), _f, C.POINTER(C.c_int), _f,
                            C.POINTER(C.c_int), _i, C.POINTER(C.c_float), C.POINTER(C.c_float), _i, _i, _i, _f, _f, _f, _f, C.c_void_p,
                            C.c_size_t, _s],
+    "pmce_smpl_workspace_bytes": [_i],
+    "pmce_smpl_forward": [_f, _f, _f, _f, _f, C.POINTER(C.c_int), _i, _f, _f, _f, _f, _f, _f, _i, _fl, _f, _f, _f, C.c_void_p, C.c_size_t,
+                          _i, _i, _s],
 }
 _RESTYPES = {
     "pmce_last_error_string": C.c_char_p,
@@ -127,6 +130,7 @@ _RESTYPES = {
     "pmce_model_workspace_offset": C.c_longlong,
     "pmce_vertex_sab_scratch_floats": C.c_longlong,
     "pmce_render_workspace_bytes": C.c_size_t,
+    "pmce_smpl_workspace_bytes": C.c_size_t,
 }
 
 _lib = None

@@ -10,10 +10,11 @@ the annotation file is plain COCO-style JSON.
     feats = table.features_on(device)                             # [N, 2048]
     p, f = datasets.window_batch(pose2d, feats, win[a:b])         # model inputs [b-a, 16, 19, 2], [b-a, 16, 2048]
 
-What is NOT here: the SMPL layer that turns ``smpl_param`` into ground-truth meshes (``PW3D.get_smpl_coord``; SMPL model files are
-out of scope) - ground-truth joints come from ``3DPW_<split>_joint_h36m_cam.json`` as the reference's ``reg_pose3d`` target
-(dataset.py:229-230,249), and a ground-truth mesh table can be supplied as ``<data_path>/3DPW_<split>_gt_mesh_cam.npy`` ([N, 6890, 3]
-float32 mm, root-relative, in the table's frame order) by whoever holds the SMPL files.
+Ground-truth meshes come from the frames' SMPL fits through the device SMPL layer (``pmce_amd.smpl``; the reference's
+``PW3D.get_smpl_coord`` / ``Human36M.get_smpl_coord``): ``table.gt_mesh(smpl, idx, device)`` with the caller's SMPL model files, which are
+licensed and not shipped.  What is NOT here: those model files - without them ground-truth joints still come from
+``3DPW_<split>_joint_h36m_cam.json`` as the reference's ``reg_pose3d`` target (dataset.py:229-230,249), and a ground-truth mesh table can
+be supplied instead as ``<data_path>/3DPW_<split>_gt_mesh_cam.npy`` ([N, 6890, 3] float32 mm, root-relative, in the table's frame order).
 
 ``load_h36m`` does the same for ``data/Human36M/dataset.py:105-130,194-350`` (``Human36M.load_data`` + ``load_pose2d_det``; test split,
 the 'human36' input joint set of config/test_mesh_h36m.yml): per-subject annotation / camera / world-joint / SMPL-fit files, the joblib
@@ -59,6 +60,7 @@ class FrameTable:
     mid_valid: np.ndarray = None     # bool [N]: the frame has an SMPL fit - a window whose middle frame has none is dropped (lib/_img_utils.py:75)
     cam_idxs: np.ndarray = None      # int [N]: Human3.6M camera of the frame (the evaluation keeps camera 4, Human36M/dataset.py:742-744)
     extras: dict = field(default_factory=dict)   # whatever else the reference's load_data returns (bboxs, joint_imgs, camera parameters)
+    _smpl_dev: dict = field(default_factory=dict, repr=False, compare=False)   # device -> the SMPL parameter tables uploaded by gt_mesh
 
     def __len__(self):
         return len(self.img_paths)
@@ -94,6 +96,38 @@ class FrameTable:
     def features_on(self, device):
         import torch
         return torch.from_numpy(self.features).to(device)
+
+    def gt_mesh(self, smpl, idx, device, root_mm=None):
+        """Root-relative ground-truth meshes [len(idx), V, 3] in metres of frames `idx`, on `device`, from the frames' SMPL fits:
+        ``((verts_m + trans) * 1000 - root_mm) / 1000``, the reference's ``targets['mesh']`` (PW3D/dataset.py:239-245,
+        Human36M/dataset.py:502-515).  `smpl` is a ``pmce_amd.smpl.SMPL``; root_mm [len(idx), 3] defaults to ``joints_cam_h36m[idx, 0]``.
+        A Human3.6M table (``cam_idxs`` set) uses the world -> camera form with ``extras['cam_Rs']`` / ``extras['cam_ts']``.  The
+        reference's ``fitting_thr`` validity flag (Human36M/dataset.py:510-512: a fit more than 25 mm from the annotated joints marks
+        the sample invalid for TRAINING) is not restated: every frame with a fit gets its mesh.
+        The per-frame parameter tables are uploaded once per device; a call gathers its rows there (one small asynchronous index upload per call,
+        and one per gender of a mixed batch inside ``smpl.forward``; the host does not wait for the stream).  The uploaded copy is made at the first call for a device and does not
+        see later edits of ``self.smpl``, ``joints_cam_h36m`` or the camera tables: the tables are read-only once targets are taken."""
+        import torch
+        idx = np.asarray(idx, dtype=np.int64).reshape(-1)
+        dev = torch.device(device)
+        if dev.index is None:
+            dev = torch.device("cuda", torch.cuda.current_device())
+        tabs = self._smpl_dev.get(dev)
+        if tabs is None:
+            up = lambda a: torch.from_numpy(np.ascontiguousarray(a, dtype=np.float32)).to(dev)    # noqa: E731
+            tabs = {"pose": up(self.smpl["pose"]), "shape": up(self.smpl["shape"]), "trans": up(self.smpl["trans"]),
+                    "root": up(self.joints_cam_h36m[:, 0])}
+            if self.cam_idxs is not None:
+                tabs.update(cam_R=up(self.extras["cam_Rs"]), cam_t=up(self.extras["cam_ts"]))
+            self._smpl_dev[dev] = tabs
+        with torch.cuda.device(dev):
+            from .smpl import upload_async
+            rows = upload_async(idx, dev)
+            root = tabs["root"][rows] if root_mm is None else np.asarray(root_mm, dtype=np.float32).reshape(len(idx), 3)
+            cam = {k: tabs[k][rows] for k in ("cam_R", "cam_t") if k in tabs}
+            verts, _ = smpl.forward(tabs["pose"][rows], tabs["shape"][rows], tabs["trans"][rows], self.smpl["gender"][idx],
+                                    scale=1000.0, offset=root, **cam)
+            return verts / 1000.0
 
     def gt_joints_root_relative(self) -> np.ndarray:
         """The reference's ``reg_pose3d`` target: h36m joints minus their root (dataset.py:229-230), mm."""

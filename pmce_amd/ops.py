@@ -557,3 +557,31 @@ def render_meshes(images, verts, cams, rotation, faces, vf_offsets, vf_faces, jo
                                       1 if depth_order else 0, P(status), P(xy_fixed), P(face_id), P(depth),
                                       C.c_void_p(workspace.data_ptr()), workspace.numel(), _st()), "render_meshes")
     return images
+
+
+def smpl_workspace_bytes(B):
+    """Bytes of workspace pmce_smpl_forward needs for a batch of B rows."""
+    b = int(_lib.load().pmce_smpl_workspace_bytes(int(B)))
+    if b == 0:
+        raise _lib.PmceError(f"smpl_workspace_bytes: {_lib.last_error()}")
+    return b
+
+
+def smpl_forward(model, pose, betas, trans, cam_R, cam_t, sample_index, scale, offset, verts_out, joints_out, workspace):
+    """pmce_smpl_forward on the current stream, in place on verts_out [B,V,3] and joints_out [B,24,3] (pmce_amd.smpl.SMPL prepares the
+    arguments: `model` a smpl.SMPLModel, sample_index an int32 device tensor of the rows to compute or None for all; trans, cam_R + cam_t
+    and offset may be None)."""
+    lib = _lib.load()
+    B, V = verts_out.shape[0], verts_out.shape[1]
+    vt, dirs, wts, jt, jsd = model.to(verts_out.device)
+    if vt.shape[1] != V:
+        raise _lib.PmceError(f"smpl_forward: the model has {vt.shape[1]} vertices, verts_out {V}")
+    par = np.ascontiguousarray(model.parents, dtype=np.int32)
+    if sample_index is not None:
+        assert sample_index.dtype == torch.int32
+    n = B if sample_index is None else int(sample_index.numel())
+    _lib.check(lib.pmce_smpl_forward(P(vt), P(dirs), P(wts), P(jt), P(jsd), par.ctypes.data_as(C.POINTER(C.c_int)), len(par), P(pose),
+                                     P(betas), P(trans), P(cam_R), P(cam_t), P(sample_index), n, scale, P(offset), P(verts_out),
+                                     P(joints_out), C.c_void_p(workspace.data_ptr()), workspace.numel() * workspace.element_size(), B, V,
+                                     _st()), "smpl_forward")
+    return verts_out, joints_out

@@ -8,6 +8,7 @@ that are uploaded ONCE and windowed on the device.
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 scripts/eval_sharded.py --clips 35515
     python scripts/eval_sharded.py --data-dir /data/PW3D/pw3d_data [--checkpoint mesh_3dpw.pth.tar]   # real files
     python scripts/eval_sharded.py --dataset h36m --data-dir /data/Human36M/h36m_data [--checkpoint mesh_h36m.pth.tar]
+    python scripts/eval_sharded.py --data-dir /data/PW3D/pw3d_data --smpl-dir /data/smpl        # MPVPE against meshes made on the device
     python scripts/eval_sharded.py --lifter-only [--joints 17|19] [--data-dir ...]     # config/test_pose_{h36m,3dpw}.yml: LiftTester.test
     python scripts/eval_sharded.py --flavour mpii3d                                    # config/test_mesh_mpii3d.yml: joints only, all 17
     python scripts/eval_sharded.py --dataset mpii3d --data-dir /data/MPII3D/mpii3d_data  # the same on the reference's validation files
@@ -57,6 +58,9 @@ def main():
                                                      "evaluate the real stride-1 window list instead of the synthetic stand-in")
     ap.add_argument("--dataset", default="pw3d", choices=("pw3d", "h36m", "mpii3d"), help="format of --data-dir: the reference's 3DPW files (J = 19) or its "
                                                                               "Human3.6M files (J = 17; the windows of camera 4, as Human36M.evaluate keeps them)")
+    ap.add_argument("--smpl-dir", default=None, help="directory holding the SMPL model files (basicModel_{neutral,f,m}_lbs_10_207_0_v1.0.0.pkl or "
+                                                     ".npz): with --data-dir, every batch's ground-truth meshes are made on the device from the "
+                                                     "frames' SMPL fits (pmce_amd.smpl) and MPVPE is reported")
     ap.add_argument("--split", default="test")
     ap.add_argument("--checkpoint", default=None, help="a reference mesh_*.pth.tar / pose_*.pth.tar (default: deterministic synthetic weights)")
     ap.add_argument("--lifter-only", action="store_true", help="evaluate the pose encoder alone (the reference's test_pose_*.yml / LiftTester)")
@@ -66,6 +70,9 @@ def main():
     args = ap.parse_args()
     if args.data_dir and args.dataset == "mpii3d":      # the reference's MPI-INF-3DHP validation files: config/test_mesh_mpii3d.yml
         args.flavour = "mpii3d"
+    if args.smpl_dir and (not args.data_dir or args.lifter_only or args.flavour == "mpii3d"):
+        ap.error("--smpl-dir makes ground-truth meshes from the SMPL fits of --data-dir's frames: it needs --data-dir with --dataset pw3d or "
+                 "h36m, and the full model (not --lifter-only, not the joints-only mpii3d flavour)")
     if args.flavour == "mpii3d":
         if args.lifter_only or (args.data_dir and args.dataset != "mpii3d"):
             ap.error("--flavour mpii3d runs the full model, on the synthetic stand-in or on --dataset mpii3d --data-dir DIR")
@@ -111,7 +118,13 @@ def main():
         model.set_j_regressor(assets.load_j_regressor("h36m"))
     model = model.to(dev)
     flavour = ("pose_pw3d" if J == 19 else "pose_h36m") if args.lifter_only else (args.flavour or None)
-    ev = Evaluator.for_flavour(flavour, dev) if flavour else Evaluator(dev)
+    smpl = None
+    if args.smpl_dir:   # the mesh is root-aligned with the SMPL regressor's root row (dataset.py:379-384): ONE row for the whole evaluation, the
+        # neutral model's if it is loaded, else the first one's, whatever genders a batch mixes (the reference's joint_regressor_smpl is the neutral layer's)
+        from pmce_amd.smpl import SMPL
+        smpl = SMPL.from_dir(args.smpl_dir)
+    ev = (Evaluator.for_flavour(flavour, dev) if flavour else
+          Evaluator(dev, root_regressor_row=smpl.root_regressor_row()) if smpl is not None else Evaluator(dev))
     if args.lifter_only and J not in (17, 19):
         raise SystemExit("--lifter-only: the reference evaluates 17 (Human3.6M) or 19 (3DPW, COCO set) joints")
     lo, hi = sharding.shard_range(args.clips, rank, world)
@@ -164,7 +177,10 @@ def main():
                 run.add(mesh, synthetic_gt(mesh, b0, pool))                         # per-sample errors + 14x3 joints; the mesh is dropped
             else:   # annotated joints (mm, root-relative); the mesh target only if the caller supplied SMPL meshes (else MPVPE is void)
                 n = mesh.shape[0]
-                gm = mesh if gt_mesh is None else torch.from_numpy(np.ascontiguousarray(gt_mesh[mid[b0:b0 + n]])).to(dev) / 1000.0
+                if smpl is not None:                      # made here, on the device, from the middle frames' SMPL fits
+                    gm = table.gt_mesh(smpl, mid[b0:b0 + n], dev)
+                else:
+                    gm = mesh if gt_mesh is None else torch.from_numpy(np.ascontiguousarray(gt_mesh[mid[b0:b0 + n]])).to(dev) / 1000.0
                 run.add(mesh, gm, gt_joints[b0:b0 + n])
 
         pending = None
@@ -225,8 +241,9 @@ def main():
                     "data": ("synthetic stand-in (no 3DPW / H36M / MPI-INF-3DHP files offline)" if table is None else
                              f"{table.name}: {len(table)} frames, {len(win)} stride-1 windows from {args.data_dir}; targets = "
                              + ("the annotated camera-space joints" if args.lifter_only else "annotated h36m joints"
-                                + ("" if gt_mesh is not None else "; no ground-truth meshes supplied: MPVPE is void")))})
-        if table is not None and gt_mesh is None:
+                                + (f"; ground-truth meshes from the frames' SMPL fits on the device (models: {args.smpl_dir})" if smpl is not None
+                                   else "" if gt_mesh is not None else "; no ground-truth meshes supplied: MPVPE is void")))})
+        if table is not None and gt_mesh is None and smpl is None:
             res["MPVPE"] = None
         print(json.dumps(res))
     if world > 1:
