@@ -546,6 +546,40 @@ int pmce_smpl_forward(const float* v_template_t, const float* dirs_t, const floa
                       const float* offset, float* verts_out, float* joints_out, void* workspace, size_t workspace_bytes, int B, int V,
                       pmce_stream_t stream);
 
+/* ---------------------------------------------------------------------------------------------------------
+ * The demo's person crops (lib/utils/_dataset_demo.py:29-75 CropDataset) from frames that are already on the device.
+ *
+ * pmce_crop_boxes: keypoints[N][K][3] = (x, y, score), fp32, N >= 1 frames of one tracklet -> the box CropDataset crops each frame with,
+ * computed and returned in fp64.  A frame is usable when some score exceeds vis_thresh and (max - min) of those keypoints has Euclidean
+ * length >= 0.5 (lib/utils/smooth_bbox.py:36-59); it gets centre = (min + max) / 2 and scale = 150 / length.  An unusable frame between
+ * two usable ones gets each of (cx, cy, scale) as np.linspace(prev, curr, n + 2)[1:-1] gives it: prev + k * ((curr - prev) / (n + 1)).
+ *   boxes[N][4] (fp64) = (cx, cy, s, s), s = 150 / scale (the reference's second division, :49-50); NaN outside the span;
+ *   usable[N] (int32); span[2] (int32) = (first usable frame, last usable frame + 1): the reference's [time_pt1:time_pt2]; (-1, 0) when
+ *   no frame is usable.  One launch on `stream`, one wavefront per frame, no host wait.
+ *
+ * pmce_crop_patches: job n crops frames[frame_index[n]] (frames[n_frames][height][width][3], uint8) around boxes[n] = (cx, cy, w, h)
+ * (fp64) to a side x side patch, side in 1..1024, width and height <= 16384.  The map is gen_trans_from_patch_cv's with rot = 0
+ * (lib/utils/_img_utils.py:53-86), per axis and in fp64:
+ *     c0 = f32(cx), half = f32(w * scale * 0.5), d = f32(cx + half) - c0, i = d / (side / 2), t = c0 - (side / 2) * i,  x_src = i x_dst + t.
+ * Sampling is the fixed-point bilinear rule of cv2.warpAffine(INTER_LINEAR, BORDER_CONSTANT) on 8-bit images: with rint = round half to
+ * even, X = (rint(t_x * 1024) + 16 + rint(i_x * x * 1024)) >> 5 and Y = (rint((i_y * y + t_y) * 1024) + 16) >> 5 (arithmetic shifts), the
+ * taps are columns X >> 5, (X >> 5) + 1 and rows Y >> 5, (Y >> 5) + 1 with fractions a = X & 31, b = Y & 31 and the integer weights
+ * (32 - b)(32 - a) 32, (32 - b) a 32, b (32 - a) 32, b a 32; a tap outside the frame contributes 0; pixel = (sum + 16384) >> 15.
+ *   norm_table[3][256] (device, fp32): the value output channel c takes for byte v - the caller builds ((v / 255) - mean[c]) / std[c]
+ *     with the very fp32 operations it wants reproduced (pmce_amd.crops: torch's, on the CPU);
+ *   swap_rb != 0: output channel c is the frame's byte 2 - c (BGR frames, RGB patches);
+ *   patch_f32[N][3][side][side]; patch_u8[N][side][side][3] or NULL: the bytes before normalisation (the reference's raw_image);
+ *   status[N] (int32): 0 fine; 1 the box is not finite or w * scale <= 0 or h * scale <= 0; 2 the map's source coordinates leave
+ *     +-2^20 px (OpenCV's saturation is not reproduced); 3 frame_index[n] outside [0, n_frames) in a device table.  A job with status != 0
+ *     gets the all-border patch (byte 0) and reads no frame;
+ *   frame_index is given twice: frame_index_host (may be NULL: a table that exists only on the device is trusted) is validated here, an
+ *     entry outside [0, n_frames) is PMCE_ERR_ARG; frame_index is the same table in device memory.
+ * One launch, no atomics, integer arithmetic after the map: bit-identical from run to run and whatever N. */
+int pmce_crop_boxes(const float* keypoints, int N, int K, double vis_thresh, double* boxes, int* usable, int* span, pmce_stream_t stream);
+int pmce_crop_patches(const unsigned char* frames, int n_frames, int height, int width, const int* frame_index_host,
+                      const int* frame_index, const double* boxes, int n_jobs, double scale, int side, int swap_rb,
+                      const float* norm_table, float* patch_f32, unsigned char* patch_u8, int* status, pmce_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif

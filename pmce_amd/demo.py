@@ -5,6 +5,7 @@ in, what the demo saves per person out - ``pred_cam``, ``mesh``, ``bboxes`` (``f
     out = demo.run_tracklet(model, keypoints[N,17,>=2], features[N,2048], img_wh=(1920, 1080))
     outs = demo.run_tracklets(model, [(kp_a, feat_a), (kp_b, feat_b)], img_wh=(1920, 1080))     # batches filled across people
     video = demo.render_tracklets(outs, frames_u8, (1920, 1080), frame_ids=ids, renderer=render.Renderer(faces, (1920, 1080)))
+    outs = demo.run_video(model, frames_u8, [(kp_a[N,17,3], ids_a), (kp_b, ids_b)], extractor, img_wh=(1920, 1080))   # crops included
 
 Per frame k the demo builds one window (``streaming.demo_window_list``), prepares the fit target from the window's middle frame
 (csrc/demo_prep.hip: add_pelvis_and_neck, get_bbox, process_bbox, j2d_processing), runs the model on the window and fits the
@@ -204,6 +205,83 @@ def tracklet_span(joints2d, vis_thresh: float = 0.3):
             ok[i] = np.linalg.norm(kp[vis, :2].max(0) - kp[vis, :2].min(0)) >= 0.5
     hit = np.nonzero(ok)[0]
     return (int(hit[0]), int(hit[-1]) + 1) if hit.size else (-1, 0)
+
+
+@torch.no_grad()
+def crop_tracklets(frames, tracklets, scale: float = 1.1, size: int = 224, channel_order: str = "rgb", vis_thresh: float = 0.3,
+                   return_raw: bool = False):
+    """The reference's ``CropDataset`` for every person of a video (main/run_demo.py:289-321 up to the feature extractor), on the device:
+    frames uint8 [F,H,W,3], tracklets = [(keypoints[N_i,17,3] (x, y, score), frame_ids[N_i]), ...] ->
+
+        {'patches': fp32 [sum n_i,3,size,size] (all persons, tracklet after tracklet), 'status': int32 [sum n_i], 'offsets': the
+         tracklets' row ranges in them (host, int64 [T+1]), 'keypoints': [fp32 [n_i,17,3] on the device, ...], 'frame_ids': [int64
+         [n_i] on the host, ...], 'spans': [(start, end), ...], 'boxes': [fp64 [n_i,4] on the device, ...][, 'raw': uint8
+         [sum n_i,size,size,3]]}
+
+    The boxes are computed per tracklet (``crops.tracklet_boxes``); every tracklet is then trimmed to its span - the reference's
+    ``[time_pt1:time_pt2]``, and the one host read of this function - and ONE ``crops.crop_patches`` launch cuts all persons' patches.
+    A tracklet without a usable frame keeps no row."""
+    from . import crops
+    crops.check_patch_args(frames, np.zeros(0, np.int32), np.zeros((0, 4)), scale, size, channel_order)
+    F = int(frames.shape[0])
+    ids = []
+    for i, (kp, fid) in enumerate(tracklets):
+        crops.check_keypoints(kp)
+        fid = np.asarray(fid.cpu() if isinstance(fid, torch.Tensor) else fid)
+        if fid.shape != (len(kp),) or not np.issubdtype(fid.dtype, np.integer):
+            raise ValueError(f"tracklet {i}: frame_ids must be an integer array [N = {len(kp)}] (got {fid.dtype} {fid.shape})")
+        if fid.size and (fid.min() < 0 or fid.max() >= F):
+            raise ValueError(f"tracklet {i}: frame_ids run {int(fid.min())}..{int(fid.max())}, there are {F} frames")
+        ids.append(fid.astype(np.int64))
+    if not isinstance(frames, torch.Tensor) or not frames.is_cuda:
+        frames = torch.as_tensor(np.ascontiguousarray(frames)).to(torch.device("cuda", torch.cuda.current_device()))
+    dev = frames.device
+    kps = [torch.as_tensor(kp).to(device=dev, dtype=torch.float32) for kp, _ in tracklets]
+    results = [crops.tracklet_boxes(kp, vis_thresh) for kp in kps]
+    spans = torch.stack([r[2] for r in results]).cpu().numpy() if results else np.zeros((0, 2), np.int64)     # the one host wait
+    spans = [(int(a), int(b)) for a, b in spans]
+    cut = [slice(max(a, 0), b) for a, b in spans]
+    boxes = [r[0][c] for r, c in zip(results, cut)]
+    kps = [k[c] for k, c in zip(kps, cut)]
+    ids = [f[c] for f, c in zip(ids, cut)]
+    offsets = np.concatenate([[0], np.cumsum([len(f) for f in ids])]).astype(np.int64)
+    fi = np.concatenate(ids).astype(np.int32) if ids else np.zeros(0, np.int32)
+    bx = torch.cat(boxes) if boxes else torch.zeros(0, 4, device=dev, dtype=torch.float64)
+    out = crops.crop_patches(frames, fi, bx, scale=scale, size=size, channel_order=channel_order, return_raw=return_raw)
+    res = {"patches": out[0], "status": out[-1], "offsets": offsets, "keypoints": kps, "frame_ids": ids, "spans": spans, "boxes": boxes}
+    if return_raw:
+        res["raw"] = out[1]
+    return res
+
+
+@torch.no_grad()
+def run_video(model, frames, tracklets, extractor, img_wh, extract_batch: int = 256, crop_scale: float = 1.1, crop_size: int = 224,
+              channel_order: str = "rgb", vis_thresh: float = 0.3, **run_tracklets_kwargs):
+    """Frames to what the demo saves: ``crop_tracklets``, then ``extractor(patches[k:k + extract_batch])`` -> [n, 2048] (the caller's
+    callable on device tensors: the reference's is a torch ResNet, main/run_demo.py:248-259,314-321), then ``run_tracklets`` on the
+    trimmed keypoints and those features.  -> ``run_tracklets``' dicts, each with 'frame_ids' (host, int64: the frames its rows belong
+    to) added, ready for ``render_tracklets``.  A tracklet shorter than 16 frames after trimming raises ``run_tracklets``' ValueError."""
+    if int(extract_batch) < 1:
+        raise ValueError(f"extract_batch must be >= 1 (got {extract_batch})")
+    if len(tracklets) == 0:
+        return []
+    c = crop_tracklets(frames, tracklets, scale=crop_scale, size=crop_size, channel_order=channel_order, vis_thresh=vis_thresh)
+    patches, off = c["patches"], c["offsets"]
+    short = [i for i in range(len(tracklets)) if off[i + 1] - off[i] < SEQLEN]
+    if short:                            # before the extractor runs: run_tracklets' own error
+        raise ValueError(f"tracklet {short[0]}: the demo's window list needs at least {SEQLEN} frames (got {int(off[short[0] + 1] - off[short[0]])})")
+    feats = []
+    for k in range(0, patches.shape[0], int(extract_batch)):
+        f = extractor(patches[k:k + int(extract_batch)])
+        if f.ndim != 2 or f.shape[0] != min(int(extract_batch), patches.shape[0] - k) or f.shape[1] != FEAT_DIM:
+            raise ValueError(f"the extractor must return [n, {FEAT_DIM}] (got {tuple(f.shape)})")
+        feats.append(f)
+    feats = torch.cat(feats)
+    outs = run_tracklets(model, [(c["keypoints"][i], feats[int(off[i]):int(off[i + 1])]) for i in range(len(tracklets))], img_wh,
+                         **run_tracklets_kwargs)
+    for o, fid in zip(outs, c["frame_ids"]):
+        o["frame_ids"] = fid
+    return outs
 
 
 def frame_results(results: dict, frame_ids, num_frames: int):
