@@ -580,6 +580,61 @@ int pmce_crop_patches(const unsigned char* frames, int n_frames, int height, int
                       const int* frame_index, const double* boxes, int n_jobs, double scale, int side, int swap_rb,
                       const float* norm_table, float* patch_f32, unsigned char* patch_u8, int* status, pmce_stream_t stream);
 
+/* ---------------------------------------------------------------------------------------------------------
+ * The demo's feature extractor (reference lib/models/spin.py:18-143: Bottleneck, the HMR backbone, HMR.feature_extractor, called at
+ * main/run_demo.py:247-252,315): convolutions on the f16 matrix pipe as three products of the exact two-term split, fp32 operands and
+ * results, NHWC between the layers (csrc/conv.hip, csrc/extractor.cpp).
+ *
+ * pmce_conv_packed_floats: floats of storage of a packed weight = ceil(Cout / 64) * 64 * Kp, Kp = KH KW Cin rounded up to 32; 0 (and the
+ *   error string) for a bad shape.
+ * pmce_conv_pack_split_f16: W_oihw[Cout][Cin][KH][KW] fp32 (BatchNorm already folded) -> Wp = the blocked planes
+ *   [ceil(Cout / 64)][Kp / 16][64][16 hi | 16 lo] f16 of W[n] * 2^s(n) with k = (ky, kx, cin), zero weights for k >= KH KW Cin and for the
+ *   rows past Cout, and wscale[Cout] = 2^-s(n): one power of two per output channel, chosen as pmce_gemm_pack_split_f16 chooses it.
+ * pmce_conv2d_split_f16: out[m][co] = relu?( wscale[co] * sum_k (xhi whi + xhi wlo + xlo whi) + bias[co] + R[m][co]? ), m = (image, oy, ox),
+ *   OH = (H + 2 pad - KH) / stride + 1 (OW likewise); out and R are dense NHWC [n][OH][OW][Cout]; bias and R may be NULL.
+ *   The input element (image i, channel c, row y, column x) is x[i sn + c sc + y sy + x sx] (element strides): NCHW and NHWC alike.  With
+ *   sc == 1, Cin % 16 == 0 and sn, sy, sx multiples of 4 the gather is 16-byte loads; any other input takes the element-wise gather.
+ *   Zero padding is a predicate of the load.  Activations are split while they are staged: a value that is not finite, or whose f16
+ *   part is not (|x| > 65504), makes every output that reads it inf / NaN and no other; the ReLU keeps a NaN.  An output element's
+ *   order of summation depends on nothing but its k index: results are bit-identical whatever n is.
+ * pmce_maxpool3x3s2_nhwc_f32: nn.MaxPool2d(3, 2, 1) on x[n][H][W][C] -> y[n][(H - 1) / 2 + 1][(W - 1) / 2 + 1][C]; C % 4 == 0; the padding
+ *   never wins, a NaN in the window is the result.
+ * pmce_avgpool_nhwc_f32: y[n][C] = the mean of x[n][HW][C] over HW: one fp64 sum per element in pixel order, rounded once.
+ * One launch each on `stream`, no atomics, no synchronisation.
+ *
+ * pmce_extractor: the [3, 4, 6, 3] bottleneck network (53 convolutions, the max pool, the average pool).  The handle owns the packed
+ * weights (one hipMalloc in finalize); the caller owns everything else.
+ *   pmce_extractor_conv_count / _conv_name / _conv_shape (Cout, Cin, KH, KW): the convolutions in the order of the forward, named as the
+ *     reference's state dict names them ("conv1", "layer2.0.conv3", "layer3.0.downsample.0", ...);
+ *   pmce_extractor_set_conv: the folded OIHW weight and the folded bias [Cout] of one convolution (device, fp32); they must stay valid
+ *     until finalize returns;
+ *   pmce_extractor_finalize_on: packs every convolution on `stream` and waits for it (the one call here that synchronises);
+ *     PMCE_ERR_ARG names a convolution that was not set;
+ *   pmce_extractor_workspace_bytes(n): 16-byte aligned device memory a forward of n patches needs (0 and the error string for n outside
+ *     1..4096): three buffers of 112 * 112 * 64 and two of 56 * 56 * 128 floats per patch;
+ *   pmce_extractor_forward: patches [n][3][224][224] through the element strides (sn, sc, sy, sx) -> feats[n][2048]; tap1..tap4, each
+ *     optional, receive the outputs of layer1..layer4 as NHWC [n][56][56][256], [n][28][28][512], [n][14][14][1024], [n][7][7][2048].
+ *     56 launches (and a copy per tap) on `stream`, no synchronisation; patch i's result does not depend on n. */
+typedef struct pmce_extractor pmce_extractor;
+long long pmce_conv_packed_floats(int Cout, int Cin, int KH, int KW);
+int pmce_conv_pack_split_f16(const float* W_oihw, int Cout, int Cin, int KH, int KW, float* Wp, float* wscale, pmce_stream_t stream);
+int pmce_conv2d_split_f16(const float* x, long long sn, long long sc, long long sy, long long sx, int n, int Cin, int H, int W,
+                          const float* Wp, const float* wscale, const float* bias, const float* R, float* out, int Cout, int KH, int KW,
+                          int stride, int pad, int relu, pmce_stream_t stream);
+int pmce_maxpool3x3s2_nhwc_f32(const float* x, float* y, int n, int H, int W, int C, pmce_stream_t stream);
+int pmce_avgpool_nhwc_f32(const float* x, float* y, int n, int HW, int C, pmce_stream_t stream);
+int pmce_extractor_create(pmce_extractor** out);
+void pmce_extractor_destroy(pmce_extractor* e);
+int pmce_extractor_conv_count(const pmce_extractor* e);
+const char* pmce_extractor_conv_name(const pmce_extractor* e, int i);
+int pmce_extractor_conv_shape(const pmce_extractor* e, int i, int* shape4);
+int pmce_extractor_set_conv(pmce_extractor* e, const char* name, const float* folded_weight, const float* folded_bias);
+int pmce_extractor_finalize_on(pmce_extractor* e, pmce_stream_t stream);
+size_t pmce_extractor_workspace_bytes(int n);
+int pmce_extractor_forward(const pmce_extractor* e, const float* patches, long long sn, long long sc, long long sy, long long sx,
+                           float* feats, int n, float* tap1, float* tap2, float* tap3, float* tap4, void* workspace,
+                           size_t workspace_bytes, pmce_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif

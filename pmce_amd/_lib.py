@@ -121,6 +121,20 @@ PROTOTYPES = {
                           _i, _i, _s],
     "pmce_crop_boxes": [_f, _i, _i, _d, _f, _f, _f, _s],
     "pmce_crop_patches": [_f, _i, _i, _i, C.POINTER(C.c_int), _f, _f, _i, _d, _i, _i, _f, _f, _f, _f, _s],
+    "pmce_conv_packed_floats": [_i, _i, _i, _i],
+    "pmce_conv_pack_split_f16": [_f, _i, _i, _i, _i, _f, _f, _s],
+    "pmce_conv2d_split_f16": [_f, _l, _l, _l, _l, _i, _i, _i, _i, _f, _f, _f, _f, _f, _i, _i, _i, _i, _i, _i, _s],
+    "pmce_maxpool3x3s2_nhwc_f32": [_f, _f, _i, _i, _i, _i, _s],
+    "pmce_avgpool_nhwc_f32": [_f, _f, _i, _i, _i, _s],
+    "pmce_extractor_create": [C.POINTER(C.c_void_p)],
+    "pmce_extractor_destroy": [C.c_void_p],
+    "pmce_extractor_conv_count": [C.c_void_p],
+    "pmce_extractor_conv_name": [C.c_void_p, _i],
+    "pmce_extractor_conv_shape": [C.c_void_p, _i, C.POINTER(C.c_int)],
+    "pmce_extractor_set_conv": [C.c_void_p, C.c_char_p, _f, _f],
+    "pmce_extractor_finalize_on": [C.c_void_p, _s],
+    "pmce_extractor_workspace_bytes": [_i],
+    "pmce_extractor_forward": [C.c_void_p, _f, _l, _l, _l, _l, _f, _i, _f, _f, _f, _f, C.c_void_p, C.c_size_t, _s],
 }
 _RESTYPES = {
     "pmce_last_error_string": C.c_char_p,
@@ -133,6 +147,10 @@ _RESTYPES = {
     "pmce_vertex_sab_scratch_floats": C.c_longlong,
     "pmce_render_workspace_bytes": C.c_size_t,
     "pmce_smpl_workspace_bytes": C.c_size_t,
+    "pmce_conv_packed_floats": C.c_longlong,
+    "pmce_extractor_destroy": None,
+    "pmce_extractor_conv_name": C.c_char_p,
+    "pmce_extractor_workspace_bytes": C.c_size_t,
 }
 
 _lib = None

@@ -1,0 +1,192 @@
+// The demo's feature extractor as one call: the backbone of the reference's HMR (lib/models/spin.py:61-143 - stem, max pool, four stages
+// of [3, 4, 6, 3] bottlenecks, the 7 x 7 average; 53 convolutions) on the operators of conv.hip.  Host code only: a table of the 53
+// convolutions in the order of the forward, the packed weights and the launch sequence.  Eval-mode BatchNorm arrives folded into each
+// convolution's weight and bias (pmce_amd/extractor.py folds on the host in fp64).
+#include <hip/hip_runtime.h>
+#include <string.h>
+
+#include <string>
+#include <vector>
+
+#include "common.hpp"
+#include "../../include/pmce_hip.h"
+
+namespace {
+
+struct ConvLayer {
+  std::string name;
+  int cout, cin, k, stride, pad;
+  const float* w_src = nullptr;  // caller's folded OIHW weight and bias (device), read by finalize
+  const float* b_src = nullptr;
+  float* wp = nullptr;  // inside the arena
+  float* wscale = nullptr;
+  float* bias = nullptr;
+};
+
+constexpr int STAGE_PLANES[4] = {64, 128, 256, 512}, STAGE_BLOCKS[4] = {3, 4, 6, 3}, STAGE_STRIDE[4] = {1, 2, 2, 2};
+constexpr int SIDE = 224;
+constexpr size_t FULL = 112 * 112 * 64;  // floats per image of the largest activation (the stem's output; also 56 x 56 x 256)
+constexpr size_t HALF = 56 * 56 * 128;   // of the largest inner activation of a bottleneck (layer2.0.conv1)
+
+size_t align64(size_t floats) { return (floats + 63) / 64 * 64; }
+
+}  // namespace
+
+struct pmce_extractor {
+  std::vector<ConvLayer> convs;
+  float* arena = nullptr;
+  bool finalized = false;
+};
+
+extern "C" int pmce_extractor_create(pmce_extractor** out) {
+  PMCE_REQUIRE(out, "extractor_create: null pointer");
+  pmce_extractor* e = new pmce_extractor();
+  auto add = [&](const std::string& name, int cout, int cin, int k, int stride, int pad) {
+    ConvLayer c;
+    c.name = name; c.cout = cout; c.cin = cin; c.k = k; c.stride = stride; c.pad = pad;
+    e->convs.push_back(c);
+  };
+  add("conv1", 64, 3, 7, 2, 3);
+  int inplanes = 64;
+  for (int s = 0; s < 4; ++s)
+    for (int b = 0; b < STAGE_BLOCKS[s]; ++b) {
+      const std::string p = "layer" + std::to_string(s + 1) + "." + std::to_string(b);
+      const int planes = STAGE_PLANES[s], stride = b == 0 ? STAGE_STRIDE[s] : 1;
+      add(p + ".conv1", planes, inplanes, 1, 1, 0);
+      add(p + ".conv2", planes, planes, 3, stride, 1);
+      add(p + ".conv3", 4 * planes, planes, 1, 1, 0);
+      if (b == 0) add(p + ".downsample.0", 4 * planes, inplanes, 1, stride, 0);
+      inplanes = 4 * planes;
+    }
+  *out = e;
+  return PMCE_OK;
+}
+
+extern "C" void pmce_extractor_destroy(pmce_extractor* e) {
+  if (!e) return;
+  if (e->arena) (void)hipFree(e->arena);
+  delete e;
+}
+
+extern "C" int pmce_extractor_conv_count(const pmce_extractor* e) { return e ? (int)e->convs.size() : 0; }
+
+extern "C" const char* pmce_extractor_conv_name(const pmce_extractor* e, int i) {
+  return e && i >= 0 && i < (int)e->convs.size() ? e->convs[i].name.c_str() : nullptr;
+}
+
+extern "C" int pmce_extractor_conv_shape(const pmce_extractor* e, int i, int* shape4) {
+  PMCE_REQUIRE(e && shape4 && i >= 0 && i < (int)e->convs.size(), "extractor_conv_shape: bad arguments");
+  const ConvLayer& c = e->convs[i];
+  shape4[0] = c.cout; shape4[1] = c.cin; shape4[2] = c.k; shape4[3] = c.k;
+  return PMCE_OK;
+}
+
+extern "C" int pmce_extractor_set_conv(pmce_extractor* e, const char* name, const float* folded_weight, const float* folded_bias) {
+  PMCE_REQUIRE(e && name && folded_weight && folded_bias, "extractor_set_conv: null pointer");
+  PMCE_REQUIRE(!e->finalized, "extractor_set_conv: the extractor is finalized");
+  for (ConvLayer& c : e->convs)
+    if (c.name == name) {
+      c.w_src = folded_weight;
+      c.b_src = folded_bias;
+      return PMCE_OK;
+    }
+  pmce_set_error("extractor_set_conv: no convolution named '%s'", name);
+  return PMCE_ERR_ARG;
+}
+
+extern "C" int pmce_extractor_finalize_on(pmce_extractor* e, pmce_stream_t stream) {
+  PMCE_REQUIRE(e, "extractor_finalize: null pointer");
+  PMCE_REQUIRE(!e->finalized, "extractor_finalize: already finalized");
+  size_t floats = 0;
+  for (const ConvLayer& c : e->convs) {
+    PMCE_REQUIRE(c.w_src && c.b_src, "extractor_finalize: convolution '%s' was not set", c.name.c_str());
+    floats += align64((size_t)pmce_conv_packed_floats(c.cout, c.cin, c.k, c.k)) + 2 * align64((size_t)c.cout);
+  }
+  const hipError_t rc = hipMalloc(reinterpret_cast<void**>(&e->arena), floats * sizeof(float));
+  if (rc != hipSuccess) {
+    e->arena = nullptr;
+    pmce_set_error("extractor_finalize: hipMalloc(%zu bytes) for the split weights failed: %s", floats * sizeof(float), hipGetErrorString(rc));
+    return PMCE_ERR_WORKSPACE;
+  }
+  float* at = e->arena;
+  for (ConvLayer& c : e->convs) {
+    c.wp = at; at += align64((size_t)pmce_conv_packed_floats(c.cout, c.cin, c.k, c.k));
+    c.wscale = at; at += align64((size_t)c.cout);
+    c.bias = at; at += align64((size_t)c.cout);
+    PMCE_TRY(pmce_conv_pack_split_f16(c.w_src, c.cout, c.cin, c.k, c.k, c.wp, c.wscale, stream));
+    if (hipMemcpyAsync(c.bias, c.b_src, (size_t)c.cout * sizeof(float), hipMemcpyDeviceToDevice, stream) != hipSuccess) {
+      pmce_set_error("extractor_finalize: copying the bias of '%s' failed", c.name.c_str());
+      return PMCE_ERR_LAUNCH;
+    }
+  }
+  // the caller may free its folded tensors when this returns
+  if (hipStreamSynchronize(stream) != hipSuccess) {
+    pmce_set_error("extractor_finalize: the packing kernels failed: %s", hipGetErrorString(hipGetLastError()));
+    return PMCE_ERR_LAUNCH;
+  }
+  for (ConvLayer& c : e->convs) c.w_src = c.b_src = nullptr;
+  e->finalized = true;
+  return PMCE_OK;
+}
+
+extern "C" size_t pmce_extractor_workspace_bytes(int n) {
+  if (n < 1 || n > 4096) {
+    pmce_set_error("extractor_workspace_bytes: n must be in 1..4096 (got %d)", n);
+    return 0;
+  }
+  return (size_t)n * (3 * FULL + 2 * HALF) * sizeof(float);
+}
+
+extern "C" int pmce_extractor_forward(const pmce_extractor* e, const float* patches, long long sn, long long sc, long long sy, long long sx,
+                                      float* feats, int n, float* tap1, float* tap2, float* tap3, float* tap4, void* workspace,
+                                      size_t workspace_bytes, pmce_stream_t stream) {
+  PMCE_REQUIRE(e && patches && feats && workspace, "extractor_forward: null pointer");
+  PMCE_REQUIRE(e->finalized, "extractor_forward: the extractor is not finalized");
+  PMCE_REQUIRE(n >= 1 && n <= 4096, "extractor_forward: n must be in 1..4096 (got %d)", n);
+  PMCE_REQUIRE((reinterpret_cast<uintptr_t>(workspace) & 15) == 0 && workspace_bytes >= pmce_extractor_workspace_bytes(n),
+               "extractor_forward: the workspace must be 16-byte aligned and hold %zu bytes (got %zu)", pmce_extractor_workspace_bytes(n), workspace_bytes);
+  float* ws = static_cast<float*>(workspace);
+  float* full[3] = {ws, ws + (size_t)n * FULL, ws + 2 * (size_t)n * FULL};
+  float* t1 = ws + 3 * (size_t)n * FULL;
+  float* t2 = t1 + (size_t)n * HALF;
+  float* taps[4] = {tap1, tap2, tap3, tap4};
+
+  // NHWC convolution of layer ci on [n][h][w][cin]
+  auto conv = [&](int ci, const float* x, int h, int w, const float* res, float* out, bool relu) {
+    const ConvLayer& c = e->convs[ci];
+    return pmce_conv2d_split_f16(x, (long long)h * w * c.cin, 1, (long long)w * c.cin, c.cin, n, c.cin, h, w, c.wp, c.wscale, c.bias, res, out,
+                                 c.cout, c.k, c.k, c.stride, c.pad, relu ? 1 : 0, stream);
+  };
+  {  // the stem reads the patches through the caller's strides
+    const ConvLayer& c = e->convs[0];
+    PMCE_TRY(pmce_conv2d_split_f16(patches, sn, sc, sy, sx, n, 3, SIDE, SIDE, c.wp, c.wscale, c.bias, nullptr, full[0], 64, 7, 7, 2, 3, 1, stream));
+  }
+  PMCE_TRY(pmce_maxpool3x3s2_nhwc_f32(full[0], full[1], n, 112, 112, 64, stream));
+  int cur = 1, side = 56, ci = 1;
+  for (int s = 0; s < 4; ++s) {
+    for (int b = 0; b < STAGE_BLOCKS[s]; ++b) {
+      const int stride = b == 0 ? STAGE_STRIDE[s] : 1, oside = side / stride;
+      const int a = (cur + 1) % 3, o = (cur + 2) % 3;
+      const float* x = full[cur];
+      PMCE_TRY(conv(ci, x, side, side, nullptr, t1, true));
+      PMCE_TRY(conv(ci + 1, t1, side, side, nullptr, t2, true));
+      const float* res = x;
+      if (b == 0) {
+        PMCE_TRY(conv(ci + 3, x, side, side, nullptr, full[a], false));
+        res = full[a];
+      }
+      PMCE_TRY(conv(ci + 2, t2, oside, oside, res, full[o], true));
+      ci += b == 0 ? 4 : 3;
+      cur = o;
+      side = oside;
+    }
+    if (taps[s]) {
+      const size_t bytes = (size_t)n * side * side * 4 * STAGE_PLANES[s] * sizeof(float);
+      if (hipMemcpyAsync(taps[s], full[cur], bytes, hipMemcpyDeviceToDevice, stream) != hipSuccess) {
+        pmce_set_error("extractor_forward: copying the output of layer%d failed", s + 1);
+        return PMCE_ERR_LAUNCH;
+      }
+    }
+  }
+  return pmce_avgpool_nhwc_f32(full[cur], feats, n, 49, 2048, stream);
+}

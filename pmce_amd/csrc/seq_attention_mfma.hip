@@ -333,3 +333,7 @@ extern "C" int pmce_seq_attention_split_f16(const float* qkv, float* out, int ns
 // The temporal blocks' fused form (qkv product + this attention in one kernel) is part of this translation unit: it shares split8_fused
 // and spells the same softmax.
 #include "qkv_attention_fused.hip"
+
+// The feature extractor's convolution (the same three-product split on the same matrix instruction) and its pools are compiled here as
+// well: the library's f16 matrix code stays in the translation units it was in.
+#include "conv.hip"

@@ -1,0 +1,251 @@
+"""The demo's feature extractor on the GPU (csrc/conv.hip, csrc/extractor.cpp): the backbone of the reference's HMR
+(lib/models/spin.py:18-143, called at main/run_demo.py:247-252,315) - patches [n,3,224,224] -> features [n,2048].
+
+    ext = FeatureExtractor.from_checkpoint("spin_model_checkpoint.pth.tar", device)      # torch.load(path)['model']
+    ext = FeatureExtractor.from_state_dict(sd, device)
+    feats = ext(patches)                                                                   # fp32 [n,2048] on the patches' device
+    feats, taps = ext.forward(patches, taps=("layer1", "layer4"))                          # + the named stage outputs, NCHW
+    out = demo.run_video(model, frames, tracklets, ext, img_wh)                            # the extractor is a plain callable
+
+Eval-mode BatchNorm is folded into each convolution on the host in fp64 (``fold_bn``); the device sees 53 convolutions with a bias.
+The operators are also bound one by one (``pack_conv``, ``conv2d``, ``maxpool3x3s2``, ``avgpool``) on NHWC tensors.  There is no
+fallback: without the library's kernels a call raises.
+"""
+from __future__ import annotations
+
+import ctypes as C
+from collections import OrderedDict
+
+import torch
+
+from . import _lib
+
+BN_EPS = 1e-5
+SIDE = 224
+FEAT_DIM = 2048
+LAYERS = ((64, 3, 1), (128, 4, 2), (256, 6, 2), (512, 3, 2))      # (planes, blocks, stride) of layer1..layer4
+TAPS = ("layer1", "layer2", "layer3", "layer4")
+TAP_SHAPES = {"layer1": (56, 256), "layer2": (28, 512), "layer3": (14, 1024), "layer4": (7, 2048)}     # side, channels
+IGNORED_PREFIXES = ("fc1.", "fc2.", "dec", "init_", "smpl.", "drop")
+
+
+def conv_table():
+    """[(conv key, bn key, (Cout, Cin, k, k))] in the order of the forward, the reference's names."""
+    out = [("conv1", "bn1", (64, 3, 7, 7))]
+    inplanes = 64
+    for li, (planes, blocks, _) in enumerate(LAYERS, 1):
+        for b in range(blocks):
+            p = f"layer{li}.{b}"
+            out.append((p + ".conv1", p + ".bn1", (planes, inplanes, 1, 1)))
+            out.append((p + ".conv2", p + ".bn2", (planes, planes, 3, 3)))
+            out.append((p + ".conv3", p + ".bn3", (4 * planes, planes, 1, 1)))
+            if b == 0:
+                out.append((p + ".downsample.0", p + ".downsample.1", (4 * planes, inplanes, 1, 1)))
+            inplanes = 4 * planes
+    return out
+
+
+def required_keys():
+    """name -> shape of every tensor the extractor reads from a state dict."""
+    req = OrderedDict()
+    for ck, bk, shape in conv_table():
+        req[ck + ".weight"] = shape
+        for s in ("weight", "bias", "running_mean", "running_var"):
+            req[f"{bk}.{s}"] = (shape[0],)
+    return req
+
+
+def select_state_dict(sd):
+    """The extractor's tensors of a state dict (an optional ``module.`` prefix stripped; ``num_batches_tracked`` and the regression head
+    ``fc1``, ``fc2``, ``dec*``, ``init_*``, ``smpl.*`` ignored) as fp32 CPU tensors.  A missing or mis-shaped tensor raises a ValueError
+    that names it - the reference loads with strict=False and would keep random weights."""
+    if not hasattr(sd, "items"):
+        raise ValueError(f"a state dict is a mapping of names to tensors (got {type(sd).__name__})")
+    clean = {}
+    for k, v in sd.items():
+        k = k[len("module."):] if k.startswith("module.") else k
+        if k.endswith("num_batches_tracked") or k.startswith(IGNORED_PREFIXES):
+            continue
+        clean[k] = v
+    out = OrderedDict()
+    for name, shape in required_keys().items():
+        if name not in clean:
+            raise ValueError(f"the state dict has no tensor '{name}' (expected shape {tuple(shape)})")
+        t = torch.as_tensor(clean[name])
+        if tuple(t.shape) != tuple(shape):
+            raise ValueError(f"tensor '{name}' has shape {tuple(t.shape)}, expected {tuple(shape)}")
+        out[name] = t.detach().to(device="cpu", dtype=torch.float32)
+    return out
+
+
+def fold_bn(w, gamma, beta, mean, var, eps: float = BN_EPS):
+    """Eval-mode BatchNorm after a bias-free convolution as one convolution with a bias, in fp64, rounded once:
+    s = gamma / sqrt(var + eps), w' = float32(w * s), b' = float32(beta - mean * s)."""
+    s = gamma.double() / torch.sqrt(var.double() + eps)
+    return (w.double() * s.view(-1, 1, 1, 1)).float().contiguous(), (beta.double() - mean.double() * s).float().contiguous()
+
+
+def check_patches(patches):
+    """fp32 [n, 3, 224, 224] -> n; raises ValueError otherwise (the reference's AvgPool2d(7) + view only yields 2048 numbers at this size)."""
+    shape = tuple(getattr(patches, "shape", ()))
+    if not isinstance(patches, torch.Tensor) or patches.dtype != torch.float32 or len(shape) != 4 or shape[1:] != (3, SIDE, SIDE):
+        raise ValueError(f"patches must be a float32 tensor [n, 3, {SIDE}, {SIDE}] (got {getattr(patches, 'dtype', type(patches).__name__)} "
+                         f"{shape})")
+    return int(shape[0])
+
+
+# ----------------------------------------------------------------------------------------------
+# the operators, one by one (NHWC device tensors)
+# ----------------------------------------------------------------------------------------------
+
+def pack_conv(weight_oihw):
+    """fp32 device [Cout,Cin,KH,KW] (BatchNorm folded) -> (planes, wscale[Cout]) for ``conv2d``."""
+    w = weight_oihw.contiguous()
+    co, ci, kh, kw = (int(s) for s in w.shape)
+    lib = _lib.load()
+    floats = lib.pmce_conv_packed_floats(co, ci, kh, kw)
+    if floats <= 0:
+        raise _lib.PmceError(_lib.last_error())
+    planes = torch.empty(floats, device=w.device, dtype=torch.float32)
+    wscale = torch.empty(co, device=w.device, dtype=torch.float32)
+    with torch.cuda.device(w.device):
+        _lib.check(lib.pmce_conv_pack_split_f16(_lib.ptr(w), co, ci, kh, kw, _lib.ptr(planes), _lib.ptr(wscale), _lib.current_stream()),
+                   "conv_pack_split_f16")
+    return planes, wscale
+
+
+def conv2d(x, layout, planes, wscale, weight_shape, bias=None, residual=None, stride=1, pad=0, relu=False):
+    """x: a device tensor in ``layout`` "nhwc" or "nchw" (any strides); -> NHWC [n,OH,OW,Cout].  residual: contiguous NHWC like the result."""
+    co, ci, kh, kw = weight_shape
+    if layout == "nhwc":
+        n, h, w, c = x.shape
+        sn, sy, sx, sc = x.stride()
+    elif layout == "nchw":
+        n, c, h, w = x.shape
+        sn, sc, sy, sx = x.stride()
+    else:
+        raise ValueError(f"layout must be 'nhwc' or 'nchw' (got {layout!r})")
+    if c != ci or x.dtype != torch.float32:
+        raise ValueError(f"conv2d: the input has {c} channels of {x.dtype}, the weight reads {ci} of float32")
+    oh, ow = (h + 2 * pad - kh) // stride + 1, (w + 2 * pad - kw) // stride + 1
+    out = torch.empty(n, oh, ow, co, device=x.device, dtype=torch.float32)
+    if residual is not None and (tuple(residual.shape) != tuple(out.shape) or not residual.is_contiguous()):
+        raise ValueError(f"conv2d: the residual must be contiguous NHWC {tuple(out.shape)} (got {tuple(residual.shape)})")
+    with torch.cuda.device(x.device):
+        _lib.check(_lib.load().pmce_conv2d_split_f16(
+            C.c_void_p(x.data_ptr()), sn, sc, sy, sx, n, ci, h, w, _lib.ptr(planes), _lib.ptr(wscale), _lib.ptr(bias), _lib.ptr(residual),
+            _lib.ptr(out), co, kh, kw, stride, pad, 1 if relu else 0, _lib.current_stream()), "conv2d_split_f16")
+    return out
+
+
+def maxpool3x3s2(x):
+    """contiguous NHWC [n,H,W,C] -> [n,(H-1)//2+1,(W-1)//2+1,C]: nn.MaxPool2d(3, 2, 1)."""
+    n, h, w, c = x.shape
+    out = torch.empty(n, (h - 1) // 2 + 1, (w - 1) // 2 + 1, c, device=x.device, dtype=torch.float32)
+    with torch.cuda.device(x.device):
+        _lib.check(_lib.load().pmce_maxpool3x3s2_nhwc_f32(_lib.ptr(x), _lib.ptr(out), n, h, w, c, _lib.current_stream()), "maxpool3x3s2")
+    return out
+
+
+def avgpool(x):
+    """contiguous NHWC [n,H,W,C] -> [n,C]: the mean over the pixels."""
+    n, h, w, c = x.shape
+    out = torch.empty(n, c, device=x.device, dtype=torch.float32)
+    with torch.cuda.device(x.device):
+        _lib.check(_lib.load().pmce_avgpool_nhwc_f32(_lib.ptr(x), _lib.ptr(out), n, h * w, c, _lib.current_stream()), "avgpool")
+    return out
+
+
+# ----------------------------------------------------------------------------------------------
+# the network
+# ----------------------------------------------------------------------------------------------
+
+class FeatureExtractor:
+    """SPIN's ResNet-50 backbone as HIP convolutions.  ``max_batch``: patches per launch sequence (the workspace, 12.8 MB per patch, is
+    allocated once for it and reused); ``check_finite``: raise when a feature is not finite, naming the first such patch."""
+
+    def __init__(self, folded, device, max_batch: int = 64, check_finite: bool = True):
+        if int(max_batch) != max_batch or not 1 <= int(max_batch) <= 4096:
+            raise ValueError(f"max_batch must be a whole number in 1..4096 (got {max_batch!r})")
+        self.device = torch.device(device)
+        self.max_batch = int(max_batch)
+        self.check_finite = bool(check_finite)
+        self._ws = None
+        lib = _lib.load()
+        h = C.c_void_p()
+        _lib.check(lib.pmce_extractor_create(C.byref(h)), "extractor_create")
+        self._h = h
+        with torch.cuda.device(self.device):
+            keep = []
+            for ck, _, shape in conv_table():
+                w, b = folded[ck]
+                assert tuple(w.shape) == tuple(shape) and tuple(b.shape) == (shape[0],)
+                wd, bd = w.to(self.device).contiguous(), b.to(self.device).contiguous()
+                keep.append((wd, bd))
+                _lib.check(lib.pmce_extractor_set_conv(h, ck.encode(), _lib.ptr(wd), _lib.ptr(bd)), "extractor_set_conv")
+            torch.cuda.current_stream().synchronize()        # the uploads (pageable copies run on the legacy stream) are done
+            _lib.check(lib.pmce_extractor_finalize_on(h, _lib.current_stream()), "extractor_finalize")
+            del keep
+
+    def __del__(self):
+        h, self._h = getattr(self, "_h", None), None
+        if h and _lib._lib is not None:
+            _lib._lib.pmce_extractor_destroy(h)
+
+    @classmethod
+    def from_state_dict(cls, sd, device="cuda", **kw):
+        t = select_state_dict(sd)
+        folded = {ck: fold_bn(t[ck + ".weight"], t[bk + ".weight"], t[bk + ".bias"], t[bk + ".running_mean"], t[bk + ".running_var"])
+                  for ck, bk, _ in conv_table()}
+        return cls(folded, device, **kw)
+
+    @classmethod
+    def from_checkpoint(cls, path, device="cuda", **kw):
+        """``torch.load(path)['model']``, as main/run_demo.py:250-251 reads the SPIN checkpoint."""
+        ckpt = torch.load(path, map_location="cpu", weights_only=False)
+        if not hasattr(ckpt, "keys") or "model" not in ckpt:
+            raise ValueError(f"{path}: the checkpoint has no 'model' entry")
+        return cls.from_state_dict(ckpt["model"], device, **kw)
+
+    def _workspace(self):
+        if self._ws is None:
+            nbytes = _lib.load().pmce_extractor_workspace_bytes(self.max_batch)
+            if nbytes == 0:
+                raise _lib.PmceError(_lib.last_error())
+            self._ws = torch.empty(nbytes // 4, device=self.device, dtype=torch.float32)
+        return self._ws
+
+    @torch.no_grad()
+    def forward(self, patches, taps=()):
+        """patches fp32 [n,3,224,224] (a host tensor is uploaded; any strides) -> features [n,2048][, {name: NCHW stage output} for the
+        names in ``taps``], by pmce_extractor_forward on the current stream, ``max_batch`` patches at a time."""
+        n = check_patches(patches)
+        for t in taps:
+            if t not in TAPS:
+                raise ValueError(f"taps must be among {TAPS} (got {t!r})")
+        x = patches.to(self.device)
+        if any(s < 1 for s in x.stride()):
+            x = x.contiguous()
+        feats = torch.empty(n, FEAT_DIM, device=self.device, dtype=torch.float32)
+        tap_out = {t: torch.empty(n, TAP_SHAPES[t][0], TAP_SHAPES[t][0], TAP_SHAPES[t][1], device=self.device, dtype=torch.float32)
+                   for t in taps}
+        lib = _lib.load()
+        with torch.cuda.device(self.device):
+            ws = self._workspace() if n else None
+            for i0 in range(0, n, self.max_batch):
+                m = min(self.max_batch, n - i0)
+                xi = x[i0:i0 + m]
+                sn, sc, sy, sx = xi.stride()
+                tp = [C.c_void_p(tap_out[t][i0:].data_ptr()) if t in tap_out else None for t in TAPS]
+                _lib.check(lib.pmce_extractor_forward(self._h, C.c_void_p(xi.data_ptr()), sn, sc, sy, sx, C.c_void_p(feats[i0:].data_ptr()), m,
+                                                      *tp, _lib.ptr(ws), ws.numel() * 4, _lib.current_stream()), "extractor_forward")
+        if self.check_finite and n:
+            bad = ~torch.isfinite(feats).all(dim=1)
+            if bool(bad.any()):
+                raise _lib.PmceError(f"extractor: patch {int(bad.nonzero()[0])} has non-finite features (an input that is not finite, or an "
+                                     "activation beyond the f16 range of the split)")
+        if taps:
+            return feats, {t: v.permute(0, 3, 1, 2) for t, v in tap_out.items()}
+        return feats
+
+    __call__ = forward

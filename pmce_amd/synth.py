@@ -154,6 +154,36 @@ def pmce_spec(num_joint: int, embed_dim: int = 256, depth: int = 3) -> "OrderedD
     return s
 
 
+def _conv_bn(s, conv, bn, cout, cin, k, bn_scale=1.0):
+    s[conv + ".weight"] = ((cout, cin, k, k), float(np.sqrt(6.0 / (cin * k * k))), 0.0)     # He-uniform
+    s[bn + ".weight"] = ((cout,), 0.5 * bn_scale, 1.0 * bn_scale)
+    s[bn + ".bias"] = ((cout,), 0.2, 0.0)
+    s[bn + ".running_mean"] = ((cout,), 0.2, 0.0)
+    s[bn + ".running_var"] = ((cout,), 0.5, 1.0)
+
+
+EXTRACTOR_LAYERS = ((64, 3, 1), (128, 4, 2), (256, 6, 2), (512, 3, 2))    # (planes, blocks, stride) of layer1..layer4
+
+
+def extractor_spec(prefix: str = "") -> "OrderedDict[str, tuple]":
+    """name -> (shape, half-width, offset) for the backbone of the demo's feature extractor (reference lib/models/spin.py:18-143: the
+    stem, four stages of [3, 4, 6, 3] bottlenecks): He-uniform convolutions, BatchNorm weight in (0.5, 1.5) - halved for every bn3, so
+    that the residual sum stays in range over sixteen blocks -, bias and running_mean in (-0.2, 0.2), running_var in (0.5, 1.5)."""
+    s: OrderedDict = OrderedDict()
+    _conv_bn(s, prefix + "conv1", prefix + "bn1", 64, 3, 7)
+    inplanes = 64
+    for li, (planes, blocks, stride) in enumerate(EXTRACTOR_LAYERS, 1):
+        for b in range(blocks):
+            p = f"{prefix}layer{li}.{b}"
+            _conv_bn(s, p + ".conv1", p + ".bn1", planes, inplanes, 1)
+            _conv_bn(s, p + ".conv2", p + ".bn2", planes, planes, 3)
+            _conv_bn(s, p + ".conv3", p + ".bn3", 4 * planes, planes, 1, bn_scale=0.5)
+            if b == 0:
+                _conv_bn(s, p + ".downsample.0", p + ".downsample.1", 4 * planes, inplanes, 1)
+            inplanes = 4 * planes
+    return s
+
+
 def make_state_dict(spec, seed: int = 123, as_torch: bool = True):
     """Materialise a spec. seed 123 = the reference's default --seed (main/test.py:12)."""
     out = OrderedDict()
