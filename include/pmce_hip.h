@@ -545,6 +545,15 @@ int pmce_smpl_forward(const float* v_template_t, const float* dirs_t, const floa
                       const float* trans, const float* cam_R, const float* cam_t, const int* sample_index, int n, float scale,
                       const float* offset, float* verts_out, float* joints_out, void* workspace, size_t workspace_bytes, int B, int V,
                       pmce_stream_t stream);
+/* The same layer on rotation matrices (smplx's pose2rot = False, what the HMR head calls: lib/models/spin.py:184-189):
+ * rotmats[B][24][3][3] row-major replace `pose` and are used as they are - the pose map is R[1:] - I, no Rodrigues formula - and there is
+ * no camera form.  betas is read at betas[b * betas_stride + 0..9], betas_stride >= 10 (the head's state rows hold the shape at a stride
+ * of 157).  Everything else, the workspace included, is as for pmce_smpl_forward, whose pose kernel shares its body with this one. */
+int pmce_smpl_forward_rotmat(const float* v_template_t, const float* dirs_t, const float* weights_t, const float* j_template,
+                             const float* j_shapedirs, const int* parents_host, int n_joints, const float* rotmats,
+                             const float* betas, int betas_stride, const float* trans, const int* sample_index, int n, float scale,
+                             const float* offset, float* verts_out, float* joints_out, void* workspace, size_t workspace_bytes, int B,
+                             int V, pmce_stream_t stream);
 
 /* ---------------------------------------------------------------------------------------------------------
  * The demo's person crops (lib/utils/_dataset_demo.py:29-75 CropDataset) from frames that are already on the device.
@@ -634,6 +643,36 @@ size_t pmce_extractor_workspace_bytes(int n);
 int pmce_extractor_forward(const pmce_extractor* e, const float* patches, long long sn, long long sc, long long sy, long long sx,
                            float* feats, int n, float* tap1, float* tap2, float* tap3, float* tap4, void* workspace,
                            size_t workspace_bytes, pmce_stream_t stream);
+
+/* ---------------------------------------------------------------------------------------------------------
+ * SPIN's regression head (reference lib/models/spin.py:145-208 after the backbone = Regressor.forward :211-293, eval mode): features ->
+ * the state (6D pose 144, shape 10, camera 3), rotation matrices, theta; then the 49 joints and their projection.
+ *
+ * pmce_hmr_head_f32: in eval mode n_iter iterations of fc1, fc2, decpose | decshape | deccam are one affine map of the initial state,
+ *     state = Q features + cst [+ P init]      (pmce_amd.hmr.fold_regressor: Q [157][2048], P [157][157], c_n, fp64 rounded to fp32 once).
+ *   features[n][2048]; q_t[2048][160] = Q transposed, each row padded with three zeros; cst[157] = c_n, or P s_0 + c_n when every sample
+ *   starts from the same state; pmi_t[157][160] = (P - I) transposed and padded + init[n][157] (both or neither): per-sample initial
+ *   states, computed as init + (cst + Q features + (P - I) init) - P is the identity plus a small correction, and the correction summed
+ *   on its own loses less than 157 terms summed at the magnitude of the state.
+ *   Outputs: state[n][157]; rotmat[n][24][3][3] = rot6d_to_rotmat of the state's first 144 numbers (lib/geometry.py:346-360: of each six
+ *   a1 = elements 0, 2, 4 and a2 = elements 1, 3, 5, each normalised by max(norm, 1e-6), the vectors are the columns);
+ *   theta[n][85] = (camera 3, rotation_matrix_to_angle_axis 72, shape 10) with geometry.py:84-249's four-branch quaternion (eps = 1e-6 on
+ *   R22, R00 > R11, R00 < -R11), atan2 with the sign flip, k = 2 where sin^2 = 0, and NaN -> 0.
+ *   One launch on `stream`, a batch tile of pmce_hmr_head_batch_tile() = 16 samples per workgroup, plain fp32 multiply-adds in a fixed
+ *   order: a sample's result depends on its own row only and has the same bits whatever n and wherever it sits; with q_t = 0, P = I
+ *   (pmi_t = 0), cst = 0 the state is `init` to the bit.  No atomics, no host wait.
+ *
+ * pmce_hmr_joints_f32: kp_3d[s][k] = joints[s][sel[k]] where sel[k] >= 0 (a posed SMPL joint, < 24), else row k of the CSR matrix
+ *   (indptr[K + 1], indices, data; columns in [0, V)) times verts[s][V][3]; kp_2d[s][k] = 5000 (p.xy / p.z) / 112 with
+ *   p = kp_3d + (cam1, cam2, 2 * 5000 / (224 cam0 + 1e-9)) (spin.py:309-353), cam read at cam[s * cam_stride + 0..2].
+ *   joints[n][24][3], kp_3d[n][K][3], kp_2d[n][K][2], K in 1..256; sel, indptr, indices, data on the device.  One wave per sample.
+ * Both return PMCE_ERR_ARG and set the error string for n < 1, a null pointer, P without init (or init without P), K out of range. */
+int pmce_hmr_head_batch_tile(void);
+int pmce_hmr_head_f32(const float* features, const float* q_t, const float* cst, const float* pmi_t, const float* init, int n,
+                      float* state, float* rotmat, float* theta, pmce_stream_t stream);
+int pmce_hmr_joints_f32(const float* joints, const float* verts, const int* sel, const int* indptr, const int* indices,
+                        const float* data, const float* cam, int cam_stride, int n, int K, int V, float* kp_3d, float* kp_2d,
+                        pmce_stream_t stream);
 
 #ifdef __cplusplus
 }

@@ -119,6 +119,8 @@ PROTOTYPES = {
     "pmce_smpl_workspace_bytes": [_i],
     "pmce_smpl_forward": [_f, _f, _f, _f, _f, C.POINTER(C.c_int), _i, _f, _f, _f, _f, _f, _f, _i, _fl, _f, _f, _f, C.c_void_p, C.c_size_t,
                           _i, _i, _s],
+    "pmce_smpl_forward_rotmat": [_f, _f, _f, _f, _f, C.POINTER(C.c_int), _i, _f, _f, _i, _f, _f, _i, _fl, _f, _f, _f, C.c_void_p,
+                                 C.c_size_t, _i, _i, _s],
     "pmce_crop_boxes": [_f, _i, _i, _d, _f, _f, _f, _s],
     "pmce_crop_patches": [_f, _i, _i, _i, C.POINTER(C.c_int), _f, _f, _i, _d, _i, _i, _f, _f, _f, _f, _s],
     "pmce_conv_packed_floats": [_i, _i, _i, _i],
@@ -135,6 +137,9 @@ PROTOTYPES = {
     "pmce_extractor_finalize_on": [C.c_void_p, _s],
     "pmce_extractor_workspace_bytes": [_i],
     "pmce_extractor_forward": [C.c_void_p, _f, _l, _l, _l, _l, _f, _i, _f, _f, _f, _f, C.c_void_p, C.c_size_t, _s],
+    "pmce_hmr_head_batch_tile": [],
+    "pmce_hmr_head_f32": [_f, _f, _f, _f, _f, _i, _f, _f, _f, _s],
+    "pmce_hmr_joints_f32": [_f, _f, _f, _f, _f, _f, _f, _i, _i, _i, _i, _f, _f, _s],
 }
 _RESTYPES = {
     "pmce_last_error_string": C.c_char_p,

@@ -26,6 +26,9 @@
 // pipe.  No atomics; a sample's result is a function of its own row only (a tail tile computes on zeros and stores nothing), so it
 // does not depend on the batch it is in, and two runs give the same bits.  `sample_index` makes one launch serve the samples of one
 // gender in place: rows are read and written at the listed indices, nothing is gathered or scattered.
+// pmce_smpl_forward_rotmat is the same layer on rotation matrices (smplx's pose2rot = False, what SPIN's regression head calls,
+// lib/models/spin.py:184-189): smpl_pose_rotmat_kernel takes the 24 matrices as they are instead of going through Rodrigues' formula; the
+// two pose kernels are instantiations of one body, the skinning kernel is shared.
 #include "common.hpp"
 
 namespace {
@@ -47,13 +50,17 @@ __device__ __forceinline__ float* ws_A(float* ws, int s) { return ws + (size_t)s
 __device__ __forceinline__ float* ws_coef(float* ws, int B, int s) { return ws + (size_t)B * SMPL_A + (size_t)s * SMPL_KP; }
 __device__ __forceinline__ float* ws_trans(float* ws, int B, int s) { return ws + (size_t)B * (SMPL_A + SMPL_KP) + (size_t)s * 4; }
 
-__global__ __launch_bounds__(64) void smpl_pose_kernel(const float* __restrict__ pose, const float* __restrict__ betas,
-                                                       const float* __restrict__ trans, const float* __restrict__ cam_R,
-                                                       const float* __restrict__ cam_t, const float* __restrict__ j_template,
-                                                       const float* __restrict__ j_shapedirs, SmplParents par,
-                                                       const int* __restrict__ sample_index, int B, float scale,
-                                                       const float* __restrict__ offset, float* __restrict__ ws,
-                                                       float* __restrict__ joints_out) {
+// The pose stage's body, shared by the two kernels below.  ROTMAT = false: `pose` holds 72 axis-angle numbers per sample and goes through
+// Rodrigues' formula.  ROTMAT = true (smplx's pose2rot = False, what the HMR head calls): `pose` holds the 24 matrices themselves, row-major,
+// and they are taken as they are.  Everything after the matrices - pose map, rest joints, chain, A - is the same text for both.
+template <bool ROTMAT>
+__device__ __forceinline__ void smpl_pose_body(const float* __restrict__ pose, const float* __restrict__ betas, int betas_stride,
+                                               const float* __restrict__ trans, const float* __restrict__ cam_R,
+                                               const float* __restrict__ cam_t, const float* __restrict__ j_template,
+                                               const float* __restrict__ j_shapedirs, const SmplParents& par,
+                                               const int* __restrict__ sample_index, int B, float scale,
+                                               const float* __restrict__ offset, float* __restrict__ ws,
+                                               float* __restrict__ joints_out) {
   __shared__ float sR[SMPL_J][9];
   __shared__ float sJ[SMPL_J][3];
   __shared__ float sG[SMPL_J][12];
@@ -65,7 +72,7 @@ __global__ __launch_bounds__(64) void smpl_pose_kernel(const float* __restrict__
   float* coef = ws_coef(ws, B, s);
 
   // shape: Human36M/dataset.py:365 zeroes the whole row where any |beta| > 3 (camera form only)
-  float b = lane < 10 ? betas[(size_t)s * 10 + lane] : 0.f;
+  float b = lane < 10 ? betas[(size_t)s * betas_stride + lane] : 0.f;
   if (cam_R && __ballot(lane < 10 && fabsf(b) > 3.0f) != 0ull) b = 0.f;
   if (lane < 10) {
     sBeta[lane] = b;
@@ -73,8 +80,9 @@ __global__ __launch_bounds__(64) void smpl_pose_kernel(const float* __restrict__
   }
   if (lane < 3) coef[SMPL_K + lane] = 0.f;
 
-  // rodrigues_layer.py:41-52 + :13-38, one joint per lane
-  if (lane < SMPL_J) {
+  if (ROTMAT) {
+    for (int i = lane; i < SMPL_J * 9; i += 64) sR[i / 9][i % 9] = pose[(size_t)s * (SMPL_J * 9) + i];
+  } else if (lane < SMPL_J) {  // rodrigues_layer.py:41-52 + :13-38, one joint per lane
     const float a0 = pose[(size_t)s * 72 + 3 * lane + 0], a1 = pose[(size_t)s * 72 + 3 * lane + 1],
                 a2 = pose[(size_t)s * 72 + 3 * lane + 2];
     const float e0 = a0 + 1e-8f, e1 = a1 + 1e-8f, e2 = a2 + 1e-8f;
@@ -167,6 +175,28 @@ __global__ __launch_bounds__(64) void smpl_pose_kernel(const float* __restrict__
     const float o = offset ? offset[(size_t)s * 3 + rr] : 0.f;
     joints_out[(size_t)s * 72 + i] = (sG[j][4 * rr + 3] + sT[rr]) * scale - o;
   }
+}
+
+__global__ __launch_bounds__(64) void smpl_pose_kernel(const float* __restrict__ pose, const float* __restrict__ betas,
+                                                       const float* __restrict__ trans, const float* __restrict__ cam_R,
+                                                       const float* __restrict__ cam_t, const float* __restrict__ j_template,
+                                                       const float* __restrict__ j_shapedirs, SmplParents par,
+                                                       const int* __restrict__ sample_index, int B, float scale,
+                                                       const float* __restrict__ offset, float* __restrict__ ws,
+                                                       float* __restrict__ joints_out) {
+  smpl_pose_body<false>(pose, betas, 10, trans, cam_R, cam_t, j_template, j_shapedirs, par, sample_index, B, scale, offset, ws,
+                        joints_out);
+}
+
+__global__ __launch_bounds__(64) void smpl_pose_rotmat_kernel(const float* __restrict__ rotmats, const float* __restrict__ betas,
+                                                              int betas_stride, const float* __restrict__ trans,
+                                                              const float* __restrict__ j_template,
+                                                              const float* __restrict__ j_shapedirs, SmplParents par,
+                                                              const int* __restrict__ sample_index, int B, float scale,
+                                                              const float* __restrict__ offset, float* __restrict__ ws,
+                                                              float* __restrict__ joints_out) {
+  smpl_pose_body<true>(rotmats, betas, betas_stride, trans, nullptr, nullptr, j_template, j_shapedirs, par, sample_index, B, scale,
+                       offset, ws, joints_out);
 }
 
 __global__ __launch_bounds__(SMPL_VT, 4) void smpl_skin_kernel(const float* __restrict__ vt, const float* __restrict__ dirs,
@@ -292,12 +322,14 @@ extern "C" size_t pmce_smpl_workspace_bytes(int B) {
   return (size_t)B * SMPL_WS_FLOATS * sizeof(float);
 }
 
-extern "C" int pmce_smpl_forward(const float* v_template_t, const float* dirs_t, const float* weights_t, const float* j_template,
-                                 const float* j_shapedirs, const int* parents_host, int n_joints, const float* pose,
-                                 const float* betas, const float* trans, const float* cam_R, const float* cam_t,
-                                 const int* sample_index, int n, float scale, const float* offset, float* verts_out,
-                                 float* joints_out, void* workspace, size_t workspace_bytes, int B, int V, hipStream_t stream) {
-  const char* what = "smpl_forward";
+namespace {
+
+// The checks and the two launches that both entry points share; `rot`: pose holds rotation matrices [B][24][9] instead of axis-angle.
+int smpl_forward_impl(const char* what, const float* v_template_t, const float* dirs_t, const float* weights_t, const float* j_template,
+                      const float* j_shapedirs, const int* parents_host, int n_joints, const float* pose, bool rot,
+                      const float* betas, int betas_stride, const float* trans, const float* cam_R, const float* cam_t,
+                      const int* sample_index, int n, float scale, const float* offset, float* verts_out, float* joints_out,
+                      void* workspace, size_t workspace_bytes, int B, int V, hipStream_t stream) {
   PMCE_REQUIRE(V >= 1, "%s: V must be >= 1 (got %d)", what, V);
   PMCE_REQUIRE(B >= 1, "%s: B must be >= 1 (got %d)", what, B);
   PMCE_REQUIRE(n_joints == SMPL_J, "%s: the kinematic tree must have %d joints (got %d)", what, SMPL_J, n_joints);
@@ -311,6 +343,7 @@ extern "C" int pmce_smpl_forward(const float* v_template_t, const float* dirs_t,
   }
   PMCE_REQUIRE(v_template_t && dirs_t && weights_t && j_template && j_shapedirs, "%s: null model table", what);
   PMCE_REQUIRE(pose && betas && verts_out && joints_out && workspace, "%s: null pointer", what);
+  PMCE_REQUIRE(betas_stride >= 10, "%s: betas_stride must be >= 10 (got %d)", what, betas_stride);
   PMCE_REQUIRE((cam_R != nullptr) == (cam_t != nullptr), "%s: cam_R and cam_t go together (both or neither)", what);
   if (sample_index) {
     PMCE_REQUIRE(n >= 1 && n <= B, "%s: with sample_index n must be in 1..B = %d (got %d)", what, B, n);
@@ -326,11 +359,38 @@ extern "C" int pmce_smpl_forward(const float* v_template_t, const float* dirs_t,
   PMCE_REQUIRE((long long)V * 3 * SMPL_KP < (1ll << 31), "%s: V = %d is too large", what, V);
   PMCE_REQUIRE(n <= 65535 * SMPL_TB, "%s: n = %d is more than one launch takes (%d)", what, n, 65535 * SMPL_TB);
   float* ws = static_cast<float*>(workspace);
-  hipLaunchKernelGGL(smpl_pose_kernel, dim3(n), dim3(64), 0, stream, pose, betas, trans, cam_R, cam_t, j_template, j_shapedirs, par,
-                     sample_index, B, scale, offset, ws, joints_out);
-  PMCE_TRY(pmce_check_launch("smpl_forward(pose)"));
+  if (rot) {
+    hipLaunchKernelGGL(smpl_pose_rotmat_kernel, dim3(n), dim3(64), 0, stream, pose, betas, betas_stride, trans, j_template,
+                       j_shapedirs, par, sample_index, B, scale, offset, ws, joints_out);
+  } else {
+    hipLaunchKernelGGL(smpl_pose_kernel, dim3(n), dim3(64), 0, stream, pose, betas, trans, cam_R, cam_t, j_template, j_shapedirs, par,
+                       sample_index, B, scale, offset, ws, joints_out);
+  }
+  PMCE_TRY(pmce_check_launch(rot ? "smpl_forward_rotmat(pose)" : "smpl_forward(pose)"));
   const dim3 grid((V + SMPL_VT - 1) / SMPL_VT, (n + SMPL_TB - 1) / SMPL_TB);
   hipLaunchKernelGGL(smpl_skin_kernel, grid, dim3(SMPL_VT), 0, stream, v_template_t, dirs_t, weights_t, ws, sample_index, n, B, V,
                      scale, offset, verts_out);
-  return pmce_check_launch("smpl_forward(skin)");
+  return pmce_check_launch(rot ? "smpl_forward_rotmat(skin)" : "smpl_forward(skin)");
+}
+
+}  // namespace
+
+extern "C" int pmce_smpl_forward(const float* v_template_t, const float* dirs_t, const float* weights_t, const float* j_template,
+                                 const float* j_shapedirs, const int* parents_host, int n_joints, const float* pose,
+                                 const float* betas, const float* trans, const float* cam_R, const float* cam_t,
+                                 const int* sample_index, int n, float scale, const float* offset, float* verts_out,
+                                 float* joints_out, void* workspace, size_t workspace_bytes, int B, int V, hipStream_t stream) {
+  return smpl_forward_impl("smpl_forward", v_template_t, dirs_t, weights_t, j_template, j_shapedirs, parents_host, n_joints, pose,
+                           false, betas, 10, trans, cam_R, cam_t, sample_index, n, scale, offset, verts_out, joints_out, workspace,
+                           workspace_bytes, B, V, stream);
+}
+
+extern "C" int pmce_smpl_forward_rotmat(const float* v_template_t, const float* dirs_t, const float* weights_t, const float* j_template,
+                                        const float* j_shapedirs, const int* parents_host, int n_joints, const float* rotmats,
+                                        const float* betas, int betas_stride, const float* trans, const int* sample_index, int n,
+                                        float scale, const float* offset, float* verts_out, float* joints_out, void* workspace,
+                                        size_t workspace_bytes, int B, int V, hipStream_t stream) {
+  return smpl_forward_impl("smpl_forward_rotmat", v_template_t, dirs_t, weights_t, j_template, j_shapedirs, parents_host, n_joints,
+                           rotmats, true, betas, betas_stride, trans, nullptr, nullptr, sample_index, n, scale, offset, verts_out,
+                           joints_out, workspace, workspace_bytes, B, V, stream);
 }

@@ -585,3 +585,42 @@ def smpl_forward(model, pose, betas, trans, cam_R, cam_t, sample_index, scale, o
                                      P(joints_out), C.c_void_p(workspace.data_ptr()), workspace.numel() * workspace.element_size(), B, V,
                                      _st()), "smpl_forward")
     return verts_out, joints_out
+
+
+def smpl_forward_rotmat(model, rotmats, betas, trans, sample_index, scale, offset, verts_out, joints_out, workspace):
+    """pmce_smpl_forward_rotmat on the current stream, in place on verts_out [B,V,3] and joints_out [B,24,3]: rotmats [B,24,3,3]
+    contiguous, betas [B,10] with unit column stride and any row stride >= 10 (read in place); the rest as for smpl_forward."""
+    lib = _lib.load()
+    B, V = verts_out.shape[0], verts_out.shape[1]
+    vt, dirs, wts, jt, jsd = model.to(verts_out.device)
+    if vt.shape[1] != V:
+        raise _lib.PmceError(f"smpl_forward_rotmat: the model has {vt.shape[1]} vertices, verts_out {V}")
+    par = np.ascontiguousarray(model.parents, dtype=np.int32)
+    assert betas.stride(1) == 1 and betas.is_cuda and betas.dtype == torch.float32
+    if sample_index is not None:
+        assert sample_index.dtype == torch.int32
+    n = B if sample_index is None else int(sample_index.numel())
+    _lib.check(lib.pmce_smpl_forward_rotmat(P(vt), P(dirs), P(wts), P(jt), P(jsd), par.ctypes.data_as(C.POINTER(C.c_int)), len(par),
+                                            P(rotmats), C.c_void_p(betas.data_ptr()), int(betas.stride(0)) if B > 1 else 10, P(trans),
+                                            P(sample_index), n, scale, P(offset), P(verts_out), P(joints_out),
+                                            C.c_void_p(workspace.data_ptr()), workspace.numel() * workspace.element_size(), B, V, _st()),
+               "smpl_forward_rotmat")
+    return verts_out, joints_out
+
+
+def hmr_head(features, q_t, cst, pmi_t, init, state, rotmat, theta):
+    """pmce_hmr_head_f32 on the current stream: features [n,2048], q_t [2048,160], cst [157], pmi_t [157,160] = (P - I)^T + init [n,157] or
+    None + None -> state [n,157], rotmat [n,24,3,3], theta [n,85], written in place."""
+    n = features.shape[0]
+    _lib.check(_lib.load().pmce_hmr_head_f32(P(features), P(q_t), P(cst), P(pmi_t), P(init), n, P(state), P(rotmat), P(theta), _st()),
+               "hmr_head")
+    return state, rotmat, theta
+
+
+def hmr_joints(joints, verts, sel, indptr, indices, data, cam, cam_stride, kp_3d, kp_2d):
+    """pmce_hmr_joints_f32 on the current stream: joints [n,24,3], verts [n,V,3], the joint table (sel int32 [K], CSR int32 / int32 / fp32)
+    on the device, cam = a device tensor whose rows start with the camera at a stride of cam_stride floats -> kp_3d [n,K,3], kp_2d [n,K,2]."""
+    n, V, K = verts.shape[0], verts.shape[1], sel.shape[0]
+    _lib.check(_lib.load().pmce_hmr_joints_f32(P(joints), P(verts), P(sel), P(indptr), P(indices), P(data), C.c_void_p(cam.data_ptr()),
+                                               int(cam_stride), n, K, V, P(kp_3d), P(kp_2d), _st()), "hmr_joints")
+    return kp_3d, kp_2d

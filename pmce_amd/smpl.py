@@ -214,18 +214,8 @@ class SMPL:
         with torch.cuda.device(dev):          # allocations, uploads and the stream the kernels go to: all on the inputs' device
             return self._forward_on(dev, on_dev, pose, shape, trans, gender, cam_R, cam_t, scale, offset)
 
-    def _forward_on(self, dev, on_dev, pose, shape, trans, gender, cam_R, cam_t, scale, offset):
-        import torch
-        from . import ops
-        pose = on_dev(pose.reshape(len(pose), -1) if hasattr(pose, "reshape") else pose, (72,), "pose")
-        B = pose.shape[0]
-        shape, trans = on_dev(shape, (N_SHAPE,), "shape"), on_dev(trans, (3,), "trans")
-        cam_R, cam_t, offset = on_dev(cam_R, (3, 3), "cam_R"), on_dev(cam_t, (3,), "cam_t"), on_dev(offset, (3,), "offset")
-        for name, t in (("shape", shape), ("trans", trans), ("cam_R", cam_R), ("cam_t", cam_t), ("offset", offset)):
-            if t is not None and t.shape[0] != B:
-                raise PmceError(f"{name} holds {t.shape[0]} rows, pose {B}")
-        if (cam_R is None) != (cam_t is None):
-            raise PmceError("cam_R and cam_t go together")
+    def _gender_groups(self, gender, B, dev):
+        """[(model name, int32 device index of its rows or None for all rows)]: one launch pair per gender present."""
         if gender is None or isinstance(gender, str):
             groups = [(_gender_name(gender or self.default_gender), None)]
         else:
@@ -238,11 +228,66 @@ class SMPL:
         for g, _ in groups:
             if g not in self.models:
                 raise PmceError(f"no {g} model loaded (have: {sorted(self.models)})")
+        return groups
+
+    def _forward_on(self, dev, on_dev, pose, shape, trans, gender, cam_R, cam_t, scale, offset):
+        import torch
+        from . import ops
+        pose = on_dev(pose.reshape(len(pose), -1) if hasattr(pose, "reshape") else pose, (72,), "pose")
+        B = pose.shape[0]
+        shape, trans = on_dev(shape, (N_SHAPE,), "shape"), on_dev(trans, (3,), "trans")
+        cam_R, cam_t, offset = on_dev(cam_R, (3, 3), "cam_R"), on_dev(cam_t, (3,), "cam_t"), on_dev(offset, (3,), "offset")
+        for name, t in (("shape", shape), ("trans", trans), ("cam_R", cam_R), ("cam_t", cam_t), ("offset", offset)):
+            if t is not None and t.shape[0] != B:
+                raise PmceError(f"{name} holds {t.shape[0]} rows, pose {B}")
+        if (cam_R is None) != (cam_t is None):
+            raise PmceError("cam_R and cam_t go together")
+        groups = self._gender_groups(gender, B, dev)
         verts = torch.empty(B, self.n_verts, 3, device=dev, dtype=torch.float32)
         joints = torch.empty(B, N_JOINTS, 3, device=dev, dtype=torch.float32)
         ws = torch.empty(ops.smpl_workspace_bytes(B), device=dev, dtype=torch.uint8)
         for g, index in groups:
             ops.smpl_forward(self.models[g], pose, shape, trans, cam_R, cam_t, index, float(scale), offset, verts, joints, ws)
+        return verts, joints
+
+    def forward_rotmat(self, rotmats, shape, trans=None, gender=None, *, scale=1.0, offset=None, sample_index=None):
+        """The layer on rotation matrices (smplx's ``pose2rot=False``, what SPIN's head calls: lib/models/spin.py:184-189): rotmats
+        [B,24,3,3] fp32 device tensor, used as they are (pose map = R[1:] - I); shape [B,10] fp32 on the same device - a row-strided view
+        such as ``state[:, 144:154]`` is read in place -; trans, gender, scale and offset as in ``forward``; there is no camera form.
+        sample_index (int32 device tensor, one gender only): only these rows are computed, the others of the result are left unwritten.
+        -> (verts [B,V,3], joints [B,24,3])."""
+        import torch
+        from . import ops
+        if not isinstance(rotmats, torch.Tensor) or not rotmats.is_cuda or rotmats.dtype != torch.float32 or \
+                tuple(rotmats.shape[1:]) != (N_JOINTS, 3, 3) or rotmats.shape[0] < 1:
+            raise PmceError(f"rotmats must be a float32 device tensor [B >= 1, {N_JOINTS}, 3, 3] (got {getattr(rotmats, 'dtype', None)} "
+                            f"{tuple(getattr(rotmats, 'shape', ()))})")
+        dev, B = rotmats.device, rotmats.shape[0]
+        rotmats = rotmats.contiguous()
+        if not isinstance(shape, torch.Tensor) or shape.device != dev or shape.dtype != torch.float32 or tuple(shape.shape) != (B, N_SHAPE):
+            raise PmceError(f"shape must be a float32 tensor [{B}, {N_SHAPE}] on {dev} (got {tuple(getattr(shape, 'shape', ()))})")
+        if shape.stride(1) != 1 or shape.stride(0) < N_SHAPE:
+            shape = shape.contiguous()
+        with torch.cuda.device(dev):
+            def on_dev(a, name):
+                if a is None:
+                    return None
+                t = a if isinstance(a, torch.Tensor) else upload_async(np.asarray(a, dtype=np.float32), dev)
+                t = t.to(device=dev, dtype=torch.float32).contiguous()
+                if tuple(t.shape) != (B, 3):
+                    raise PmceError(f"{name} must be [{B}, 3] (got {tuple(t.shape)})")
+                return t
+            trans, offset = on_dev(trans, "trans"), on_dev(offset, "offset")
+            groups = self._gender_groups(gender, B, dev)
+            if sample_index is not None:
+                if len(groups) != 1 or sample_index.dtype != torch.int32 or sample_index.device != dev or sample_index.dim() != 1:
+                    raise PmceError("sample_index must be a 1-d int32 tensor on the inputs' device, with one gender for all rows")
+                groups = [(groups[0][0], sample_index.contiguous())]
+            verts = torch.empty(B, self.n_verts, 3, device=dev, dtype=torch.float32)
+            joints = torch.empty(B, N_JOINTS, 3, device=dev, dtype=torch.float32)
+            ws = torch.empty(ops.smpl_workspace_bytes(B), device=dev, dtype=torch.uint8)
+            for g, index in groups:
+                ops.smpl_forward_rotmat(self.models[g], rotmats, shape, trans, index, float(scale), offset, verts, joints, ws)
         return verts, joints
 
     __call__ = forward

@@ -184,6 +184,43 @@ def extractor_spec(prefix: str = "") -> "OrderedDict[str, tuple]":
     return s
 
 
+def hmr_head_spec(prefix: str = "") -> "OrderedDict[str, tuple]":
+    """name -> (shape, half-width, offset) for the linear layers of SPIN's regression head (reference lib/models/spin.py:79-85,
+    217-223): fc1 [1024, 2048 + 157], fc2 [1024, 1024] at 1 / sqrt(fan_in), the three decoders at 0.1 of that (the reference
+    initialises them with gain 0.01: an iteration is a small correction of the state)."""
+    s: OrderedDict = OrderedDict()
+    _lin(s, prefix + "fc1", 1024, FEAT_DIM + 157)
+    _lin(s, prefix + "fc2", 1024, 1024)
+    _lin(s, prefix + "decpose", 144, 1024, scale=0.1)
+    _lin(s, prefix + "decshape", 10, 1024, scale=0.1)
+    _lin(s, prefix + "deccam", 3, 1024, scale=0.1)
+    return s
+
+
+def hmr_head_state_dict(seed: int = 123, as_torch: bool = True, prefix: str = "", feature_gain: float = 1.0):
+    """The head's state dict: ``hmr_head_spec`` materialised plus the three mean-parameter buffers - init_pose [1,144] = the first two
+    columns of 24 seeded rotations (angles in 0.2 .. 2.0 rad about seeded axes) in the reference's 6D order (element 2 r + c of a
+    joint's six is R[r][c]), init_shape [1,10] in +-0.5, init_cam = (0.9, 0, 0).  feature_gain multiplies fc1's 2048 feature columns: the
+    synthetic backbone of ``extractor_spec`` yields features with an rms near 80 where a trained one's are O(1), and a head that is to
+    follow it (a power of two such as 2^-7 keeps the values exact) must not be thrown far from the mean pose by them."""
+    out = make_state_dict(hmr_head_spec(prefix), seed, as_torch=False)
+    out[prefix + "fc1.weight"][:, :FEAT_DIM] *= np.float32(feature_gain)
+    axis = uniform_pm1("hmr.init_axis", 72, seed).astype(np.float64).reshape(24, 3) + 1e-3
+    axis /= np.linalg.norm(axis, axis=1, keepdims=True)
+    angle = 1.1 + 0.9 * uniform_pm1("hmr.init_angle", 24, seed).astype(np.float64)
+    x, y, z = axis.T
+    zero = np.zeros(24)
+    Kx = np.stack([zero, -z, y, z, zero, -x, -y, x, zero], axis=1).reshape(24, 3, 3)
+    R = np.eye(3) + np.sin(angle)[:, None, None] * Kx + (1 - np.cos(angle))[:, None, None] * (Kx @ Kx)
+    out[prefix + "init_pose"] = R[:, :, :2].reshape(1, 144).astype(np.float32)
+    out[prefix + "init_shape"] = (uniform_pm1("hmr.init_shape", 10, seed) * np.float32(0.5)).reshape(1, 10)
+    out[prefix + "init_cam"] = np.array([[0.9, 0.0, 0.0]], dtype=np.float32)
+    if as_torch:
+        import torch
+        out = OrderedDict((k, torch.from_numpy(np.ascontiguousarray(v))) for k, v in out.items())
+    return out
+
+
 def make_state_dict(spec, seed: int = 123, as_torch: bool = True):
     """Materialise a spec. seed 123 = the reference's default --seed (main/test.py:12)."""
     out = OrderedDict()
