@@ -674,6 +674,64 @@ int pmce_hmr_joints_f32(const float* joints, const float* verts, const int* sel,
                         const float* data, const float* cam, int cam_stride, int n, int K, int V, float* kp_3d, float* kp_2d,
                         pmce_stream_t stream);
 
+/* ---------------------------------------------------------------------------------------------------------
+ * The demo's 2D pose network, ViTPose (a ViT backbone + TopdownHeatmapSimpleHead; hyper-parameters of the reference's config
+ * pose_detector/ViTPose_huge_coco_256x192.py): normalised person patches -> keypoint heatmaps (csrc/vit_attention.hip,
+ * csrc/layernorm_rows.hip, csrc/deconv_gather.hip, csrc/vitpose.cpp).  Every nn.Linear is pmce_gemm_nt_split_f16, the patch
+ * embedding pmce_conv2d_split_f16.
+ *
+ * pmce_vit_attention_split_f16: softmax(q k^T hd^-0.5) v per head on qkv[n N][3 C] fp32 (a row = q | k | v, each (heads, hd), as the
+ *   qkv product writes it) -> out_planes[n N][C/16][16 hi | 16 lo*2^11] f16 in the bytes of an fp32 [n N][C], the A operand of proj.
+ *   n images of N tokens, N in 1..192, hd = C / heads = 64 or 80 (pmce_vit_attention_supported tells; anything else PMCE_ERR_ARG).
+ *   The three-product form on the f16 matrix pipe, fp32 accumulation, the exact two-pass softmax on the hardware 2^x; one workgroup
+ *   per (image, head).  Keys at or beyond N are masked to -inf; no row outside [image N, image N + N) is read for an image.  A result
+ *   row depends only on its own image: the same bits whatever n is and wherever the image sits.  A non-finite result sets the
+ *   calling thread's overflow sink.  Buffers 16-byte aligned.
+ * pmce_layernorm_rows_f32: y = x + add[row % add_mod] (add NULL: y = x); out1 = y (optional; may be x);
+ *   out = LayerNorm(y; w, b, eps) as fp32 [rows][C] or, out_split != 0, as planes.  C % 16 == 0, C <= 2048, any rows >= 1;
+ *   two-pass fp32 mean and (biased) variance, one wave per row.
+ * pmce_deconv4x4s2_gather_f32: the gather half of ConvTranspose2d(Cin, Cout, 4, stride 2, padding 1) + BatchNorm + ReLU.  With
+ *   Y[n H W][16 Cout] = X[n H W][Cin] W'^T, W'[(ky, kx, co)][ci] = W[ci][co][ky][kx] s[co] (one pmce_gemm_nt_split_f16 on the packed W'),
+ *   out[n][oy][ox][co] = relu(sum Y[n][iy][ix][(ky, kx, co)] + bias[co]) over the pairs with oy = 2 iy - 1 + ky, ox = 2 ix - 1 + kx, summed
+ *   ky ascending, then kx ascending, the bias last; NHWC [n][2H][2W][Cout] fp32 or planes (out_split).  Cout % 16 == 0.  No atomics.
+ *
+ * pmce_vitpose: the network.  The handle owns the packed weights (one hipMalloc in finalize); the caller owns everything else.
+ *   pmce_vitpose_create(H, W, C, depth, heads, F1, F2, K): image H x W in whole 16 x 16 patches, N = (H/16)(W/16) <= 192 tokens;
+ *     C % 32 == 0; C / heads = 64 or 80; depth >= 1; F1, F2 % 32 == 0 (the deconvolutions' filters); K in 1..64 keypoints;
+ *     PMCE_ERR_ARG names the offending value.
+ *   pmce_vitpose_tensor_count / _tensor_name / _tensor_shape (fills shape4, returns the rank or a negative error): the tensors the
+ *     handle reads, under their state-dict names, all fp32 on the device and 16-byte aligned.  Three of them are prepared by the
+ *     host: "backbone.pos_embed" is the [N][C] table pos_embed[1:] + pos_embed[:1]; "keypoint_head.deconv_layers.{0,3}.weight" are
+ *     the product forms W' [16 Cout][Cin] above (BatchNorm scale folded in fp64, rounded once) and
+ *     "keypoint_head.deconv_layers.{1,4}.bias" the folded BatchNorm biases beta - mean s; "keypoint_head.final_layer.weight" is [K][F2].
+ *   pmce_vitpose_set_tensor: one tensor; it must stay valid until finalize returns.
+ *   pmce_vitpose_finalize_on: packs every matrix with pmce_gemm_pack_split_f16(blocked = 1) / pmce_conv_pack_split_f16 on `stream`
+ *     and waits for it (the one call here that synchronises); PMCE_ERR_ARG names a tensor that was not set.
+ *   pmce_vitpose_workspace_bytes(v, n): 16-byte aligned device memory a forward of n patches needs, n in 1..256 (0 and the error
+ *     string otherwise; the second deconvolution's product result [768 n][16 F2] must stay below the product's 4 GiB operand limit).
+ *   pmce_vitpose_forward: patches [n][3][H][W] through the element strides (sn, sc, sy, sx) -> heat NHWC [n][4 H/16][4 W/16][K];
+ *     feat (optional) NHWC [n][H/16][W/16][C], the backbone's map after last_norm.  Per block: LayerNorm (planes), qkv product,
+ *     attention (planes), proj with the residual, LayerNorm (planes), fc1 with GELU and a pre-split result, fc2 with the residual -
+ *     seven launches; block 0's first LayerNorm also adds the position table.  Then last_norm, product + gather twice, the final
+ *     product.  No synchronisation; patch i's result does not depend on n. */
+typedef struct pmce_vitpose pmce_vitpose;
+int pmce_vit_attention_supported(int N, int C, int heads);
+int pmce_vit_attention_split_f16(const float* qkv, float* out_planes, int n, int N, int C, int heads, pmce_stream_t stream);
+int pmce_layernorm_rows_f32(const float* x, long long rows, int C, const float* add, int add_mod, float* out1, const float* w,
+                            const float* b, float eps, float* out, int out_split, pmce_stream_t stream);
+int pmce_deconv4x4s2_gather_f32(const float* Y, const float* bias, float* out, int n, int H, int W, int Cout, int out_split,
+                                pmce_stream_t stream);
+int pmce_vitpose_create(int H, int W, int C, int depth, int heads, int F1, int F2, int K, pmce_vitpose** out);
+void pmce_vitpose_destroy(pmce_vitpose* v);
+int pmce_vitpose_tensor_count(const pmce_vitpose* v);
+const char* pmce_vitpose_tensor_name(const pmce_vitpose* v, int i);
+int pmce_vitpose_tensor_shape(const pmce_vitpose* v, int i, int* shape4);
+int pmce_vitpose_set_tensor(pmce_vitpose* v, const char* name, const float* dev_ptr);
+int pmce_vitpose_finalize_on(pmce_vitpose* v, pmce_stream_t stream);
+size_t pmce_vitpose_workspace_bytes(const pmce_vitpose* v, int n);
+int pmce_vitpose_forward(const pmce_vitpose* v, const float* patches, long long sn, long long sc, long long sy, long long sx, int n,
+                         float* heat, float* feat, void* workspace, size_t workspace_bytes, pmce_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif

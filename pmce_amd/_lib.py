@@ -140,6 +140,19 @@ PROTOTYPES = {
     "pmce_hmr_head_batch_tile": [],
     "pmce_hmr_head_f32": [_f, _f, _f, _f, _f, _i, _f, _f, _f, _s],
     "pmce_hmr_joints_f32": [_f, _f, _f, _f, _f, _f, _f, _i, _i, _i, _i, _f, _f, _s],
+    "pmce_vit_attention_supported": [_i, _i, _i],
+    "pmce_vit_attention_split_f16": [_f, _f, _i, _i, _i, _i, _s],
+    "pmce_layernorm_rows_f32": [_f, _l, _i, _f, _i, _f, _f, _f, _fl, _f, _i, _s],
+    "pmce_deconv4x4s2_gather_f32": [_f, _f, _f, _i, _i, _i, _i, _i, _s],
+    "pmce_vitpose_create": [_i, _i, _i, _i, _i, _i, _i, _i, C.POINTER(C.c_void_p)],
+    "pmce_vitpose_destroy": [C.c_void_p],
+    "pmce_vitpose_tensor_count": [C.c_void_p],
+    "pmce_vitpose_tensor_name": [C.c_void_p, _i],
+    "pmce_vitpose_tensor_shape": [C.c_void_p, _i, C.POINTER(C.c_int)],
+    "pmce_vitpose_set_tensor": [C.c_void_p, C.c_char_p, _f],
+    "pmce_vitpose_finalize_on": [C.c_void_p, _s],
+    "pmce_vitpose_workspace_bytes": [C.c_void_p, _i],
+    "pmce_vitpose_forward": [C.c_void_p, _f, _l, _l, _l, _l, _i, _f, _f, C.c_void_p, C.c_size_t, _s],
 }
 _RESTYPES = {
     "pmce_last_error_string": C.c_char_p,
@@ -156,6 +169,9 @@ _RESTYPES = {
     "pmce_extractor_destroy": None,
     "pmce_extractor_conv_name": C.c_char_p,
     "pmce_extractor_workspace_bytes": C.c_size_t,
+    "pmce_vitpose_destroy": None,
+    "pmce_vitpose_tensor_name": C.c_char_p,
+    "pmce_vitpose_workspace_bytes": C.c_size_t,
 }
 
 _lib = None

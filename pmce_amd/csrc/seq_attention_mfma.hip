@@ -337,3 +337,6 @@ extern "C" int pmce_seq_attention_split_f16(const float* qkv, float* out, int ns
 // The feature extractor's convolution (the same three-product split on the same matrix instruction) and its pools are compiled here as
 // well: the library's f16 matrix code stays in the translation units it was in.
 #include "conv.hip"
+
+// ViTPose's attention (sequences of up to 192 tokens, heads of 64 or 80 channels; the same split arithmetic and plane layout) likewise.
+#include "vit_attention.hip"

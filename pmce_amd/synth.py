@@ -221,11 +221,56 @@ def hmr_head_state_dict(seed: int = 123, as_torch: bool = True, prefix: str = ""
     return out
 
 
+def vitpose_spec(C: int = 1280, depth: int = 32, heads: int = 16, F1: int = 256, F2: int = 256, K: int = 17, img_size=(256, 192),
+                 prefix: str = "") -> "OrderedDict[str, tuple]":
+    """name -> (shape, half-width, offset) for ViTPose (a ViT backbone without class token + TopdownHeatmapSimpleHead; the reference's
+    config pose_detector/ViTPose_huge_coco_256x192.py): linear layers at 1 / sqrt(fan_in), LayerNorm and BatchNorm as ``_ln`` / ``_conv_bn``
+    draw them, pos_embed in +-0.1, the patch embedding and the deconvolutions He-uniform over the terms of one output.  The q and k rows of
+    every attn.qkv.weight have half-width sqrt(6) / sqrt(C) (a per-row half-width, [3C, 1]): with unit-variance inputs q and k then have
+    variance 2 and the scaled scores a standard deviation of 2 - a softmax that is neither uniform nor one-hot, on which a wrong mask or
+    scale shows.  ``heads`` does not change a shape; it is checked against C."""
+    if heads < 1 or C % heads:
+        raise ValueError(f"C={C} is not a multiple of heads={heads}")
+    n_tok = (img_size[0] // 16) * (img_size[1] // 16)
+    s: OrderedDict = OrderedDict()
+    b = prefix + "backbone."
+    s[b + "pos_embed"] = ((1, n_tok + 1, C), 0.1, 0.0)
+    s[b + "patch_embed.proj.weight"] = ((C, 3, 16, 16), float(np.sqrt(6.0 / (3 * 16 * 16))), 0.0)
+    s[b + "patch_embed.proj.bias"] = ((C,), float(1.0 / np.sqrt(3 * 16 * 16)), 0.0)
+    qk = np.full((3 * C, 1), 1.0 / np.sqrt(C), dtype=np.float32)
+    qk[:2 * C] = np.float32(np.sqrt(6.0) / np.sqrt(C))
+    for i in range(depth):
+        p = f"{b}blocks.{i}"
+        _ln(s, p + ".norm1", C)
+        _lin(s, p + ".attn.qkv", 3 * C, C)
+        s[p + ".attn.qkv.weight"] = ((3 * C, C), qk, 0.0)
+        _lin(s, p + ".attn.proj", C, C)
+        _ln(s, p + ".norm2", C)
+        _lin(s, p + ".mlp.fc1", 4 * C, C)
+        _lin(s, p + ".mlp.fc2", C, 4 * C)
+    _ln(s, b + "last_norm", C)
+    h = prefix + "keypoint_head."
+    for conv, bn, cin, cout in (("0", "1", C, F1), ("3", "4", F1, F2)):
+        # an output pixel of ConvTranspose2d(4, 2, 1) sums 2 x 2 taps of every input channel
+        s[f"{h}deconv_layers.{conv}.weight"] = ((cin, cout, 4, 4), float(np.sqrt(6.0 / (4 * cin))), 0.0)
+        s[f"{h}deconv_layers.{bn}.weight"] = ((cout,), 0.5, 1.0)
+        s[f"{h}deconv_layers.{bn}.bias"] = ((cout,), 0.2, 0.0)
+        s[f"{h}deconv_layers.{bn}.running_mean"] = ((cout,), 0.2, 0.0)
+        s[f"{h}deconv_layers.{bn}.running_var"] = ((cout,), 0.5, 1.0)
+    s[h + "final_layer.weight"] = ((K, F2, 1, 1), float(1.0 / np.sqrt(F2)), 0.0)
+    s[h + "final_layer.bias"] = ((K,), float(1.0 / np.sqrt(F2)), 0.0)
+    return s
+
+
 def make_state_dict(spec, seed: int = 123, as_torch: bool = True):
-    """Materialise a spec. seed 123 = the reference's default --seed (main/test.py:12)."""
+    """Materialise a spec. seed 123 = the reference's default --seed (main/test.py:12).  A half-width may be an array that broadcasts
+    against the tensor's shape (``vitpose_spec``: one per row)."""
     out = OrderedDict()
     for name, (shape, half, off) in spec.items():
         n = int(np.prod(shape))
+        if np.ndim(half):
+            out[name] = uniform_pm1(name, n, seed).reshape(shape) * np.asarray(half, dtype=np.float32) + np.float32(off)
+            continue
         v = uniform_pm1(name, n, seed) * np.float32(half) + np.float32(off)
         out[name] = v.reshape(shape)
     if as_torch:
