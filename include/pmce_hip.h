@@ -590,6 +590,51 @@ int pmce_crop_patches(const unsigned char* frames, int n_frames, int height, int
                       const float* norm_table, float* patch_f32, unsigned char* patch_u8, int* status, pmce_stream_t stream);
 
 /* ---------------------------------------------------------------------------------------------------------
+ * The demo's 2D pose stage around the network (main/run_demo.py:264-286: inference_top_down_pose_model with the config
+ * pose_detector/ViTPose_huge_coco_256x192.py): boxes to patches before pmce_vitpose_forward, heatmaps to keypoints after it
+ * (csrc/pose2d.hip).  The formulas are written from mmpose 0.x's published text (TopDownAffine with use_udp, TopDown.forward_test,
+ * keypoints_from_heatmaps with post_process='default', use_udp, kernel 11) and OpenCV's documented warpAffine rule; no value was
+ * recorded from either.  f32(.) rounds to fp32, everything else is fp64.
+ *
+ * pmce_pose_patches: job n warps frames[frame_index[n]] (uint8 [n_frames][height][width][3]) around boxes[n] (fp64: (x, y, w, h) with
+ * a top-left corner, or (cx, cy, w, h) when centred != 0: x = cx - 0.5 w, y = cy - 0.5 h) to a patch_h x patch_w patch, both in 2..1024.
+ *   _box2cs: a = patch_w / patch_h; cx = f32(x + 0.5 w), cy = f32(y + 0.5 h); if w > a h: h = w / a, else if w < a h: w = h a;
+ *     sx = f32(f32(w / 200) * f32(padding)), wt = f32(sx * 200f); sy, ht likewise from h.  centre_scale[n] = (cx, cy, wt, ht), fp32.
+ *   The UDP map per axis (x shown): k = (patch_w - 1) / (double)wt, m00 = f32(k), m02 = f32(k * (double)f32(0.5f wt - cx)); inverted
+ *     as OpenCV does: D = 1 / (m00 m11), ix = m11 D, iy = m00 D, tx = -ix m02, ty = -iy m12; x_src = ix x_dst + tx.
+ *   From (ix, tx, iy, ty) on, the sampling, norm_table and swap_rb are those of pmce_crop_patches above.
+ *   patch_f32[N][3][patch_h][patch_w]; patch_u8[N][patch_h][patch_w][3] or NULL.  mirror != 0: both hold 2 N patches, row N + n is
+ *     row n mirrored in x (what the flip test feeds the network).
+ *   status[N]: 0 fine; 1 the box is not finite or w <= 0 or h <= 0 (centre_scale[n] is then 0); 2 the source coordinates leave
+ *     +-2^20 px (or the map is not finite); 3 frame_index[n] outside [0, n_frames) in a device table.  A job with status != 0 gets the
+ *     all-border patch and reads no frame.  frame_index_host as for pmce_crop_patches.
+ * One launch, no host wait, integer arithmetic after the map: bit-identical from run to run and whatever N.
+ *
+ * pmce_pose_decode: heatmaps heat[n][K][heat_h][heat_w] read through the element strides (sn, sk, sy, sx) - the network's NHWC
+ * storage as it is - to keypoints[n][K][3] = (x, y, score) in image pixels.  K in 1..64, heat_h and heat_w in 6..4096.
+ *   flip test: with heat_flipped (strides fn, fk, fy, fx; the network's heatmaps of the mirrored patches) and perm_host[K] (the
+ *     flip pairs as a permutation, host memory), A[k][y][x] = f32(f32(h[k][y][x] + hf[perm[k]][y][heat_w - 1 - x]) * 0.5f); else A = h.
+ *   maximum: score = max A[k], (px, py) its first position in row-major order.  score <= 0: the heatmap coordinates are (-1, -1) and
+ *     are not refined (mmpose refines them at an index outside the map; that read is not reproduced).
+ *   DARK (post_dark_udp, kernel 11): blur_host[11] (host memory) = f32(e_i / sum e), e_i = exp(-(i - 5)^2 / 8); B = g (x) g on A with
+ *     BORDER_REFLECT_101, horizontal pass first, taps in ascending order, fp32; L = f32(log(min(max(B, 0.001f), 50f))) (the
+ *     logarithm correctly rounded: taken in fp64), extended by edge replication; at (px, py) in
+ *     fp32 dx = 0.5 (L[x+1] - L[x-1]), dxx = L[x+1] - 2 L + L[x-1], dy, dyy likewise, dxy = 0.5 (L[x+1,y+1] - L[x+1,y] - L[x,y+1] + L + L
+ *     - L[x-1,y] - L[x,y-1] + L[x-1,y-1]); (ox, oy) = (Hess + 2^-23 I)^-1 (dx, dy) in fp64; hx = f32(px - ox), hy = f32(py - oy).
+ *   transform_preds: x = f32(f32(f32(hx * f32(wt / (heat_w - 1))) + cx) - f32(0.5f wt)), y likewise, from centre_scale[n][4].
+ *   status[n] (device, may be NULL) != 0: the image's keypoints are (0, 0, 0).
+ *   coords[n][K][2] (fp32, may be NULL): (hx, hy); argmax[n][K][2] (int32, may be NULL): (px, py), (-1, -1) where score <= 0.
+ * One launch, one workgroup per image, no atomics, no host wait: bit-identical from run to run and whatever n. */
+int pmce_pose_patches(const unsigned char* frames, int n_frames, int height, int width, const int* frame_index_host,
+                      const int* frame_index, const double* boxes, int n_jobs, int centred, double padding, int patch_h, int patch_w,
+                      int swap_rb, int mirror, const float* norm_table, float* patch_f32, unsigned char* patch_u8, float* centre_scale,
+                      int* status, pmce_stream_t stream);
+int pmce_pose_decode(const float* heat, long long sn, long long sk, long long sy, long long sx, const float* heat_flipped,
+                     long long fn, long long fk, long long fy, long long fx, int n, int K, int heat_h, int heat_w, const int* perm_host,
+                     const float* blur_host, const float* centre_scale, const int* status, float* keypoints, float* coords,
+                     int* argmax, pmce_stream_t stream);
+
+/* ---------------------------------------------------------------------------------------------------------
  * The demo's feature extractor (reference lib/models/spin.py:18-143: Bottleneck, the HMR backbone, HMR.feature_extractor, called at
  * main/run_demo.py:247-252,315): convolutions on the f16 matrix pipe as three products of the exact two-term split, fp32 operands and
  * results, NHWC between the layers (csrc/conv.hip, csrc/extractor.cpp).

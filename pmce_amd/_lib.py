@@ -123,6 +123,9 @@ PROTOTYPES = {
                                  C.c_size_t, _i, _i, _s],
     "pmce_crop_boxes": [_f, _i, _i, _d, _f, _f, _f, _s],
     "pmce_crop_patches": [_f, _i, _i, _i, C.POINTER(C.c_int), _f, _f, _i, _d, _i, _i, _f, _f, _f, _f, _s],
+    "pmce_pose_patches": [_f, _i, _i, _i, C.POINTER(C.c_int), _f, _f, _i, _i, _d, _i, _i, _i, _i, _f, _f, _f, _f, _f, _s],
+    "pmce_pose_decode": [_f, _l, _l, _l, _l, _f, _l, _l, _l, _l, _i, _i, _i, _i, C.POINTER(C.c_int), C.POINTER(C.c_float), _f, _f, _f, _f,
+                         _f, _s],
     "pmce_conv_packed_floats": [_i, _i, _i, _i],
     "pmce_conv_pack_split_f16": [_f, _i, _i, _i, _i, _f, _f, _s],
     "pmce_conv2d_split_f16": [_f, _l, _l, _l, _l, _i, _i, _i, _i, _f, _f, _f, _f, _f, _i, _i, _i, _i, _i, _i, _s],

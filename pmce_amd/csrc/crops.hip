@@ -13,15 +13,17 @@
 // source rows, their validity, the vertical fraction) is computed once per row and is wave-uniform.  What depends on the column alone
 // (tap column, horizontal fraction) is computed once per lane and kept across the rows of the workgroup's band.  The 3-byte source pixels
 // are unaligned and read with byte loads (served by L1 / L2: two source rows per output row, re-read by the neighbouring rows);
-// DESIGN.md section 8 says what else was considered.
+// DESIGN.md section 8 says what else was considered.  The sampling body is patch_sampler.hpp, shared with the 2D pose stage's patches
+// (pose2d.hip).
 #include "common.hpp"
+#include "patch_sampler.hpp"
 
 namespace {
 
-constexpr int MAX_SIDE = 1024;       // S
-constexpr int MAX_DIM = 16384;       // frame width / height
-constexpr int ROWS_PER_BLOCK = 32;   // output rows of one workgroup: 8 per wave
-constexpr double COORD_LIMIT = 1048576.0;   // 2^20 px
+using patch_sampler::MAX_SIDE;         // S
+using patch_sampler::MAX_DIM;          // frame width / height
+using patch_sampler::ROWS_PER_BLOCK;   // output rows of one workgroup: 8 per wave
+using patch_sampler::in_reach;         // |v| <= 2^20 px
 
 // ---------------------------------------------------------------------------------------------------------------------------------------
 // boxes
@@ -125,7 +127,6 @@ __device__ __forceinline__ void axis_map(double c, double size, double scale, in
   i = d / hs;
   t = c0 - hs * i;
 }
-__device__ __forceinline__ bool in_reach(double v) { return fabs(v) <= COORD_LIMIT; }   // false for NaN and inf
 
 // grid (N, bands of ROWS_PER_BLOCK rows).  table[3][256]: the normalised value of byte v in output channel c.
 template <bool ALIGNED>
@@ -139,8 +140,6 @@ __global__ __launch_bounds__(256) void crop_patches_kernel(const unsigned char* 
   for (int i = threadIdx.x; i < 3 * 256; i += 256) lut[i] = table[i];
   __syncthreads();
   const int n = blockIdx.x;
-  const int lane = threadIdx.x & 63;
-  const int wave = __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6));
   const int y_begin = blockIdx.y * ROWS_PER_BLOCK, y_end = min(y_begin + ROWS_PER_BLOCK, S);
 
   const double bx = boxes[4ll * n], by = boxes[4ll * n + 1], bw = boxes[4ll * n + 2], bh = boxes[4ll * n + 3];
@@ -163,80 +162,8 @@ __global__ __launch_bounds__(256) void crop_patches_kernel(const unsigned char* 
   float* of = out_f32 + (size_t)n * 3 * plane;
   unsigned char* ou = out_u8 ? out_u8 + (size_t)n * 3 * plane : nullptr;
   const unsigned char* frame = frames + (live ? (size_t)fi * H * W * 3 : 0);
-  const long long X0 = live ? (long long)rint(tx * 1024.0) + 16 : 0;
-  const int c_r = swap_rb ? 2 : 0, c_b = swap_rb ? 0 : 2;     // source byte of output channels 0 and 2
-  const int quads = (S + 3) >> 2;
-
-  for (int q = lane; q < quads; q += 64) {
-    const int x0 = q * 4;
-    int Xs[4];                                   // per column: (tap column << 5) | fraction
-#pragma unroll
-    for (int e = 0; e < 4; ++e) Xs[e] = live ? (int)((X0 + (long long)rint(ix * (double)(x0 + e) * 1024.0)) >> 5) : 0;
-    for (int y = y_begin + wave; y < y_end; y += 4) {
-      float r[3][4];
-      unsigned char u[4][3];
-      if (live) {
-        const long long Yl = ((long long)rint((iy * (double)y + ty) * 1024.0) + 16) >> 5;
-        const int Y = __builtin_amdgcn_readfirstlane((int)Yl);
-        const int row = Y >> 5, b = Y & 31;
-        const bool v0 = row >= 0 && row < H, v1 = row + 1 >= 0 && row + 1 < H;
-        const unsigned char* p0 = frame + (size_t)min(max(row, 0), H - 1) * W * 3;
-        const unsigned char* p1 = frame + (size_t)min(max(row + 1, 0), H - 1) * W * 3;
-        const int wb0 = v0 ? 32 - b : 0, wb1 = v1 ? b : 0;      // a row outside the frame contributes nothing
-#pragma unroll
-        for (int e = 0; e < 4; ++e) {
-          const int col = Xs[e] >> 5, a = Xs[e] & 31;
-          const int o0 = min(max(col, 0), W - 1) * 3, o1 = min(max(col + 1, 0), W - 1) * 3;
-          const int wa0 = (col >= 0 && col < W) ? 32 - a : 0, wa1 = (col + 1 >= 0 && col + 1 < W) ? a : 0;
-          const int w00 = wb0 * wa0 * 32, w01 = wb0 * wa1 * 32, w10 = wb1 * wa0 * 32, w11 = wb1 * wa1 * 32;
-#pragma unroll
-          for (int c = 0; c < 3; ++c) {
-            const int sc = c == 0 ? c_r : (c == 2 ? c_b : 1);
-            const int sum = w00 * p0[o0 + sc] + w01 * p0[o1 + sc] + w10 * p1[o0 + sc] + w11 * p1[o1 + sc];
-            const int v = (sum + 16384) >> 15;
-            u[e][c] = (unsigned char)v;
-            r[c][e] = lut[c * 256 + v];
-          }
-        }
-      } else {
-#pragma unroll
-        for (int e = 0; e < 4; ++e)
-#pragma unroll
-          for (int c = 0; c < 3; ++c) {
-            u[e][c] = 0;
-            r[c][e] = lut[c * 256];
-          }
-      }
-      const size_t o = (size_t)y * S + x0;
-      if (ALIGNED) {                             // S % 4 == 0: every quad is whole and 16-byte aligned
-#pragma unroll
-        for (int c = 0; c < 3; ++c) *reinterpret_cast<f32x4*>(of + c * plane + o) = f32x4{r[c][0], r[c][1], r[c][2], r[c][3]};
-        if (ou) {
-          uint32_t wds[3];
-#pragma unroll
-          for (int k = 0; k < 3; ++k) {
-            uint32_t v = 0;
-#pragma unroll
-            for (int j = 0; j < 4; ++j) v |= (uint32_t)u[(4 * k + j) / 3][(4 * k + j) % 3] << (8 * j);
-            wds[k] = v;
-          }
-          uint32_t* d = reinterpret_cast<uint32_t*>(ou + o * 3);
-          d[0] = wds[0];
-          d[1] = wds[1];
-          d[2] = wds[2];
-        }
-      } else {
-        const int ne = min(4, S - x0);
-        for (int e = 0; e < ne; ++e) {
-#pragma unroll
-          for (int c = 0; c < 3; ++c) {
-            of[c * plane + o + e] = r[c][e];
-            if (ou) ou[(o + e) * 3 + c] = u[e][c];
-          }
-        }
-      }
-    }
-  }
+  patch_sampler::sample_rows<ALIGNED, false>(frame, H, W, live, ix, tx, iy, ty, S, S, y_begin, y_end, swap_rb, lut, of, ou, nullptr,
+                                             nullptr);
 }
 
 }  // namespace

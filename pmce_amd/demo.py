@@ -6,6 +6,7 @@ in, what the demo saves per person out - ``pred_cam``, ``mesh``, ``bboxes`` (``f
     outs = demo.run_tracklets(model, [(kp_a, feat_a), (kp_b, feat_b)], img_wh=(1920, 1080))     # batches filled across people
     video = demo.render_tracklets(outs, frames_u8, (1920, 1080), frame_ids=ids, renderer=render.Renderer(faces, (1920, 1080)))
     outs = demo.run_video(model, frames_u8, [(kp_a[N,17,3], ids_a), (kp_b, ids_b)], extractor, img_wh=(1920, 1080))   # crops included
+    tracklets = demo.pose_tracklets(frames_u8, [(boxes_a[N,4], ids_a), (boxes_b, ids_b)], pose2d.TopDownPose(vitpose_net))   # boxes -> run_video's tracklets
 
 Per frame k the demo builds one window (``streaming.demo_window_list``), prepares the fit target from the window's middle frame
 (csrc/demo_prep.hip: add_pelvis_and_neck, get_bbox, process_bbox, j2d_processing), runs the model on the window and fits the
@@ -252,6 +253,36 @@ def crop_tracklets(frames, tracklets, scale: float = 1.1, size: int = 224, chann
     if return_raw:
         res["raw"] = out[1]
     return res
+
+
+@torch.no_grad()
+def pose_tracklets(frames, tracklets, pose):
+    """The reference's 2D pose stage for every person of a video (main/run_demo.py:264-286), on the device: frames uint8 [F,H,W,3],
+    tracklets = [(boxes[N_i,4] as the tracker gives them - ``pose.box_format`` -, frame_ids[N_i]), ...], ``pose`` a
+    ``pose2d.TopDownPose`` -> [(keypoints fp32 [N_i,K,3] = (x, y, score) on the device, frame_ids int64 [N_i] on the host), ...]: what
+    ``run_video`` takes as its tracklets.  All persons go through ONE ``pose`` call (its chunks are filled across persons); there is no
+    host wait here.  A job the warp refused (a box that is not finite, or empty) has the keypoints (0, 0, 0): an unusable frame to
+    ``crops.tracklet_boxes``."""
+    F = int(frames.shape[0]) if getattr(frames, "ndim", 0) == 4 else -1
+    ids, boxes = [], []
+    for i, (bx, fid) in enumerate(tracklets):
+        bs = tuple(getattr(bx, "shape", ()))
+        if len(bs) != 2 or bs[1] != 4 or "float" not in str(getattr(bx, "dtype", "")):
+            raise ValueError(f"tracklet {i}: boxes must be floating point [N, 4] (got {getattr(bx, 'dtype', None)} {bs})")
+        fid = np.asarray(fid.cpu() if isinstance(fid, torch.Tensor) else fid)
+        if fid.shape != (bs[0],) or not np.issubdtype(fid.dtype, np.integer):
+            raise ValueError(f"tracklet {i}: frame_ids must be an integer array [N = {bs[0]}] (got {fid.dtype} {fid.shape})")
+        if F >= 0 and fid.size and (fid.min() < 0 or fid.max() >= F):
+            raise ValueError(f"tracklet {i}: frame_ids run {int(fid.min())}..{int(fid.max())}, there are {F} frames")
+        ids.append(fid.astype(np.int64))
+        boxes.append(torch.as_tensor(bx).to(torch.float64))
+    if not ids:
+        return []
+    if len({b.device for b in boxes}) > 1:
+        raise ValueError("the tracklets' boxes must all be on one device")
+    kp, _ = pose(frames, np.concatenate(ids).astype(np.int32), torch.cat(boxes))
+    off = np.concatenate([[0], np.cumsum([len(f) for f in ids])])
+    return [(kp[int(off[i]):int(off[i + 1])], ids[i]) for i in range(len(ids))]
 
 
 @torch.no_grad()

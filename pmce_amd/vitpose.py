@@ -7,7 +7,8 @@ pose_detector/ViTPose_huge_coco_256x192.py - from normalised person patches [n,3
     heat = net(patches)                                                      # fp32 [n,K,4 Hp,4 Wp] on the patches' device
     heat, feat = net.forward(patches, return_features=True)                  # + the backbone's map [n,C,Hp,Wp] after last_norm
 
-The box-to-patch warp, the flip test and the decoding of heatmaps to keypoints are not part of this module.  Eval-mode BatchNorm is
+The box-to-patch warp, the flip test and the decoding of heatmaps to keypoints are not part of this module: ``pmce_amd.pose2d`` has
+them, and ``pose2d.TopDownPose(net)`` is the stage from tracker boxes to keypoints around this network.  Eval-mode BatchNorm is
 folded into each deconvolution on the host in fp64 (``fold_bn_deconv``), a deconvolution is one product and a gather
 (``deconv_weight_as_product``, ``deconv_gather``).  The operators are also bound one by one (``vit_attention``, ``layernorm_rows``,
 ``deconv_gather``).  There is no fallback: without the library's kernels a call raises.
