@@ -777,6 +777,72 @@ size_t pmce_vitpose_workspace_bytes(const pmce_vitpose* v, int n);
 int pmce_vitpose_forward(const pmce_vitpose* v, const float* patches, long long sn, long long sc, long long sy, long long sx, int n,
                          float* heat, float* feat, void* workspace, size_t workspace_bytes, pmce_stream_t stream);
 
+/* ---------------------------------------------------------------------------------------------------------
+ * The tracker's detector: YOLOv3 as the reference calls it (main/run_demo.py:199-215: MPT(detector_type='yolo', yolo_img_size=416)),
+ * video frames -> box predictions (csrc/conv.hip, csrc/yolo.hip, csrc/yolo.cpp).  The structure is the published yolov3.cfg's and that of
+ * the PyTorch-YOLOv3 lineage; no tensor was recorded from the yolov3 or multi_person_tracker packages.  Non-maximum suppression, SORT and
+ * the tracklet records are not here.
+ *
+ * pmce_conv2d_act_split_f16: pmce_conv2d_split_f16 with
+ *     v = wscale[co] * sum_k (...) + bias[co];   res_after_act == 0: out = act(v + R);   res_after_act == 1: out = act(v) + R
+ *   act = 0 none, 1 ReLU, 2 leaky (v < 0 ? v * slope : v, slope in [0, 1]); row m of the result is out + m * out_pitch and of the residual
+ *   R + m * res_pitch (floats; both >= Cout): a convolution writes into, and reads its residual from, a channel slice of a wider NHWC
+ *   buffer.  The input is addressed by its four strides as before (a slice: sx = the pitch).  With act = 1, res_after_act = 0 and both
+ *   pitches = Cout it is pmce_conv2d_split_f16 (relu = 1) to the bit - both are one launcher.  Same summation order: bit-identical whatever n.
+ * pmce_upsample2x_nhwc_f32: nearest x2: out[i][2 y + dy][2 x + dx][c] = x[i][y][x][c], c < C; pixel rows of in_pitch / out_pitch floats
+ *   (`out` points at the slice's first channel); C, the pitches % 4 == 0 and 16-byte aligned pointers: 16-byte accesses.
+ * pmce_yolo_decode_f32: the three detection maps (NHWC [n][g_s][g_s][pitch_s], channel a (5 + nc) + c, a < 3) -> out[n][R][5 + nc],
+ *   R = 3 (g_0^2 + g_1^2 + g_2^2), rows ordered scale, anchor, gy, gx.  With stride = (float)S / g, anchors_host[s][a] = (w, h) in input
+ *   pixels and sigmoid, exp correctly rounded to fp32, every other operation one fp32 rounding (no contraction):
+ *     x = (sigmoid(t0) + gx) * stride, y = (sigmoid(t1) + gy) * stride, w = (exp(t2) * (aw / stride)) * stride, h alike,
+ *     conf = sigmoid(t4), cls_c = sigmoid(t5+c).     Boxes are (cx, cy, w, h) in pixels of the S x S input.  nc in 1..255, any g in 1..2048.
+ *   pitches_host[3], grids_host[3], anchors_host[3][3][2] are host memory.  One launch, a thread per output float, no atomics.
+ * pmce_letterbox_u8_f32: job j pads frames[frame_index[j]] (uint8 [n_frames][height][width][3]) to a square of side L = max(height,
+ *   width) - d = |height - width|, d / 2 (rounded down) before and the rest after - and samples it at S x S as
+ *   F.interpolate(mode="nearest") does: src = min((int)floorf(dst * scale), L - 1), scale = (float)L / S in fp32.
+ *   out[j][c][y][x] = table[byte] (table[256], device: the caller's fp32 byte / 255) or pad_value outside the frame; swap_rb != 0: output
+ *   channel c is the frame's byte 2 - c.  frame_index_host (may be NULL) is validated here; an entry of a device-only table outside
+ *   [0, n_frames) gives the all-pad image and reads no frame.  One launch for all jobs.
+ *
+ * pmce_yolo: the network.  The handle owns the packed weights (one hipMalloc in finalize); the caller owns everything else.
+ *   pmce_yolo_create: table[n_layers][9] = (kind, filters, size, stride, batch_normalize, leaky, source 0, source 1, anchor mask), one row
+ *     per cfg section; kind 0 convolutional (pad = (size - 1) / 2), 1 shortcut (source 0 = the absolute index added to the layer before),
+ *     2 route (absolute indices; source 1 = -1 for one source), 3 upsample (stride 2), 4 yolo (mask = bits of its three anchors).
+ *     anchors18 = nine (w, h) in input pixels.  Supported: a shortcut right after the convolution it completes (out = from +
+ *     act(conv): one launch); a two-source route [the upsample before it, a convolution's or shortcut's map]; three yolo layers, each
+ *     after a linear convolution of 3 (5 + num_classes) filters; body convolutions with filters % 4 == 0.  PMCE_ERR_ARG names the layer.
+ *   pmce_yolo_layer_plan: plan8 = (channels, input side / map side, buffer id (-1 none, -2 the caller's detection map), channel offset,
+ *     pitch, buffer offset, buffer size, step of the buffer's last reader); offsets and sizes in units of n (S / 32)^2 floats.
+ *   pmce_yolo_conv_shape (Cout, Cin, k, k) / pmce_yolo_set_conv: by layer index; folded OIHW weight and bias (device, fp32), valid until
+ *     finalize returns.  pmce_yolo_finalize_on packs on `stream` and waits for it (the one call here that synchronises).
+ *   pmce_yolo_workspace_bytes(y, n, S): n in 1..1024, S a multiple of 32 in 32..1024 (0 and the error string otherwise).
+ *   pmce_yolo_forward: images [n][3][S][S] through the element strides -> map0..2 (NHWC [n][g][g][3 (5 + nc)], the raw detection maps in
+ *     the order of the yolo layers) and rows[n][R][5 + nc] (NULL: no decoding).  One launch per convolution (a shortcut is an epilogue),
+ *     per upsample and for the decoding, on `stream`, no synchronisation; image i's result does not depend on n. */
+typedef struct pmce_yolo pmce_yolo;
+int pmce_conv2d_act_split_f16(const float* x, long long sn, long long sc, long long sy, long long sx, int n, int Cin, int H, int W,
+                              const float* Wp, const float* wscale, const float* bias, const float* R, long long res_pitch, float* out,
+                              long long out_pitch, int Cout, int KH, int KW, int stride, int pad, int act, float slope, int res_after_act,
+                              pmce_stream_t stream);
+int pmce_upsample2x_nhwc_f32(const float* x, long long in_pitch, float* out, long long out_pitch, int n, int H, int W, int C,
+                             pmce_stream_t stream);
+int pmce_yolo_decode_f32(const float* map0, const float* map1, const float* map2, const long long* pitches_host, const int* grids_host,
+                         const float* anchors_host, int n, int nc, int S, float* out, pmce_stream_t stream);
+int pmce_letterbox_u8_f32(const unsigned char* frames, int n_frames, int height, int width, const int* frame_index_host,
+                          const int* frame_index, int n_jobs, int S, int swap_rb, const float* table, float pad_value, float* out,
+                          pmce_stream_t stream);
+int pmce_yolo_create(const int* table, int n_layers, const float* anchors18, int num_classes, pmce_yolo** out);
+void pmce_yolo_destroy(pmce_yolo* y);
+int pmce_yolo_layer_count(const pmce_yolo* y);
+int pmce_yolo_conv_shape(const pmce_yolo* y, int i, int* shape4);
+int pmce_yolo_layer_plan(const pmce_yolo* y, int i, long long* plan8);
+long long pmce_yolo_workspace_units(const pmce_yolo* y);
+int pmce_yolo_set_conv(pmce_yolo* y, int layer, const float* folded_weight, const float* folded_bias);
+int pmce_yolo_finalize_on(pmce_yolo* y, pmce_stream_t stream);
+size_t pmce_yolo_workspace_bytes(const pmce_yolo* y, int n, int S);
+int pmce_yolo_forward(const pmce_yolo* y, const float* images, long long sn, long long sc, long long sy, long long sx, int n, int S,
+                      float* map0, float* map1, float* map2, float* rows, void* workspace, size_t workspace_bytes, pmce_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif

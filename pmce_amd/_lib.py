@@ -156,6 +156,20 @@ PROTOTYPES = {
     "pmce_vitpose_finalize_on": [C.c_void_p, _s],
     "pmce_vitpose_workspace_bytes": [C.c_void_p, _i],
     "pmce_vitpose_forward": [C.c_void_p, _f, _l, _l, _l, _l, _i, _f, _f, C.c_void_p, C.c_size_t, _s],
+    "pmce_conv2d_act_split_f16": [_f, _l, _l, _l, _l, _i, _i, _i, _i, _f, _f, _f, _f, _l, _f, _l, _i, _i, _i, _i, _i, _i, _fl, _i, _s],
+    "pmce_upsample2x_nhwc_f32": [_f, _l, _f, _l, _i, _i, _i, _i, _s],
+    "pmce_yolo_decode_f32": [_f, _f, _f, C.POINTER(C.c_longlong), C.POINTER(C.c_int), C.POINTER(C.c_float), _i, _i, _i, _f, _s],
+    "pmce_letterbox_u8_f32": [_f, _i, _i, _i, C.POINTER(C.c_int), _f, _i, _i, _i, _f, _fl, _f, _s],
+    "pmce_yolo_create": [C.POINTER(C.c_int), _i, C.POINTER(C.c_float), _i, C.POINTER(C.c_void_p)],
+    "pmce_yolo_destroy": [C.c_void_p],
+    "pmce_yolo_layer_count": [C.c_void_p],
+    "pmce_yolo_conv_shape": [C.c_void_p, _i, C.POINTER(C.c_int)],
+    "pmce_yolo_layer_plan": [C.c_void_p, _i, C.POINTER(C.c_longlong)],
+    "pmce_yolo_workspace_units": [C.c_void_p],
+    "pmce_yolo_set_conv": [C.c_void_p, _i, _f, _f],
+    "pmce_yolo_finalize_on": [C.c_void_p, _s],
+    "pmce_yolo_workspace_bytes": [C.c_void_p, _i, _i],
+    "pmce_yolo_forward": [C.c_void_p, _f, _l, _l, _l, _l, _i, _i, _f, _f, _f, _f, C.c_void_p, C.c_size_t, _s],
 }
 _RESTYPES = {
     "pmce_last_error_string": C.c_char_p,
@@ -175,6 +189,9 @@ _RESTYPES = {
     "pmce_vitpose_destroy": None,
     "pmce_vitpose_tensor_name": C.c_char_p,
     "pmce_vitpose_workspace_bytes": C.c_size_t,
+    "pmce_yolo_destroy": None,
+    "pmce_yolo_workspace_units": C.c_longlong,
+    "pmce_yolo_workspace_bytes": C.c_size_t,
 }
 
 _lib = None

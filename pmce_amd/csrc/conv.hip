@@ -20,6 +20,9 @@
 //   FAST (channel stride 1, Cin % 16 == 0, 16-byte aligned rows): a k-tile lies inside one tap and is 64 contiguous bytes per pixel:
 //        one 16-byte load per thread and row, the tap arithmetic is scalar.
 //   generic (the stem, Cin = 3): every element is its own predicated load; k -> (ky, kx, c) by division.  3 % of the network's work.
+// Epilogue: v = 2^-s(n) acc + bias[n]; then act(v + R) (the bottleneck's order) or act(v) + R (darknet's shortcut), act = none, ReLU or
+// leaky with a slope; the result's and the residual's rows have their own pitches, so both may be channel slices of wider NHWC buffers
+// (the detector's concatenations are written in place).  pmce_conv2d_split_f16 is the case (ReLU or none, R first, pitch = Cout).
 // Order of summation: an output element is ONE accumulator register that takes the k-tiles 0, 1, 2, ... in turn, three matrix
 // instructions each in a fixed order, whatever the batch, the tile it falls into or its place in the tile: results are bit-identical
 // whatever n is (tests/test_gpu_conv.py T2).
@@ -34,15 +37,19 @@ struct ConvParams {
   const float* Wp;      // packed planes (see above)
   const float* wscale;  // [Cout] 2^-s(n)
   const float* bias;    // [Cout] or null
-  const float* R;       // residual [M][Cout] or null
-  float* out;           // [M][Cout]
+  const float* R;       // residual, row m at R + m ldr, or null
+  float* out;           // row m at out + m ldo
+  long long ldo, ldr;   // row pitches in floats (>= Cout): a channel slice of a wider NHWC buffer
   int M, N, K, KT;      // M = n OH OW, N = Cout, K = KH KW Cin, KT = Kp / 16
   int ntn;              // column tiles
-  int relu;
+  int act;              // CONV_ACT_NONE / _RELU / _LEAKY
+  float slope;          // of the leaky activation
+  int res_after;        // 0: act(v + R) (ResNet's bottleneck); 1: act(v) + R (darknet's shortcut)
   unsigned* oflow;      // set to 1 when a result is not finite; may be null
 };
 
 constexpr int CONV_BM = 128;
+constexpr int CONV_ACT_NONE = 0, CONV_ACT_RELU = 1, CONV_ACT_LEAKY = 2;
 
 template <int NT, bool FAST>
 __global__ __launch_bounds__(256) void conv_split_kernel(ConvParams p) {
@@ -202,10 +209,13 @@ __global__ __launch_bounds__(256) void conv_split_kernel(ConvParams p) {
         if (m < p.M) {
           float v = acc[j][r] * w_down;  // a power of two: exact
           v = v + b;
-          if (p.R) v = v + p.R[(size_t)m * p.N + n];
-          if (p.relu) v = v < 0.f ? 0.f : v;  // (NaN stays NaN)
+          const float res = p.R ? p.R[(size_t)m * p.ldr + n] : 0.f;
+          if (p.R && !p.res_after) v = v + res;
+          if (p.act == CONV_ACT_RELU) v = v < 0.f ? 0.f : v;  // (NaN stays NaN)
+          if (p.act == CONV_ACT_LEAKY) v = v < 0.f ? v * p.slope : v;
+          if (p.R && p.res_after) v = v + res;
           bad = bad || nonfinite(v);
-          p.out[(size_t)m * p.N + n] = v;
+          p.out[(size_t)m * p.ldo + n] = v;
         }
       }
     }
@@ -315,9 +325,12 @@ extern "C" int pmce_conv_pack_split_f16(const float* W_oihw, int Cout, int Cin, 
   return pmce_check_launch("conv_pack_split_f16");
 }
 
-extern "C" int pmce_conv2d_split_f16(const float* x, long long sn, long long sc, long long sy, long long sx, int n, int Cin, int H, int W,
-                                     const float* Wp, const float* wscale, const float* bias, const float* R, float* out, int Cout, int KH,
-                                     int KW, int stride, int pad, int relu, hipStream_t stream) {
+namespace {
+
+// The one launcher behind both entries.
+int conv2d_launch(const float* x, long long sn, long long sc, long long sy, long long sx, int n, int Cin, int H, int W, const float* Wp,
+                  const float* wscale, const float* bias, const float* R, long long ldr, float* out, long long ldo, int Cout, int KH, int KW,
+                  int stride, int pad, int act, float slope, int res_after, hipStream_t stream) {
   PMCE_REQUIRE(x && Wp && wscale && out, "conv2d_split_f16: null pointer");
   PMCE_REQUIRE(n >= 1 && Cin >= 1 && H >= 1 && W >= 1 && Cout >= 1 && KH >= 1 && KW >= 1 && stride >= 1 && pad >= 0 && pad < KH && pad < KW,
                "conv2d_split_f16: need n, Cin, H, W, Cout, KH, KW, stride >= 1 and 0 <= pad < KH, KW (n=%d Cin=%d H=%d W=%d Cout=%d KH=%d KW=%d "
@@ -330,17 +343,41 @@ extern "C" int pmce_conv2d_split_f16(const float* x, long long sn, long long sc,
   // the largest element offset a load can form, and the output's extent, stay inside 2^40 elements; row indices are ints
   PMCE_REQUIRE(M < (1ll << 30) && (n - 1) * sn + (Cin - 1) * sc + (H - 1) * sy + (W - 1) * sx < (1ll << 40),
                "conv2d_split_f16: the problem is too large (M = %lld rows; split the batch)", M);
+  PMCE_REQUIRE(ldo >= Cout && ldo < (1ll << 24) && (!R || (ldr >= Cout && ldr < (1ll << 24))),
+               "conv2d_split_f16: the row pitches must be in Cout..2^24 (Cout=%d out pitch=%lld residual pitch=%lld)", Cout, ldo, ldr);
   ConvParams p{};
   p.X = x; p.sn = sn; p.sc = sc; p.sy = sy; p.sx = sx;
   p.H = H; p.W = W; p.Cin = Cin; p.OH = OH; p.OW = OW; p.KH = KH; p.KW = KW; p.stride = stride; p.pad = pad;
-  p.Wp = Wp; p.wscale = wscale; p.bias = bias; p.R = R; p.out = out;
+  p.Wp = Wp; p.wscale = wscale; p.bias = bias; p.R = R; p.out = out; p.ldo = ldo; p.ldr = R ? ldr : 0;
   p.M = (int)M; p.N = Cout; p.K = Cin * KH * KW; p.KT = (p.K + 31) / 32 * 2;
-  p.relu = relu ? 1 : 0;
+  p.act = act; p.slope = slope; p.res_after = res_after;
   p.oflow = pmce_overflow_sink();
   const bool fast = sc == 1 && Cin % 16 == 0 && sn % 4 == 0 && sy % 4 == 0 && sx % 4 == 0 && (reinterpret_cast<uintptr_t>(x) & 15) == 0;
   p.ntn = (Cout + 63) / 64;  // one tile shape for every layer and every batch
   PMCE_REQUIRE((long long)((M + CONV_BM - 1) / CONV_BM) * p.ntn < (1ll << 31), "conv2d_split_f16: too many tiles");
   return fast ? launch_conv<2, true>(p, stream) : launch_conv<2, false>(p, stream);
+}
+
+}  // namespace
+
+extern "C" int pmce_conv2d_split_f16(const float* x, long long sn, long long sc, long long sy, long long sx, int n, int Cin, int H, int W,
+                                     const float* Wp, const float* wscale, const float* bias, const float* R, float* out, int Cout, int KH,
+                                     int KW, int stride, int pad, int relu, hipStream_t stream) {
+  return conv2d_launch(x, sn, sc, sy, sx, n, Cin, H, W, Wp, wscale, bias, R, Cout, out, Cout, Cout, KH, KW, stride, pad,
+                       relu ? CONV_ACT_RELU : CONV_ACT_NONE, 0.f, 0, stream);
+}
+
+extern "C" int pmce_conv2d_act_split_f16(const float* x, long long sn, long long sc, long long sy, long long sx, int n, int Cin, int H, int W,
+                                         const float* Wp, const float* wscale, const float* bias, const float* R, long long res_pitch,
+                                         float* out, long long out_pitch, int Cout, int KH, int KW, int stride, int pad, int act, float slope,
+                                         int res_after_act, hipStream_t stream) {
+  PMCE_REQUIRE(act == CONV_ACT_NONE || act == CONV_ACT_RELU || act == CONV_ACT_LEAKY,
+               "conv2d_act_split_f16: act must be 0 (none), 1 (ReLU) or 2 (leaky) (got %d)", act);
+  PMCE_REQUIRE(act != CONV_ACT_LEAKY || (slope == slope && slope >= 0.f && slope <= 1.f),
+               "conv2d_act_split_f16: the leaky slope must be in [0, 1] (got %g)", (double)slope);
+  PMCE_REQUIRE(res_after_act == 0 || res_after_act == 1, "conv2d_act_split_f16: res_after_act must be 0 or 1 (got %d)", res_after_act);
+  return conv2d_launch(x, sn, sc, sy, sx, n, Cin, H, W, Wp, wscale, bias, R, res_pitch, out, out_pitch, Cout, KH, KW, stride, pad, act,
+                       act == CONV_ACT_LEAKY ? slope : 0.f, res_after_act, stream);
 }
 
 extern "C" int pmce_maxpool3x3s2_nhwc_f32(const float* x, float* y, int n, int H, int W, int C, hipStream_t stream) {

@@ -340,3 +340,6 @@ extern "C" int pmce_seq_attention_split_f16(const float* qkv, float* out, int ns
 
 // ViTPose's attention (sequences of up to 192 tokens, heads of 64 or 80 channels; the same split arithmetic and plane layout) likewise.
 #include "vit_attention.hip"
+
+// The detector's letterbox, upsample and decode kernels (no matrix code; they ride along with the convolution they surround).
+#include "yolo.hip"
