@@ -780,8 +780,8 @@ int pmce_vitpose_forward(const pmce_vitpose* v, const float* patches, long long 
 /* ---------------------------------------------------------------------------------------------------------
  * The tracker's detector: YOLOv3 as the reference calls it (main/run_demo.py:199-215: MPT(detector_type='yolo', yolo_img_size=416)),
  * video frames -> box predictions (csrc/conv.hip, csrc/yolo.hip, csrc/yolo.cpp).  The structure is the published yolov3.cfg's and that of
- * the PyTorch-YOLOv3 lineage; no tensor was recorded from the yolov3 or multi_person_tracker packages.  Non-maximum suppression, SORT and
- * the tracklet records are not here.
+ * the PyTorch-YOLOv3 lineage; no tensor was recorded from the yolov3 or multi_person_tracker packages.  Non-maximum suppression and SORT follow below
+ * (csrc/tracker.hip).
  *
  * pmce_conv2d_act_split_f16: pmce_conv2d_split_f16 with
  *     v = wscale[co] * sum_k (...) + bias[co];   res_after_act == 0: out = act(v + R);   res_after_act == 1: out = act(v) + R
@@ -842,6 +842,55 @@ int pmce_yolo_finalize_on(pmce_yolo* y, pmce_stream_t stream);
 size_t pmce_yolo_workspace_bytes(const pmce_yolo* y, int n, int S);
 int pmce_yolo_forward(const pmce_yolo* y, const float* images, long long sn, long long sc, long long sy, long long sx, int n, int S,
                       float* map0, float* map1, float* map2, float* rows, void* workspace, size_t workspace_bytes, pmce_stream_t stream);
+
+/* ---------------------------------------------------------------------------------------------------------
+ * The tracker's back half (csrc/tracker.hip): non-maximum suppression of the detector's rows, SORT over the frames of a video.  Written
+ * from the published texts (the PyTorch-YOLOv3 lineage's non_max_suppression; Bewley's sort.py over filterpy's KalmanFilter formulas;
+ * multi_person_tracker's run_tracker); no value was recorded from any of these packages.  tests/tracker_ref.py restates both.
+ *
+ * pmce_yolo_nms_f32: rows[n][R][5 + nc] = (cx, cy, w, h, conf, classes), R >= 1, nc in 1..255; one workgroup per image, one launch.
+ *   fp32, one rounding per operation (no contraction), per image:
+ *     candidates: conf >= conf_thres;  cls_conf = max of the class columns, cls = the FIRST maximum's index;  score = conf * cls_conf;
+ *     corners (cx - w/2, cy - h/2, cx + w/2, cy + h/2);  order: score descending, ties by the lower row (the project's rule);
+ *     while candidates remain: head = the first; invalid = the remaining ones of the head's cls with iou(head, .) > nms_thres,
+ *       iou = inter / (a + b - inter + 1e-16), inter = max(x2 - x1 + 1, 0) max(y2 - y1 + 1, 0), areas (x2 - x1 + 1)(y2 - y1 + 1);
+ *       kept box = sum(conf_i box_i) / sum(conf_i) over invalid, summed in sorted order; kept row = (x1, y1, x2, y2, conf, cls_conf,
+ *       cls) with the head's confidences; invalid leave, and the head leaves ALWAYS (the lineage loops forever on a head whose
+ *       self-IoU is not > nms_thres); heads are raw boxes: no IoU depends on a merged box.
+ *   dets[n][max_keep][7] in keep order, rows past count[i] zero; status[i] = 0, 1 (more than max_candidates candidates) or 2 (more than
+ *   max_keep kept) - then count[i] = 0 and the image's rows are zero, never a part.  max_candidates in 1..2048, max_keep in 1..64.
+ *   src_row (may be NULL) [n][max_keep]: the row of every kept head, -1 past the count.
+ *   people (may be NULL; with people_count) [n][max_keep][5] fp64 = (x1, y1, x2, y2, score), people_count[n]: the kept rows, in keep
+ *   order, with cls == class_id, score > score_thres (score = conf, or the fp32 conf * cls_conf when score_product != 0) and a box that
+ *   is finite with w > 0, h > 0 after the map to the frame x * ratio - pad_x, y * ratio - pad_y, evaluated in fp64 from the fp32 values
+ *   (pmce_letterbox_u8_f32's geometry; the lineage's rescale_boxes is the same map up to the rounding of its pad // 2).
+ *   The same bits whatever n; no atomics; validated on the host before the launch; no host wait.
+ *
+ * pmce_sort_track_f64: people[F][K][5], people_count[F] (clamped to 0..K, K <= 64) -> tracks[F][max_tracks][5] = (x1, y1, x2, y2,
+ *   id + 1) in report order, track_count[F], status[F] (1: a new tracker did not fit into max_tracks <= 64 and its detection was
+ *   dropped).  seq_offsets (host and device, or both NULL = one sequence) [S + 1] over frames: one 64-lane wave per sequence, ids from
+ *   0 per sequence.  fp64, no contraction.  State (u, v, s, r, du, dv, ds), s = w h, r = w / h; F = I + ones at (0,4), (1,5), (2,6);
+ *   H = [I4 | 0]; R = diag(1, 1, 10, 10); P0 = diag(10, 10, 10, 10, 1e4, 1e4, 1e4); Q = diag(1, 1, 1, 1, 0.01, 0.01, 0.0001).
+ *   Per frame with a detection (update_on_empty != 0: per frame): frame_count += 1; every tracker predicts (x[6] = 0 if x[6] + x[2] <= 0;
+ *   x = F x; P = F P F' + Q; hit_streak = 0 if time_since_update > 0; time_since_update += 1; box: w = sqrt(x2 x3), h = x2 / w) and is
+ *   deleted when its box has a NaN; IoU = inter / (a + b - inter) (no +1) between every detection and every tracker; the assignment
+ *   that maximises the total IoU (shortest augmenting paths with potentials; the newer sort.py's shortcut for one-to-one threshold
+ *   matrices is not built); pairs below iou_threshold are unmatched; a matched tracker updates (time_since_update = 0, hit_streak += 1,
+ *   y = z - H x, S = H P H' + R, K = P H' S^-1 by Gaussian elimination with partial pivoting, x += K y,
+ *   P = (I - K H) P (I - K H)' + K R K'); unmatched detections found trackers in detection order; the list is walked from last to
+ *   first: reported when time_since_update < 1 and (hit_streak >= min_hits or frame_count <= min_hits), deleted when
+ *   time_since_update > max_age.  A sequence computes the same bits alone or beside others.
+ *
+ * pmce_tracklet_boxes_f64: multi_person_tracker's prepare_output_tracks for a gathered list of reported rows: row index[i] of
+ *   tracks[total][5] (an index outside gives zeros) -> out[n][4] = (cx, cy, s, s), w = x2 - x1, h = y2 - y1, cx = x1 + w / 2,
+ *   cy = y1 + h / 2, s = w if w / h > 1 else h, in fp64. */
+int pmce_yolo_nms_f32(const float* rows, int n, int R, int nc, float conf_thres, float nms_thres, int max_candidates, int max_keep,
+                      float* dets, int* count, int* status, int* src_row, double* people, int* people_count, int class_id,
+                      double score_thres, int score_product, double pad_x, double pad_y, double ratio, pmce_stream_t stream);
+int pmce_sort_track_f64(const double* people, const int* people_count, const int* seq_offsets_host, const int* seq_offsets, int F, int K,
+                        int S, int max_age, int min_hits, double iou_threshold, int max_tracks, int update_on_empty, double* tracks,
+                        int* track_count, int* status, pmce_stream_t stream);
+int pmce_tracklet_boxes_f64(const double* tracks, const int* index, int total, int n, double* out, pmce_stream_t stream);
 
 #ifdef __cplusplus
 }

@@ -170,6 +170,9 @@ PROTOTYPES = {
     "pmce_yolo_finalize_on": [C.c_void_p, _s],
     "pmce_yolo_workspace_bytes": [C.c_void_p, _i, _i],
     "pmce_yolo_forward": [C.c_void_p, _f, _l, _l, _l, _l, _i, _i, _f, _f, _f, _f, C.c_void_p, C.c_size_t, _s],
+    "pmce_yolo_nms_f32": [_f, _i, _i, _i, _fl, _fl, _i, _i, _f, _f, _f, _f, _f, _f, _i, _d, _i, _d, _d, _d, _s],
+    "pmce_tracklet_boxes_f64": [_f, _f, _i, _i, _f, _s],
+    "pmce_sort_track_f64": [_f, _f, C.POINTER(C.c_int), _f, _i, _i, _i, _i, _i, _d, _i, _i, _f, _f, _f, _s],
 }
 _RESTYPES = {
     "pmce_last_error_string": C.c_char_p,

@@ -7,6 +7,8 @@ in, what the demo saves per person out - ``pred_cam``, ``mesh``, ``bboxes`` (``f
     video = demo.render_tracklets(outs, frames_u8, (1920, 1080), frame_ids=ids, renderer=render.Renderer(faces, (1920, 1080)))
     outs = demo.run_video(model, frames_u8, [(kp_a[N,17,3], ids_a), (kp_b, ids_b)], extractor, img_wh=(1920, 1080))   # crops included
     tracklets = demo.pose_tracklets(frames_u8, [(boxes_a[N,4], ids_a), (boxes_b, ids_b)], pose2d.TopDownPose(vitpose_net))   # boxes -> run_video's tracklets
+    boxes, person_ids = demo.track_video(frames_u8, tracker.Tracker(yolo_net))                  # frames -> pose_tracklets' tracklets
+    outs = demo.run_frames(model, frames_u8, tracker.Tracker(yolo_net), pose, extractor, img_wh=(1920, 1080))   # the demo up to rendering
 
 Per frame k the demo builds one window (``streaming.demo_window_list``), prepares the fit target from the window's middle frame
 (csrc/demo_prep.hip: add_pelvis_and_neck, get_bbox, process_bbox, j2d_processing), runs the model on the window and fits the
@@ -283,6 +285,29 @@ def pose_tracklets(frames, tracklets, pose):
     kp, _ = pose(frames, np.concatenate(ids).astype(np.int32), torch.cat(boxes))
     off = np.concatenate([[0], np.cumsum([len(f) for f in ids])])
     return [(kp[int(off[i]):int(off[i + 1])], ids[i]) for i in range(len(ids))]
+
+
+@torch.no_grad()
+def track_video(frames, tracker, min_frames: int = 25):
+    """The reference's tracking stage (main/run_demo.py:199-215) on the device: frames uint8 [F,H,W,3], ``tracker`` a
+    ``tracker.Tracker`` -> ([(boxes fp64 [N_i,4] = (cx, cy, s, s) on the device, frame_ids int64 [N_i] on the host), ...], person ids):
+    ``pose_tracklets``' tracklets, without the persons seen in fewer than ``min_frames`` frames (MIN_NUM_FRAMES)."""
+    return tracker(frames, min_frames=min_frames)
+
+
+@torch.no_grad()
+def run_frames(model, frames, tracker, pose, extractor, img_wh, min_frames: int = 25, **run_video_kwargs):
+    """The whole demo up to rendering: ``track_video``, then ``pose_tracklets``, then ``run_video`` -> ``run_video``'s dicts, each with
+    'person_id' (the tracker's id) added.  ``tracker``'s boxes are (cx, cy, w, h): ``pose.box_format`` must be "cxcywh"."""
+    if getattr(pose, "box_format", "cxcywh") != "cxcywh":
+        raise ValueError(f"run_frames: the tracker's boxes are cxcywh, pose.box_format is {pose.box_format!r}")
+    if not isinstance(frames, torch.Tensor) or not frames.is_cuda:
+        frames = torch.as_tensor(np.ascontiguousarray(frames)).to(torch.device("cuda", torch.cuda.current_device()))     # one upload for all stages
+    boxes, ids = track_video(frames, tracker, min_frames=min_frames)
+    outs = run_video(model, frames, pose_tracklets(frames, boxes, pose), extractor, img_wh, **run_video_kwargs)
+    for o, pid in zip(outs, ids):
+        o["person_id"] = pid
+    return outs
 
 
 @torch.no_grad()

@@ -8,7 +8,7 @@
     rows, maps = det.forward(images, return_maps=True)                   # + the three raw detection maps, NCHW views
 
 The structure is the published ``yolov3.cfg``'s and that of the PyTorch-YOLOv3 lineage; no tensor was recorded from the ``yolov3`` or
-``multi_person_tracker`` packages.  Non-maximum suppression, SORT and the tracklet records are not here.  There is no fallback and no
+``multi_person_tracker`` packages.  Non-maximum suppression, SORT and the tracklet records are ``pmce_amd/tracker.py``.  There is no fallback and no
 torch convolution on the path: without the library's kernels a call raises.
 """
 from __future__ import annotations
