@@ -276,7 +276,10 @@ __global__ __launch_bounds__(256) void seq_attention_kernel(const float* __restr
 #pragma unroll
       for (int k = 0; k < 4; ++k) sc += q[4 * d4 + k] * t[k];
     }
-    sc *= scale;
+    // ONE fp32 value for the maximum and for the exponent (common.hpp): left to -ffp-contract=fast, `sc - mn` below becomes
+    // fma(sc, scale, -mn) of the unrounded product, and the key that holds the maximum gets 2^(the product's rounding error) in place
+    // of 2^0 - at N = 1 a result an ulp away from v (found by test_gpu_seq_attention.py)
+    sc = pinned(sc * scale);
     const float mn = fmaxf(m, sc);
     const float corr = __builtin_amdgcn_exp2f(m - mn);  // first key: 2^(-inf) = 0
     const float pj = __builtin_amdgcn_exp2f(sc - mn);

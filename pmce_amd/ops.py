@@ -265,20 +265,31 @@ def lifter_head(x, lnw, lnb, Wr, br, wf, bf, B, T, J, pre=None):
     return out
 
 
-def seq_attention(qkv, nseq, N, Cc, seq_div, seq_lo, seq_hi, tok_stride, out_split=False):
+def _attention_out(qkv, Cc, out):
+    """The [rows, C] fp32 result buffer of an attention call: a fresh one, or the caller's `out` (the rows no sequence of the call owns keep
+    what they held)."""
+    if out is None:
+        return torch.empty(qkv.shape[0], Cc, device=qkv.device, dtype=torch.float32)
+    if out.dtype != torch.float32 or tuple(out.shape) != (qkv.shape[0], Cc) or out.device != qkv.device or not out.is_contiguous():
+        raise ValueError(f"out must be a contiguous float32 [{qkv.shape[0]}, {Cc}] tensor on {qkv.device}, "
+                         f"got {out.dtype} {tuple(out.shape)} on {out.device}")
+    return out
+
+
+def seq_attention(qkv, nseq, N, Cc, seq_div, seq_lo, seq_hi, tok_stride, out_split=False, out=None):
     lib = _lib.load()
     qkv = _c(qkv)
-    out = torch.empty(qkv.shape[0], Cc, device=qkv.device, dtype=torch.float32)
+    out = _attention_out(qkv, Cc, out)
     _lib.check(lib.pmce_seq_attention_f32(P(qkv), P(out), nseq, N, Cc, seq_div, seq_lo, seq_hi, tok_stride,
                                           1 if out_split else 0, _st()), "seq_attention")
     return out
 
 
-def seq_attention_split(qkv, nseq, N, Cc, seq_div, seq_lo, seq_hi, tok_stride):
+def seq_attention_split(qkv, nseq, N, Cc, seq_div, seq_lo, seq_hi, tok_stride, out=None):
     """The matrix-pipe attention of the split-f16 mode: fp32 q, k, v in, pre-split result out (see :func:`unsplit_rows_f16`)."""
     lib = _lib.load()
     qkv = _c(qkv)
-    out = torch.empty(qkv.shape[0], Cc, device=qkv.device, dtype=torch.float32)
+    out = _attention_out(qkv, Cc, out)
     _lib.check(lib.pmce_seq_attention_split_f16(P(qkv), P(out), nseq, N, Cc, seq_div, seq_lo, seq_hi, tok_stride, _st()),
                "seq_attention_split_f16")
     return out
