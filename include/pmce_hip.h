@@ -892,6 +892,56 @@ int pmce_sort_track_f64(const double* people, const int* people_count, const int
                         int* track_count, int* status, pmce_stream_t stream);
 int pmce_tracklet_boxes_f64(const double* tracks, const int* index, int total, int n, double* out, pmce_stream_t stream);
 
+/* ---------------------------------------------------------------------------------------------------------
+ * The demo's frames from JPEG files (csrc/jpeg.hip, csrc/jpeg_entropy.hpp): baseline Huffman JPEG, 8 bit, grey or YCbCr 4:4:4 / 4:2:2 /
+ * 4:2:0 in one interleaved scan, decoded to the bytes that libjpeg's default decoder (and with it cv2.imread) gives: jidctint "islow",
+ * "fancy" chroma upsampling, jdcolor's fixed-point conversion.  Integer arithmetic, no atomics, no host wait; the same bits whatever
+ * the batch.  pmce_amd/jpeg.py parses the markers on the host, refuses what is not served and writes the records below; all are
+ * int32 unless stated, and one batch of files is one set of concatenated arrays.  An Exif orientation tag is not read.
+ *
+ * data[n_bytes]            the files' bytes, one after the other (n_bytes <= 2^31 - 129).
+ * images[n][24]            0 width, 1 height, 2 components (1 or 3), 3 h, 4 v (luma sampling, 1 or 2; 1, 1 for a grey file),
+ *                          5 mcus_x, 6 mcus_y, 7 restart interval (0: none), 8..10 quantisation table of component c (index into
+ *                          quant), 11..13 its DC and 14..16 its AC Huffman table (index into huffman), 17 first block of the image in
+ *                          the coefficient buffer, 18 first byte of its planes in the plane buffer (both relative to the round the image
+ *                          is decoded in), 19 first segment, 20 segment count, 21 blocks per MCU (h v + 2, or 1), 22..23 zero.
+ * quant[n][64]             uint16, in zigzag order as DQT stores them.
+ * huffman[n][546]          0..16 maxcode[l]: the largest code of length l (-1: none; entry 0 unused); 17..33 valoff[l]: the index of a
+ *                          length-l code's value is code + valoff[l]; 34..289 values; 290..545 lookahead by the next 8 bits:
+ *                          (length << 8) | value for codes of at most 8 bits, 0 otherwise.
+ * segments[n][5]           (image, first byte, end byte, first MCU, MCU count): one per restart interval, one per image without DRI;
+ *                          bytes index `data`; [first, end) holds entropy-coded bytes only (it ends where the next marker begins).
+ * coefficients             int16 [blocks][64] in natural order; blocks in scan order: MCU by MCU, inside an MCU the luma blocks (v rows
+ *                          of h), then Cb, then Cr.
+ * planes                   uint8; per image the luma plane (mcus_x h 8) x (mcus_y v 8), then Cb and Cr, (mcus_x 8) x (mcus_y 8) each.
+ * status bits              PMCE_JPEG_STATUS_TRUNCATED 1: a segment consumed bits from beyond its end (zero bits are supplied there);
+ *                          PMCE_JPEG_STATUS_CORRUPT 2: a code of no table, a run past coefficient 63 or a marker inside a segment;
+ *                          PMCE_JPEG_STATUS_RECORD 4: a record that does not fit its arrays (the host never writes one).  A segment
+ *                          with a bit set ends after the block at hand; what it did not decode stays zero.  No lane reads outside its
+ *                          segment's bytes or writes outside its segment's blocks, whatever the bytes say (scripts/jpeg_entropy_host.cpp).
+ *
+ * pmce_jpeg_entropy: zeroes coefficients[n_blocks] (16-byte aligned) and decodes segments [first_segment, first_segment + n_segments),
+ *   one lane each, into them; segment_status[s] for each of them (the array spans all segments).  lds_tables != 0 (the default of
+ *   pmce_amd.jpeg): with at most 16 Huffman tables in the batch the lanes read them from LDS; 0: always from global memory (the same
+ *   bits, slower; the form a batch with more tables takes).  lanes: segments per 64-lane wavefront, 1 .. 64, or 0: as few as still give
+ *   every segment a lane within 4096 wavefronts (lanes of one wavefront take their branches in turn, wavefronts do not).
+ * pmce_jpeg_idct: images [first_image, first_image + n_images): coefficient blocks -> planes; max_blocks: the largest block count of one
+ *   of these images.
+ * pmce_jpeg_colour: the same images: planes -> frames[image][height][width][3] (B, G, R; R, G, B with rgb != 0) and status[image] = the
+ *   OR of the image's segment status words.  frames and status are indexed by the absolute image number. */
+#define PMCE_JPEG_STATUS_TRUNCATED 1
+#define PMCE_JPEG_STATUS_CORRUPT 2
+#define PMCE_JPEG_STATUS_RECORD 4
+int pmce_jpeg_entropy(const unsigned char* data, long long n_bytes, const int* segments, int first_segment, int n_segments,
+                      const int* images, int n_images, const int* huffman, int n_huffman, short* coefficients, long long n_blocks,
+                      int* segment_status, int lds_tables, int lanes, pmce_stream_t stream);
+int pmce_jpeg_idct(const short* coefficients, const int* images, int first_image, int n_images, int max_blocks,
+                   const unsigned short* quant, int n_quant, long long n_blocks, unsigned char* planes, long long plane_bytes,
+                   pmce_stream_t stream);
+int pmce_jpeg_colour(const unsigned char* planes, long long plane_bytes, const int* images, int first_image, int n_images,
+                     const int* segment_status, int n_segments_total, int width, int height, int rgb, unsigned char* frames, int* status,
+                     pmce_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -9,6 +9,8 @@ in, what the demo saves per person out - ``pred_cam``, ``mesh``, ``bboxes`` (``f
     tracklets = demo.pose_tracklets(frames_u8, [(boxes_a[N,4], ids_a), (boxes_b, ids_b)], pose2d.TopDownPose(vitpose_net))   # boxes -> run_video's tracklets
     boxes, person_ids = demo.track_video(frames_u8, tracker.Tracker(yolo_net))                  # frames -> pose_tracklets' tracklets
     outs = demo.run_frames(model, frames_u8, tracker.Tracker(yolo_net), pose, extractor, img_wh=(1920, 1080))   # the demo up to rendering
+    frames_u8, (w, h), names = demo.load_frames("video_frames/")                               # a folder of .jpg files, decoded on the device
+    outs = demo.run_folder(model, "video_frames/", tracker.Tracker(yolo_net), pose, extractor)  # load_frames, then run_frames
 
 Per frame k the demo builds one window (``streaming.demo_window_list``), prepares the fit target from the window's middle frame
 (csrc/demo_prep.hip: add_pelvis_and_neck, get_bbox, process_bbox, j2d_processing), runs the model on the window and fits the
@@ -308,6 +310,47 @@ def run_frames(model, frames, tracker, pose, extractor, img_wh, min_frames: int 
     for o, pid in zip(outs, ids):
         o["person_id"] = pid
     return outs
+
+
+def load_frames(folder, device=None, strict: bool = True, chunk: int = 32):
+    """The frames of a folder of JPEG files, as the reference's demo first sees its video (lib/utils/demo_utils.py:101-121 has ffmpeg
+    write ``%06d.jpg``) -> (frames uint8 [F, H, W, 3] on the device, channels B, G, R as ``cv2.imread`` leaves them, (width, height),
+    the file names in frame order).  The files ending in .jpg or .jpeg (any letter case) are taken, sorted by name as
+    main/run_demo.py:386-390 sorts them, and decoded by ``jpeg.decode`` (csrc/jpeg.hip): no host decode, one upload of the files' bytes.
+    A .png in the folder is a ValueError (PNG is not served), as are an empty folder, files of unequal size and every file
+    ``jpeg.parse`` refuses.  ``strict``: make the one host read of the decoder's status and raise, naming the first file whose
+    scan was truncated or corrupt; without it such a frame is returned as far as it decoded.  An Exif orientation tag is not read
+    (``cv2.imread`` would rotate such a file; ffmpeg's frames carry none).  ``chunk``: images per round of the decoder (``jpeg.decode``);
+    files without restart markers - what ffmpeg writes - decode one lane per image, so raise it as far as memory allows (9.4 MB of
+    workspace per 1080p image)."""
+    import os
+    from . import jpeg
+    entries = sorted(os.listdir(folder))
+    png = [x for x in entries if x.lower().endswith(".png")]
+    if png:
+        raise ValueError(f"{os.path.join(folder, png[0])}: PNG is not served, only JPEG files (.jpg, .jpeg)")
+    names = [x for x in entries if x.lower().endswith((".jpg", ".jpeg"))]
+    if not names:
+        raise ValueError(f"{folder}: no .jpg or .jpeg file")
+    files = []
+    for x in names:
+        with open(os.path.join(folder, x), "rb") as fh:
+            files.append(fh.read())
+    frames, status = jpeg.decode(files, device, channel_order="bgr", chunk=chunk, names=[os.path.join(folder, x) for x in names])
+    if strict:
+        st = status.cpu().numpy()
+        bad = np.flatnonzero(st)
+        if len(bad):
+            what = " and ".join(w for bit, w in ((jpeg.STATUS_TRUNCATED, "truncated"), (jpeg.STATUS_CORRUPT, "corrupt"),
+                                                (jpeg.STATUS_RECORD, "not decodable")) if st[bad[0]] & bit)
+            raise ValueError(f"{os.path.join(folder, names[int(bad[0])])}: the scan is {what} (status {int(st[bad[0]])})")
+    return frames, (int(frames.shape[2]), int(frames.shape[1])), names
+
+
+def run_folder(model, folder, tracker, pose, extractor, device=None, strict: bool = True, chunk: int = 32, **run_frames_kwargs):
+    """``load_frames`` then ``run_frames``, with ``img_wh`` taken from the files -> ``run_frames``' dicts."""
+    frames, img_wh, _ = load_frames(folder, device=device, strict=strict, chunk=chunk)
+    return run_frames(model, frames, tracker, pose, extractor, img_wh, **run_frames_kwargs)
 
 
 @torch.no_grad()

@@ -1,0 +1,438 @@
+"""The demo's frames from JPEG files, decoded on the GPU (csrc/jpeg.hip): what the reference does with ``cv2.imread`` four or more
+times per frame (lib/utils/demo_utils.py:101-121 has ffmpeg write ``%06d.jpg``; main/run_demo.py:264-286, 392-395 and
+lib/utils/_dataset_demo.py:60 read the files back), once, for a whole folder, into the uint8 [F, H, W, 3] tensor the demo's stages take.
+
+    header = jpeg.parse(data, "000001.jpg")                     # host only: markers, tables, the scan's segments; refuses with ValueError
+    frames, status = jpeg.decode([data0, data1, ...], device)   # uint8 [F, H, W, 3] in B, G, R (cv2's order), int32 [F]; no wait for the device
+    frames, status = jpeg.decode(files, device, channel_order="rgb", chunk=32, out=preallocated)
+
+Served: baseline Huffman JPEG (SOF0, and SOF1 with 8-bit samples), grey or YCbCr with luma sampling 1x1, 2x1 or 2x2 (4:4:4, 4:2:2,
+4:2:0) in one interleaved scan, 8-bit quantisation tables, up to four DC and four AC Huffman tables, restart intervals.  The pixels
+are those of libjpeg's default decoder, to the bit: "islow" inverse DCT, "fancy" chroma upsampling, jdcolor's
+fixed-point conversion.  Refused, with a ValueError that names the file and the reason: progressive, lossless and arithmetic-coded
+files, 12-bit samples, four components, 16-bit quantisation tables, an Adobe marker whose transform is not 1 on a three-component
+file, any other sampling, more than one scan, DNL, a missing table, a width or height of 0 or above 16384, data that ends before SOS.
+
+An Exif orientation tag is NOT read: ``cv2.imread`` would rotate such a file, this reader does not.  (ffmpeg's frames carry none.)
+
+``status[f]`` is an OR of STATUS_TRUNCATED (the scan ended before its last MCU; zero bits are supplied beyond the end) and
+STATUS_CORRUPT (a code of no table, a run past coefficient 63, a marker inside a restart interval); ``decode`` does not read it.
+There is no fallback: without the library's kernels a call raises.
+"""
+from __future__ import annotations
+
+import ctypes as C
+import struct
+from dataclasses import dataclass, field
+
+import numpy as np
+
+from . import _lib
+
+MAX_DIM = 16384
+IMG_WORDS, SEG_WORDS, HUFF_WORDS = 24, 5, 546          # csrc/jpeg_entropy.hpp, include/pmce_hip.h
+HUFF_MAXCODE, HUFF_VALOFF, HUFF_VALUES, HUFF_LOOK = 0, 17, 34, 290
+STATUS_TRUNCATED, STATUS_CORRUPT, STATUS_RECORD = 1, 2, 4
+CHANNEL_ORDERS = ("bgr", "rgb")
+DUMP_MAGIC = b"PMCEJPG1"
+
+_SOF_NAMES = {0xC2: "progressive (SOF2)", 0xC3: "lossless (SOF3)", 0xC5: "differential sequential (SOF5)",
+              0xC6: "differential progressive (SOF6)", 0xC7: "differential lossless (SOF7)", 0xC8: "a reserved frame type (JPG)",
+              0xC9: "arithmetic coding (SOF9)", 0xCA: "arithmetic coding, progressive (SOF10)", 0xCB: "arithmetic coding, lossless (SOF11)",
+              0xCC: "arithmetic coding (DAC)", 0xCD: "arithmetic coding, differential (SOF13)",
+              0xCE: "arithmetic coding, differential progressive (SOF14)", 0xCF: "arithmetic coding, differential lossless (SOF15)"}
+
+
+@dataclass
+class Header:
+    """What ``parse`` found.  ``quant[c]``: uint16 [64] in zigzag order as stored; ``dc[c]`` / ``ac[c]``: (counts of the lengths 1..16,
+    values) of component c's Huffman tables; ``segments``: int64 [n, 4] = (first byte, end byte, first MCU, MCU count), bytes counted
+    from the start of the file, one row per restart interval (one row without DRI)."""
+    name: str
+    data: bytes
+    width: int
+    height: int
+    ncomp: int
+    h: int
+    v: int
+    mcus_x: int
+    mcus_y: int
+    restart_interval: int
+    blocks_per_mcu: int
+    scan_begin: int
+    scan_end: int
+    quant: list = field(default_factory=list)
+    dc: list = field(default_factory=list)
+    ac: list = field(default_factory=list)
+    segments: np.ndarray = None
+
+    @property
+    def n_blocks(self) -> int:
+        return self.mcus_x * self.mcus_y * self.blocks_per_mcu
+
+    @property
+    def plane_bytes(self) -> int:
+        luma = (self.mcus_x * self.h * 8) * (self.mcus_y * self.v * 8)
+        return luma + (2 * (self.mcus_x * 8) * (self.mcus_y * 8) if self.ncomp == 3 else 0)
+
+
+def _refuse(name, why):
+    raise ValueError(f"{name or '<bytes>'}: {why}")
+
+
+def huffman_record(counts, values, name="") -> np.ndarray:
+    """One table as the device reads it: int32 [546] = maxcode[17] | valoff[17] | values[256] | lookahead[256] (include/pmce_hip.h)."""
+    rec = np.zeros(HUFF_WORDS, dtype=np.int32)
+    rec[HUFF_MAXCODE:HUFF_MAXCODE + 17] = -1
+    if sum(counts) > 256 or sum(counts) != len(values):
+        _refuse(name, f"a Huffman table with {sum(counts)} codes and {len(values)} values")
+    rec[HUFF_VALUES:HUFF_VALUES + len(values)] = np.frombuffer(bytes(values), dtype=np.uint8)
+    code = k = 0
+    for length in range(1, 17):
+        n = counts[length - 1]
+        if n:
+            if code + n > (1 << length):
+                _refuse(name, f"a Huffman table with more codes of {length} bits than there are")
+            rec[HUFF_VALOFF + length] = k - code
+            rec[HUFF_MAXCODE + length] = code + n - 1
+            if length <= 8:
+                for j in range(n):
+                    lo = (code + j) << (8 - length)
+                    rec[HUFF_LOOK + lo:HUFF_LOOK + lo + (1 << (8 - length))] = (length << 8) | values[k + j]
+            code += n
+            k += n
+        code <<= 1
+    return rec
+
+
+def _scan_segments(data: bytes, scan_begin: int, n_mcu: int, restart_interval: int):
+    """The scan's extent and its restart intervals, by one vectorised pass over the scan's bytes: every FF that is followed by neither 00
+    (a stuffed byte) nor FF (a fill byte) begins a marker; RSTn markers split the scan, the first other marker ends it.  A scan with
+    fewer intervals than its DRI promises (a file cut short) gets empty segments for the missing ones: the device reports them as
+    truncated.  -> (segments int64 [n, 4], scan_end, the position of the marker that ended the scan or -1)."""
+    a = np.frombuffer(data, dtype=np.uint8)[scan_begin:]
+    ff = np.flatnonzero(a[:-1] == 0xFF) if len(a) > 1 else np.zeros(0, dtype=np.int64)
+    nxt = a[ff + 1]
+    marks = ff[(nxt != 0x00) & (nxt != 0xFF)]
+    is_rst = (a[marks + 1] & 0xF8) == 0xD0
+    other = np.flatnonzero(~is_rst)
+    n_rst = int(other[0]) if len(other) else len(marks)
+    end_marker = int(marks[n_rst]) if len(other) else -1
+    scan_end = end_marker if end_marker >= 0 else len(a)
+    expected = -(-n_mcu // restart_interval) if restart_interval else 1
+    rst = marks[:min(n_rst, expected - 1)] if restart_interval else marks[:0]
+    begins = np.concatenate([[0], rst + 2]).astype(np.int64)
+    ends = np.concatenate([rst, [marks[0] if (not restart_interval and len(marks)) else scan_end]]).astype(np.int64)
+    while len(a):                                 # fill bytes in front of a marker are not data (a data FF is followed by 00)
+        fill = (ends > begins) & (a[np.maximum(ends - 1, 0)] == 0xFF)
+        if not fill.any():
+            break
+        ends[fill] -= 1
+    seg = np.zeros((expected, 4), dtype=np.int64)
+    seg[:, 0] = seg[:, 1] = scan_end
+    seg[:len(begins), 0], seg[:len(begins), 1] = begins, ends
+    seg[:, :2] += scan_begin
+    ri = restart_interval or n_mcu
+    seg[:, 2] = np.arange(expected) * ri
+    seg[:, 3] = np.minimum(ri, n_mcu - seg[:, 2])
+    return seg, scan_begin + scan_end, (scan_begin + end_marker if end_marker >= 0 else -1)
+
+
+def parse(data: bytes, name: str = "") -> Header:
+    """Walk the markers of one file up to SOS and find the scan's extent -> ``Header``; ValueError (naming ``name`` and the reason) for
+    anything this reader does not serve.  Host only.  An Exif orientation tag is not read (``cv2.imread`` would rotate such a file)."""
+    data = bytes(data)
+    n = len(data)
+    if n < 2 or data[0] != 0xFF or data[1] != 0xD8:
+        _refuse(name, "not a JPEG file (no SOI marker)")
+    quant, huff = {}, {}
+    frame = scan = adobe = None
+    restart = 0
+    i = 2
+    while scan is None:
+        if i + 2 > n:
+            _refuse(name, "the data ends before SOS")
+        if data[i] != 0xFF:
+            _refuse(name, f"a marker was expected at byte {i}")
+        while i + 1 < n and data[i + 1] == 0xFF:      # fill bytes
+            i += 1
+        if i + 2 > n:
+            _refuse(name, "the data ends before SOS")
+        m = data[i + 1]
+        if m == 0x01 or m == 0xD8 or 0xD0 <= m <= 0xD7:
+            i += 2
+            continue
+        if m == 0xD9:
+            _refuse(name, "the data ends before SOS (EOI)")
+        if i + 4 > n:
+            _refuse(name, "the data ends before SOS")
+        L = (data[i + 2] << 8) | data[i + 3]
+        if L < 2 or i + 2 + L > n:
+            _refuse(name, "the data ends before SOS")
+        body = data[i + 4:i + 2 + L]
+        if m in _SOF_NAMES:
+            _refuse(name, f"{_SOF_NAMES[m]} is not served, only baseline Huffman files")
+        if m in (0xC0, 0xC1):
+            if frame is not None:
+                _refuse(name, "more than one frame header")
+            if len(body) < 6 or len(body) < 6 + 3 * body[5]:
+                _refuse(name, "a frame header that is too short")
+            if body[0] != 8:
+                _refuse(name, f"{body[0]}-bit samples are not served, only 8-bit")
+            height, width, nc = (body[1] << 8) | body[2], (body[3] << 8) | body[4], body[5]
+            if nc == 4:
+                _refuse(name, "4 components (CMYK / YCCK) are not served")
+            if nc not in (1, 3):
+                _refuse(name, f"{nc} components are not served, only 1 (grey) or 3 (YCbCr)")
+            if not (1 <= width <= MAX_DIM and 1 <= height <= MAX_DIM):
+                _refuse(name, f"a width or height of 0 or above {MAX_DIM} (got {width} x {height})")
+            frame = dict(width=width, height=height, comps=[(body[6 + 3 * c], body[7 + 3 * c] >> 4, body[7 + 3 * c] & 15, body[8 + 3 * c])
+                                                            for c in range(nc)])
+        elif m == 0xDB:
+            p = 0
+            while p < len(body):
+                if body[p] >> 4:
+                    _refuse(name, "16-bit quantisation tables are not served")
+                if (body[p] & 15) > 3 or p + 65 > len(body):
+                    _refuse(name, "a malformed quantisation table")
+                quant[body[p] & 15] = np.frombuffer(body[p + 1:p + 65], dtype=np.uint8).astype(np.uint16)
+                p += 65
+        elif m == 0xC4:
+            p = 0
+            while p < len(body):
+                if p + 17 > len(body) or (body[p] >> 4) > 1 or (body[p] & 15) > 3:
+                    _refuse(name, "a malformed Huffman table")
+                counts = tuple(body[p + 1:p + 17])
+                if p + 17 + sum(counts) > len(body):
+                    _refuse(name, "a malformed Huffman table")
+                huff[(body[p] >> 4, body[p] & 15)] = (counts, bytes(body[p + 17:p + 17 + sum(counts)]))
+                p += 17 + sum(counts)
+        elif m == 0xDD:
+            if len(body) < 2:
+                _refuse(name, "a malformed DRI segment")
+            restart = (body[0] << 8) | body[1]
+        elif m == 0xDC:
+            _refuse(name, "DNL is not served")
+        elif m == 0xEE and body[:5] == b"Adobe" and len(body) >= 12:
+            adobe = body[11]
+        elif m == 0xDA:
+            if frame is None:
+                _refuse(name, "SOS before the frame header")
+            scan = body
+            scan_begin = i + 2 + L
+        i += 2 + L
+
+    comps = frame["comps"]
+    nc = len(comps)
+    if nc == 3 and adobe is not None and adobe != 1:
+        _refuse(name, f"an Adobe marker with transform {adobe} (not YCbCr) is not served")
+    if len(scan) < 1 or scan[0] != nc or len(scan) < 1 + 2 * nc + 3:
+        _refuse(name, f"a scan of {scan[0] if len(scan) else 0} of the {nc} components: more than one SOS is not served")
+    if [scan[1 + 2 * c] for c in range(nc)] != [c[0] for c in comps]:
+        _refuse(name, "the scan's components are not the frame's, in the frame's order")
+    if (scan[1 + 2 * nc], scan[2 + 2 * nc], scan[3 + 2 * nc]) != (0, 63, 0):
+        _refuse(name, "a scan that is not the whole spectrum at full precision (progressive parameters)")
+    if nc == 1:
+        h = v = 1                  # one component is never interleaved: its MCU is one block whatever the factors say
+    else:
+        h, v = comps[0][1], comps[0][2]
+        if (h, v) not in ((1, 1), (2, 1), (2, 2)) or any((c[1], c[2]) != (1, 1) for c in comps[1:]):
+            _refuse(name, "sampling " + ", ".join(f"{c[1]}x{c[2]}" for c in comps) + " is not served, only 4:4:4, 4:2:2 and 4:2:0")
+    hdr = Header(name=name, data=data, width=frame["width"], height=frame["height"], ncomp=nc, h=h, v=v,
+                 mcus_x=-(-frame["width"] // (8 * h)), mcus_y=-(-frame["height"] // (8 * v)), restart_interval=restart,
+                 blocks_per_mcu=1 if nc == 1 else h * v + 2, scan_begin=scan_begin, scan_end=scan_begin)
+    for c in range(nc):
+        td, ta = scan[2 + 2 * c] >> 4, scan[2 + 2 * c] & 15
+        if comps[c][3] not in quant:
+            _refuse(name, f"quantisation table {comps[c][3]} is referenced but not defined")
+        if (0, td) not in huff or (1, ta) not in huff:
+            _refuse(name, f"Huffman table {'DC ' + str(td) if (0, td) not in huff else 'AC ' + str(ta)} is referenced but not defined")
+        hdr.quant.append(quant[comps[c][3]])
+        hdr.dc.append(huff[(0, td)])
+        hdr.ac.append(huff[(1, ta)])
+        huffman_record(*hdr.dc[-1], name=name), huffman_record(*hdr.ac[-1], name=name)      # their checks
+    hdr.segments, hdr.scan_end, at = _scan_segments(data, scan_begin, hdr.mcus_x * hdr.mcus_y, restart)
+    # what follows the scan: nothing this reader would have to decode
+    while at >= 0 and at + 2 <= n:
+        m = data[at + 1]
+        if m == 0xD9:
+            break
+        if m == 0xDA:
+            _refuse(name, "more than one SOS is not served")
+        if m == 0xDC:
+            _refuse(name, "DNL is not served")
+        if m in (0xC0, 0xC1) or m in _SOF_NAMES:
+            _refuse(name, "more than one frame is not served")
+        if at + 4 > n:
+            break
+        at += 2 + ((data[at + 2] << 8) | data[at + 3])
+        while at + 1 < n and data[at] == 0xFF and data[at + 1] == 0xFF:
+            at += 1
+        if at + 1 < n and data[at] != 0xFF:
+            break
+    return hdr
+
+
+def build_records(headers, chunk: int) -> dict:
+    """The flat arrays of a batch (include/pmce_hip.h): ``data`` uint8, ``images`` int32 [F, 24], ``quant`` uint16 [nq, 64],
+    ``huffman`` int32 [nh, 546], ``segments`` int32 [S, 5]; equal tables are stored once.  ``rounds``: per round of ``chunk`` images
+    (first image, image count, first segment, segment count, coefficient blocks, plane bytes, the largest image's blocks)."""
+    F = len(headers)
+    images = np.zeros((F, IMG_WORDS), dtype=np.int32)
+    quant, huffman, qi, hi = [], [], {}, {}
+    segs, rounds, datas = [], [], []
+    base = seg0 = 0
+    for f, hd in enumerate(headers):
+        if f % chunk == 0:
+            rounds.append([f, 0, seg0, 0, 0, 0, 0])
+        rd = rounds[-1]
+        im = images[f]
+        im[:8] = (hd.width, hd.height, hd.ncomp, hd.h, hd.v, hd.mcus_x, hd.mcus_y, hd.restart_interval)
+        for c in range(hd.ncomp):
+            key = hd.quant[c].tobytes()
+            if key not in qi:
+                qi[key] = len(quant)
+                quant.append(hd.quant[c])
+            im[8 + c] = qi[key]
+            for word, tab in ((11, hd.dc[c]), (14, hd.ac[c])):
+                if tab not in hi:
+                    hi[tab] = len(huffman)
+                    huffman.append(huffman_record(*tab, name=hd.name))
+                im[word + c] = hi[tab]
+        if rd[4] + hd.n_blocks >= 2 ** 31 or rd[5] + hd.plane_bytes >= 2 ** 31:
+            raise ValueError(f"{hd.name}: {chunk} images of {hd.width} x {hd.height} per round need a workspace past 2^31: use a smaller chunk")
+        im[17], im[18], im[19], im[20], im[21] = rd[4], rd[5], seg0, len(hd.segments), hd.blocks_per_mcu
+        s = np.empty((len(hd.segments), SEG_WORDS), dtype=np.int64)
+        s[:, 0] = f
+        s[:, 1:3] = hd.segments[:, :2] + base
+        s[:, 3:5] = hd.segments[:, 2:4]
+        segs.append(s)
+        rd[1] += 1
+        rd[3] += len(hd.segments)
+        rd[4] += hd.n_blocks
+        rd[5] += hd.plane_bytes
+        rd[6] = max(rd[6], hd.n_blocks)
+        seg0 += len(hd.segments)
+        base += len(hd.data)
+        datas.append(np.frombuffer(hd.data, dtype=np.uint8))
+        if base > 2 ** 31 - 129:
+            raise ValueError(f"{hd.name}: the files of one call must stay below 2^31 - 128 bytes together: decode them in parts")
+    return dict(data=np.concatenate(datas), images=images, quant=np.stack(quant), huffman=np.stack(huffman),
+                segments=np.concatenate(segs).astype(np.int32), rounds=rounds)
+
+
+def parse_all(files, names=None, same_size: bool = True):
+    """``parse`` of every file of one batch; with ``same_size`` all must have one size, else ValueError names the first file that differs."""
+    if len(files) == 0:
+        raise ValueError("decode: no files")
+    names = list(names) if names is not None else [f"file {i}" for i in range(len(files))]
+    if len(names) != len(files):
+        raise ValueError(f"decode: {len(files)} files but {len(names)} names")
+    headers = [parse(d, nm) for d, nm in zip(files, names)]
+    w, h = headers[0].width, headers[0].height
+    for hd in headers:
+        if same_size and (hd.width, hd.height) != (w, h):
+            raise ValueError(f"{hd.name}: {hd.width} x {hd.height}, but {headers[0].name} is {w} x {h}: all files of one call must have one size")
+    return headers
+
+
+def decode(files, device=None, channel_order: str = "bgr", chunk: int = 32, out=None, names=None, return_coefficients: bool = False,
+           timings=None, lds_tables: bool = True, lanes: int = 0):
+    """files: a list of ``bytes``, one JPEG file each, all of one size -> (frames uint8 [F, H, W, 3] on ``device``, status int32 [F] on
+    the device), by pmce_jpeg_entropy / _idct / _colour on the current stream, ``chunk`` images per round through one workspace
+    (2 bytes of coefficients and 1 of planes per padded sample: 9.4 MB per 1080p 4:2:0 image), after ONE upload of the files' bytes and their records.
+    Channels are B, G, R as ``cv2.imread`` returns them, or R, G, B with ``channel_order="rgb"``.  ``out``: a contiguous uint8
+    [F, H, W, 3] device tensor to fill.  Sampling, tables and restart interval may differ from file to file.  ``status`` is not
+    read here (no wait for the device: the upload leaves page-locked memory asynchronously, no kernel and no result is waited for): 0 is a clean decode, see STATUS_*.  ``names`` label the files in errors.  ``return_coefficients``
+    (one round only: F <= chunk) adds the entropy stage's int16 [blocks, 64] as a third result.  ``timings``: a list that receives
+    (stage, start event, end event) per launch, for scripts/bench_jpeg.py.  ``lds_tables=False``: the entropy stage reads the Huffman
+    tables from global memory even where they would fit into LDS (at most 16 distinct tables in the batch) - the same bits, slower;
+    the form a batch with more tables takes anyway.  ``lanes``: segments per wavefront of the entropy stage, 1..64, or 0 for the
+    library's choice (one until a round has more than 4096 segments) - the same bits whatever it is."""
+    import torch
+    if channel_order not in CHANNEL_ORDERS:
+        raise ValueError(f"channel_order must be one of {CHANNEL_ORDERS} (got {channel_order!r})")
+    if int(lanes) != lanes or not 0 <= int(lanes) <= 64:
+        raise ValueError(f"lanes must be 0 or a whole number in 1..64 (got {lanes!r})")
+    if int(chunk) != chunk or int(chunk) < 1 or int(chunk) > 65535:
+        raise ValueError(f"chunk must be a whole number in 1..65535 (got {chunk!r})")
+    headers = parse_all(files, names)
+    F, H, W = len(headers), headers[0].height, headers[0].width
+    if return_coefficients and F > chunk:
+        raise ValueError(f"return_coefficients needs one round: {F} files, chunk {chunk}")
+    rec = build_records(headers, int(chunk))
+    if out is not None:
+        if not (isinstance(out, torch.Tensor) and out.is_cuda and out.dtype == torch.uint8 and tuple(out.shape) == (F, H, W, 3)
+                and out.is_contiguous()):
+            raise ValueError(f"out must be a contiguous uint8 device tensor [{F}, {H}, {W}, 3]")
+        dev = out.device
+    else:
+        dev = torch.device(device) if device is not None else torch.device("cuda", torch.cuda.current_device())
+    # one buffer, one upload: images | huffman | segments | quant | data, each part 16-byte aligned
+    parts = [rec["images"], rec["huffman"], rec["segments"], rec["quant"], rec["data"]]
+    offs, total = [], 0
+    for p in parts:
+        offs.append(total)
+        total += -(-p.nbytes // 16) * 16
+    pinned = torch.zeros(total, dtype=torch.uint8, pin_memory=True)          # staged in page-locked memory: the upload is asynchronous
+    host = pinned.numpy()
+    for p, o in zip(parts, offs):
+        host[o:o + p.nbytes] = p.reshape(-1).view(np.uint8)
+    n_seg = len(rec["segments"])
+    with torch.cuda.device(dev):
+        buf = pinned.to(dev, non_blocking=True)
+        frames = out if out is not None else torch.empty(F, H, W, 3, device=dev, dtype=torch.uint8)
+        status = torch.empty(F, device=dev, dtype=torch.int32)
+        seg_status = torch.empty(n_seg, device=dev, dtype=torch.int32)
+        n_blocks = max(r[4] for r in rec["rounds"])
+        plane_bytes = max(r[5] for r in rec["rounds"])
+        coef = torch.empty(n_blocks, 64, device=dev, dtype=torch.int16)
+        planes = torch.empty(max(plane_bytes, 64), device=dev, dtype=torch.uint8)
+        p_img, p_huf, p_seg, p_q, p_data = (C.c_void_p(buf.data_ptr() + o) for o in offs)
+        lib, stream = _lib.load(), _lib.current_stream()
+
+        def timed(stage, fn):
+            if timings is None:
+                return fn()
+            e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+            e0.record()
+            fn()
+            e1.record()
+            timings.append((stage, e0, e1))
+
+        for i0, ni, s0, ns, nb, pb, mb in rec["rounds"]:
+            timed("entropy", lambda: _lib.check(lib.pmce_jpeg_entropy(
+                p_data, len(rec["data"]), p_seg, s0, ns, p_img, F, p_huf, len(rec["huffman"]), _lib.ptr(coef), nb, _lib.ptr(seg_status),
+                1 if lds_tables else 0, int(lanes), stream), "jpeg_entropy"))
+            timed("idct", lambda: _lib.check(lib.pmce_jpeg_idct(
+                _lib.ptr(coef), p_img, i0, ni, mb, p_q, len(rec["quant"]), nb, _lib.ptr(planes), max(pb, 64), stream), "jpeg_idct"))
+            timed("colour", lambda: _lib.check(lib.pmce_jpeg_colour(
+                _lib.ptr(planes), max(pb, 64), p_img, i0, ni, _lib.ptr(seg_status), n_seg, W, H, 1 if channel_order == "rgb" else 0,
+                _lib.ptr(frames), _lib.ptr(status), stream), "jpeg_colour"))
+    if return_coefficients:
+        return frames, status, coef[:rec["rounds"][0][4]]
+    return frames, status
+
+
+def dump_records(files, path, coefficients=None, names=None):
+    """Write the records of ``files`` (one round: every image in one coefficient buffer) as the binary file scripts/jpeg_entropy_host.cpp
+    reads: the magic "PMCEJPG1"; int64 x 7 = (bytes, images, quantisation tables, Huffman tables, segments, blocks, 1 if coefficients
+    follow); then images int32, huffman int32, segments int32, quant uint16, data uint8 and, if given, ``coefficients`` int16
+    [blocks, 64] (the expected output of the entropy stage, in its layout) - little-endian, no padding.  The files need not be of one
+    size: only the entropy stage reads these records."""
+    headers = parse_all(files, names, same_size=False)
+    rec = build_records(headers, len(headers))
+    n_blocks = rec["rounds"][0][4]
+    if coefficients is not None:
+        coefficients = np.ascontiguousarray(coefficients, dtype=np.int16)
+        if coefficients.shape != (n_blocks, 64):
+            raise ValueError(f"coefficients must be [{n_blocks}, 64] (got {coefficients.shape})")
+    with open(path, "wb") as fh:
+        fh.write(DUMP_MAGIC)
+        fh.write(struct.pack("<7q", len(rec["data"]), len(headers), len(rec["quant"]), len(rec["huffman"]), len(rec["segments"]), n_blocks,
+                             0 if coefficients is None else 1))
+        for key in ("images", "huffman", "segments", "quant", "data"):
+            fh.write(np.ascontiguousarray(rec[key]).astype(rec[key].dtype.newbyteorder("<"), copy=False).tobytes())
+        if coefficients is not None:
+            fh.write(coefficients.astype("<i2", copy=False).tobytes())
+    return rec
