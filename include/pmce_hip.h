@@ -935,6 +935,31 @@ int pmce_tracklet_boxes_f64(const double* tracks, const int* index, int total, i
 int pmce_jpeg_entropy(const unsigned char* data, long long n_bytes, const int* segments, int first_segment, int n_segments,
                       const int* images, int n_images, const int* huffman, int n_huffman, short* coefficients, long long n_blocks,
                       int* segment_status, int lds_tables, int lanes, pmce_stream_t stream);
+/* pmce_jpeg_entropy_parallel (csrc/jpeg_parallel.hip, csrc/jpeg_parallel.hpp): pmce_jpeg_entropy's result - the same coefficients and
+ *   the same segment_status words for every byte string - with many lanes per segment, for files with few restart markers or none.
+ *   A segment of n bytes is cut into max(1, ceil(n / subsequence)) subsequences of `subsequence` bytes (a multiple of 4 in 4 .. 65536),
+ *   one lane each; pmce_jpeg_parallel_run() (256) consecutive ones of a segment are a run, one workgroup.  Lanes decode from guessed
+ *   states and synchronise (Weissenberger and Schmidt, ICPP 2018): run by run in LDS, then twice across the runs' borders; a check
+ *   of the fixed-point condition hands a segment that has not converged to the serial body, so the result is exact for every stream.
+ *   offsets[segment][2]         int32, for every segment of the batch: its first subsequence and its first run, both counted from
+ *                               the first segment of the round it is decoded in (pmce_amd.jpeg.subsequence_records).
+ *   n_subsequences, n_runs      of the segments [first_segment, first_segment + n_segments) together.
+ *   workspace                   8-byte aligned, 32 bytes per subsequence + 28 per run + 8 per segment, in this order: entry[n_subsequences]
+ *                               and exit[n_subsequences] (64 bits each: byte position | bit << 32 | block in MCU << 35 | zigzag index
+ *                               << 38, bit 63: ended), border[2][n_runs] (64 bits), then int32: rounds[3][n_runs] (per synchronising
+ *                               launch, the rounds in which a lane of the run decoded again), per subsequence the blocks it completed,
+ *                               its first block, its status and its DC extent, then serial[n_segments] (1: handed to the serial body)
+ *                               and stop[n_segments] (the first lane with a code error: the lanes behind it write nothing).
+ *   stage                       -1: everything (the coefficients' memset and pmce_jpeg_parallel_stages() launches); 0 .. stages - 1:
+ *                               that launch alone, for timing - 0 sync (with the memset), 1 .. 2 join, 3 place, 4 write, 5 dc.
+ *   No atomics, no host read or wait; the number of launches depends on nothing but `stage`. */
+int pmce_jpeg_entropy_parallel(const unsigned char* data, long long n_bytes, const int* segments, int first_segment, int n_segments,
+                               const int* images, int n_images, const int* huffman, int n_huffman, short* coefficients,
+                               long long n_blocks, int* segment_status, int lds_tables, int subsequence, const int* offsets,
+                               int n_subsequences, int n_runs, void* workspace, long long workspace_bytes, int stage,
+                               pmce_stream_t stream);
+int pmce_jpeg_parallel_run(void);
+int pmce_jpeg_parallel_stages(void);
 int pmce_jpeg_idct(const short* coefficients, const int* images, int first_image, int n_images, int max_blocks,
                    const unsigned short* quant, int n_quant, long long n_blocks, unsigned char* planes, long long plane_bytes,
                    pmce_stream_t stream);

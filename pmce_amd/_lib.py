@@ -174,6 +174,9 @@ PROTOTYPES = {
     "pmce_tracklet_boxes_f64": [_f, _f, _i, _i, _f, _s],
     "pmce_sort_track_f64": [_f, _f, C.POINTER(C.c_int), _f, _i, _i, _i, _i, _i, _d, _i, _i, _f, _f, _f, _s],
     "pmce_jpeg_entropy": [_f, _l, _f, _i, _i, _f, _i, _f, _i, _f, _l, _f, _i, _i, _s],
+    "pmce_jpeg_entropy_parallel": [_f, _l, _f, _i, _i, _f, _i, _f, _i, _f, _l, _f, _i, _i, _f, _i, _i, _f, _l, _i, _s],
+    "pmce_jpeg_parallel_run": [],
+    "pmce_jpeg_parallel_stages": [],
     "pmce_jpeg_idct": [_f, _f, _i, _i, _i, _f, _i, _l, _f, _l, _s],
     "pmce_jpeg_colour": [_f, _l, _f, _i, _i, _f, _i, _i, _i, _i, _f, _f, _s],
 }

@@ -312,7 +312,7 @@ def run_frames(model, frames, tracker, pose, extractor, img_wh, min_frames: int 
     return outs
 
 
-def load_frames(folder, device=None, strict: bool = True, chunk: int = 32):
+def load_frames(folder, device=None, strict: bool = True, chunk: int = 32, entropy: str = "auto"):
     """The frames of a folder of JPEG files, as the reference's demo first sees its video (lib/utils/demo_utils.py:101-121 has ffmpeg
     write ``%06d.jpg``) -> (frames uint8 [F, H, W, 3] on the device, channels B, G, R as ``cv2.imread`` leaves them, (width, height),
     the file names in frame order).  The files ending in .jpg or .jpeg (any letter case) are taken, sorted by name as
@@ -320,9 +320,9 @@ def load_frames(folder, device=None, strict: bool = True, chunk: int = 32):
     A .png in the folder is a ValueError (PNG is not served), as are an empty folder, files of unequal size and every file
     ``jpeg.parse`` refuses.  ``strict``: make the one host read of the decoder's status and raise, naming the first file whose
     scan was truncated or corrupt; without it such a frame is returned as far as it decoded.  An Exif orientation tag is not read
-    (``cv2.imread`` would rotate such a file; ffmpeg's frames carry none).  ``chunk``: images per round of the decoder (``jpeg.decode``);
-    files without restart markers - what ffmpeg writes - decode one lane per image, so raise it as far as memory allows (9.4 MB of
-    workspace per 1080p image)."""
+    (``cv2.imread`` would rotate such a file; ffmpeg's frames carry none).  ``chunk``: images per round of the decoder (``jpeg.decode``; 9.4 MB of
+    workspace per 1080p image).  ``entropy``: ``jpeg.decode``'s - "auto" gives files without restart markers, which is what ffmpeg
+    writes, the entropy stage with many lanes per scan; "serial" and "parallel" force one stage.  The same frames either way."""
     import os
     from . import jpeg
     entries = sorted(os.listdir(folder))
@@ -336,7 +336,8 @@ def load_frames(folder, device=None, strict: bool = True, chunk: int = 32):
     for x in names:
         with open(os.path.join(folder, x), "rb") as fh:
             files.append(fh.read())
-    frames, status = jpeg.decode(files, device, channel_order="bgr", chunk=chunk, names=[os.path.join(folder, x) for x in names])
+    frames, status = jpeg.decode(files, device, channel_order="bgr", chunk=chunk, names=[os.path.join(folder, x) for x in names],
+                                 entropy=entropy)
     if strict:
         st = status.cpu().numpy()
         bad = np.flatnonzero(st)
@@ -347,9 +348,11 @@ def load_frames(folder, device=None, strict: bool = True, chunk: int = 32):
     return frames, (int(frames.shape[2]), int(frames.shape[1])), names
 
 
-def run_folder(model, folder, tracker, pose, extractor, device=None, strict: bool = True, chunk: int = 32, **run_frames_kwargs):
-    """``load_frames`` then ``run_frames``, with ``img_wh`` taken from the files -> ``run_frames``' dicts."""
-    frames, img_wh, _ = load_frames(folder, device=device, strict=strict, chunk=chunk)
+def run_folder(model, folder, tracker, pose, extractor, device=None, strict: bool = True, chunk: int = 32, entropy=None,
+               **run_frames_kwargs):
+    """``load_frames`` then ``run_frames``, with ``img_wh`` taken from the files -> ``run_frames``' dicts.  ``entropy``: passed to
+    ``load_frames``; None leaves it at ``load_frames``' default ("auto")."""
+    frames, img_wh, _ = load_frames(folder, device=device, strict=strict, chunk=chunk, **({} if entropy is None else dict(entropy=entropy)))
     return run_frames(model, frames, tracker, pose, extractor, img_wh, **run_frames_kwargs)
 
 

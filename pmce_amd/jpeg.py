@@ -34,6 +34,12 @@ IMG_WORDS, SEG_WORDS, HUFF_WORDS = 24, 5, 546          # csrc/jpeg_entropy.hpp, 
 HUFF_MAXCODE, HUFF_VALOFF, HUFF_VALUES, HUFF_LOOK = 0, 17, 34, 290
 STATUS_TRUNCATED, STATUS_CORRUPT, STATUS_RECORD = 1, 2, 4
 CHANNEL_ORDERS = ("bgr", "rgb")
+ENTROPY_MODES = ("auto", "serial", "parallel")
+PARALLEL_RUN = 256                     # subsequences per workgroup of the parallel entropy stage (csrc/jpeg_parallel.hpp, RUN)
+PARALLEL_STAGES = ("sync", "join", "join", "place", "write", "dc")       # its launches, as ``timings`` names them ("entropy_" in front)
+MIN_SUBSEQUENCE, MAX_SUBSEQUENCE = 4, 1 << 16
+DEFAULT_SUBSEQUENCE = 128              # bytes per lane of the parallel entropy stage: the fastest of the sweep in profiles/jpeg_bench.json
+AUTO_THRESHOLD = 4096                  # "auto": a round whose longest segment has at least this many bytes takes the parallel stage
 DUMP_MAGIC = b"PMCEJPG1"
 
 _SOF_NAMES = {0xC2: "progressive (SOF2)", 0xC3: "lossless (SOF3)", 0xC5: "differential sequential (SOF5)",
@@ -321,6 +327,48 @@ def build_records(headers, chunk: int) -> dict:
                 segments=np.concatenate(segs).astype(np.int32), rounds=rounds)
 
 
+def subsequence_records(rec: dict, subsequence: int) -> dict:
+    """What the parallel entropy stage needs beside ``build_records``' arrays (include/pmce_hip.h): ``offsets`` int32 [S, 2], per
+    segment its first subsequence and its first run (``PARALLEL_RUN`` subsequences), both counted from the first segment of the
+    segment's round; ``totals``: per round (subsequences, runs, the longest segment's bytes).  A segment of n bytes has
+    max(1, ceil(n / subsequence)) subsequences."""
+    seg = rec["segments"].astype(np.int64)
+    length = seg[:, 2] - seg[:, 1]
+    n_sub = np.maximum(1, -(-length // subsequence))
+    n_run = -(-n_sub // PARALLEL_RUN)
+    offsets = np.zeros((len(seg), 2), dtype=np.int64)
+    totals = []
+    for _, _, s0, ns, *_ in rec["rounds"]:
+        offsets[s0:s0 + ns, 0] = np.cumsum(n_sub[s0:s0 + ns]) - n_sub[s0:s0 + ns]
+        offsets[s0:s0 + ns, 1] = np.cumsum(n_run[s0:s0 + ns]) - n_run[s0:s0 + ns]
+        totals.append((int(n_sub[s0:s0 + ns].sum()), int(n_run[s0:s0 + ns].sum()), int(length[s0:s0 + ns].max())))
+    return dict(offsets=offsets.astype(np.int32), totals=totals)
+
+
+def parallel_workspace_bytes(n_sub: int, n_runs: int, n_seg: int) -> int:
+    """The parallel entropy stage's workspace for one round (include/pmce_hip.h)."""
+    return 32 * n_sub + 28 * n_runs + 8 * n_seg
+
+
+def parallel_diagnostics(diagnostics) -> dict:
+    """What ``decode(..., diagnostics=[])`` collected, read back (a host wait): over all rounds that took the parallel stage, the
+    largest number of rounds in which a lane of a run decoded again, per synchronising launch (sync, join, join), the runs in which the
+    last join still changed a lane, and the segments handed to the serial body."""
+    most, late, serial, runs, segments = [0, 0, 0], 0, 0, 0, 0
+    for ws, n_sub, n_runs, n_seg in diagnostics:
+        words = ws.cpu().numpy().view(np.int32)
+        at = (16 * n_sub + 16 * n_runs) // 4
+        rounds = words[at:at + 3 * n_runs].reshape(3, n_runs)
+        most = [max(m, int(r.max())) for m, r in zip(most, rounds)]
+        late += int((rounds[2] > 0).sum())
+        at += 3 * n_runs + 4 * n_sub
+        serial += int(words[at:at + n_seg].sum())
+        runs += n_runs
+        segments += n_seg
+    return dict(rounds_max_sync=most[0], rounds_max_join_1=most[1], rounds_max_join_2=most[2], runs=runs, runs_changed_by_the_last_join=late,
+                segments=segments, segments_handed_to_the_serial_body=serial)
+
+
 def parse_all(files, names=None, same_size: bool = True):
     """``parse`` of every file of one batch; with ``same_size`` all must have one size, else ValueError names the first file that differs."""
     if len(files) == 0:
@@ -337,7 +385,8 @@ def parse_all(files, names=None, same_size: bool = True):
 
 
 def decode(files, device=None, channel_order: str = "bgr", chunk: int = 32, out=None, names=None, return_coefficients: bool = False,
-           timings=None, lds_tables: bool = True, lanes: int = 0):
+           timings=None, lds_tables: bool = True, lanes: int = 0, entropy: str = "auto", subsequence: int = 0,
+           diagnostics=None):
     """files: a list of ``bytes``, one JPEG file each, all of one size -> (frames uint8 [F, H, W, 3] on ``device``, status int32 [F] on
     the device), by pmce_jpeg_entropy / _idct / _colour on the current stream, ``chunk`` images per round through one workspace
     (2 bytes of coefficients and 1 of planes per padded sample: 9.4 MB per 1080p 4:2:0 image), after ONE upload of the files' bytes and their records.
@@ -348,7 +397,14 @@ def decode(files, device=None, channel_order: str = "bgr", chunk: int = 32, out=
     (stage, start event, end event) per launch, for scripts/bench_jpeg.py.  ``lds_tables=False``: the entropy stage reads the Huffman
     tables from global memory even where they would fit into LDS (at most 16 distinct tables in the batch) - the same bits, slower;
     the form a batch with more tables takes anyway.  ``lanes``: segments per wavefront of the entropy stage, 1..64, or 0 for the
-    library's choice (one until a round has more than 4096 segments) - the same bits whatever it is."""
+    library's choice (one until a round has more than 4096 segments) - the same bits whatever it is.  ``entropy``: "serial" is
+    pmce_jpeg_entropy, one lane per restart interval; "parallel" is pmce_jpeg_entropy_parallel (csrc/jpeg_parallel.hip), many lanes per
+    interval that start from guessed states and synchronise - the same coefficients and status words for every file, damaged ones
+    included; "auto" takes the parallel stage for every round whose longest segment has at least ``AUTO_THRESHOLD`` bytes (what ffmpeg
+    and ``cv2.imwrite`` write: no restart markers).  ``subsequence``: bytes per lane of the parallel stage, a multiple of 4 in
+    4 .. 65536, or 0 for ``DEFAULT_SUBSEQUENCE`` - the same bits whatever it is.  ``timings`` names the parallel stage's launches
+    "entropy_sync", "entropy_join" (twice), "entropy_place", "entropy_write" and "entropy_dc".  ``diagnostics``: a list that receives a
+    copy of the parallel stage's workspace per round (made on the device, not waited for), for ``parallel_diagnostics``."""
     import torch
     if channel_order not in CHANNEL_ORDERS:
         raise ValueError(f"channel_order must be one of {CHANNEL_ORDERS} (got {channel_order!r})")
@@ -356,6 +412,12 @@ def decode(files, device=None, channel_order: str = "bgr", chunk: int = 32, out=
         raise ValueError(f"lanes must be 0 or a whole number in 1..64 (got {lanes!r})")
     if int(chunk) != chunk or int(chunk) < 1 or int(chunk) > 65535:
         raise ValueError(f"chunk must be a whole number in 1..65535 (got {chunk!r})")
+    if entropy not in ENTROPY_MODES:
+        raise ValueError(f"entropy must be one of {ENTROPY_MODES} (got {entropy!r})")
+    if isinstance(subsequence, bool) or int(subsequence) != subsequence or not (
+            int(subsequence) == 0 or (MIN_SUBSEQUENCE <= int(subsequence) <= MAX_SUBSEQUENCE and int(subsequence) % 4 == 0)):
+        raise ValueError(f"subsequence must be 0 or a multiple of 4 in {MIN_SUBSEQUENCE}..{MAX_SUBSEQUENCE} (got {subsequence!r})")
+    subsequence = int(subsequence) or DEFAULT_SUBSEQUENCE
     headers = parse_all(files, names)
     F, H, W = len(headers), headers[0].height, headers[0].width
     if return_coefficients and F > chunk:
@@ -368,8 +430,10 @@ def decode(files, device=None, channel_order: str = "bgr", chunk: int = 32, out=
         dev = out.device
     else:
         dev = torch.device(device) if device is not None else torch.device("cuda", torch.cuda.current_device())
-    # one buffer, one upload: images | huffman | segments | quant | data, each part 16-byte aligned
-    parts = [rec["images"], rec["huffman"], rec["segments"], rec["quant"], rec["data"]]
+    sub = subsequence_records(rec, subsequence)
+    parallel = [entropy == "parallel" or (entropy == "auto" and longest >= AUTO_THRESHOLD) for _, _, longest in sub["totals"]]
+    # one buffer, one upload: images | huffman | segments | quant | data | offsets, each part 16-byte aligned
+    parts = [rec["images"], rec["huffman"], rec["segments"], rec["quant"], rec["data"], sub["offsets"]]
     offs, total = [], 0
     for p in parts:
         offs.append(total)
@@ -388,8 +452,11 @@ def decode(files, device=None, channel_order: str = "bgr", chunk: int = 32, out=
         plane_bytes = max(r[5] for r in rec["rounds"])
         coef = torch.empty(n_blocks, 64, device=dev, dtype=torch.int16)
         planes = torch.empty(max(plane_bytes, 64), device=dev, dtype=torch.uint8)
-        p_img, p_huf, p_seg, p_q, p_data = (C.c_void_p(buf.data_ptr() + o) for o in offs)
+        p_img, p_huf, p_seg, p_q, p_data, p_off = (C.c_void_p(buf.data_ptr() + o) for o in offs)
         lib, stream = _lib.load(), _lib.current_stream()
+        ws_bytes = max([parallel_workspace_bytes(t[0], t[1], r[3]) for t, r, par in zip(sub["totals"], rec["rounds"], parallel) if par],
+                       default=0)
+        workspace = torch.empty(ws_bytes, device=dev, dtype=torch.uint8) if ws_bytes else None
 
         def timed(stage, fn):
             if timings is None:
@@ -400,10 +467,24 @@ def decode(files, device=None, channel_order: str = "bgr", chunk: int = 32, out=
             e1.record()
             timings.append((stage, e0, e1))
 
-        for i0, ni, s0, ns, nb, pb, mb in rec["rounds"]:
-            timed("entropy", lambda: _lib.check(lib.pmce_jpeg_entropy(
+        def entropy_parallel(s0, ns, nb, n_sub, n_runs, stage):
+            _lib.check(lib.pmce_jpeg_entropy_parallel(
                 p_data, len(rec["data"]), p_seg, s0, ns, p_img, F, p_huf, len(rec["huffman"]), _lib.ptr(coef), nb, _lib.ptr(seg_status),
-                1 if lds_tables else 0, int(lanes), stream), "jpeg_entropy"))
+                1 if lds_tables else 0, subsequence, p_off, n_sub, n_runs, _lib.ptr(workspace), ws_bytes, stage, stream),
+                "jpeg_entropy_parallel")
+
+        for (i0, ni, s0, ns, nb, pb, mb), (n_sub, n_runs, _), par in zip(rec["rounds"], sub["totals"], parallel):
+            if not par:
+                timed("entropy", lambda: _lib.check(lib.pmce_jpeg_entropy(
+                    p_data, len(rec["data"]), p_seg, s0, ns, p_img, F, p_huf, len(rec["huffman"]), _lib.ptr(coef), nb, _lib.ptr(seg_status),
+                    1 if lds_tables else 0, int(lanes), stream), "jpeg_entropy"))
+            elif timings is None:
+                entropy_parallel(s0, ns, nb, n_sub, n_runs, -1)
+            else:                                  # launch by launch, so that each has its events
+                for stage, name in enumerate(PARALLEL_STAGES):
+                    timed("entropy_" + name, lambda: entropy_parallel(s0, ns, nb, n_sub, n_runs, stage))
+            if par and diagnostics is not None:
+                diagnostics.append((workspace[:parallel_workspace_bytes(n_sub, n_runs, ns)].clone(), n_sub, n_runs, ns))
             timed("idct", lambda: _lib.check(lib.pmce_jpeg_idct(
                 _lib.ptr(coef), p_img, i0, ni, mb, p_q, len(rec["quant"]), nb, _lib.ptr(planes), max(pb, 64), stream), "jpeg_idct"))
             timed("colour", lambda: _lib.check(lib.pmce_jpeg_colour(

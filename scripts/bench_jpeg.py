@@ -1,6 +1,10 @@
 #!/usr/bin/env python3
 """Time of pmce_amd.jpeg.decode on the demo's video: 300 frames of 1920 x 1080, 4:2:0, in two forms - without restart markers (what
-ffmpeg and cv2.imwrite write: one entropy-decoding lane per image) and with one restart interval per MCU row (68 lanes per image).
+ffmpeg and cv2.imwrite write: one segment per image) and with one restart interval per MCU row (68 segments per image).  The first
+three entries take the library's defaults (``entropy="auto"``); beside them each form is run with the serial entropy stage (one lane
+per segment) and with the parallel one (many lanes per segment, csrc/jpeg_parallel.hip), and the form without markers with the
+parallel stage at several subsequence sizes; the parallel entries also carry how the synchronisation went
+(``jpeg.parallel_diagnostics``).
 Four distinct frames (a smooth colour field, texture, noise, a saturated patch) are encoded once per form - with Pillow where it
 imports, otherwise with the small encoder of tests/jpeg_ref.py - and repeated to 300.  The form without markers is also run with all 300 images in ONE round (``chunk`` = 300: its parallelism is the
 number of images in flight, and so is its workspace).  Per entry: the median of ``--passes`` (>= 5)
@@ -26,10 +30,11 @@ REPO = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, REPO)
 sys.path.insert(0, os.path.join(REPO, "tests"))
 
-STEPS = (("device", 900), ("pillow", 600))               # (name, timeout in seconds)
+STEPS = (("device", 1100), ("pillow", 600))               # (name, timeout in seconds)
 WH = (1920, 1080)
 QUALITY = 85
 FORMS = ("no_restart_markers", "restart_interval_per_mcu_row")
+SWEEP = (32, 64, 128, 256, 512)                          # subsequence sizes of the parallel entropy stage
 
 
 def clock_now():
@@ -97,16 +102,20 @@ def step_device(args):
         pillow = None
     # (entry, form, images per round): the default chunk for both forms, and the form without markers with every image in one round
     # (its parallelism is the number of images in flight; the workspace grows with it: 3 bytes per padded sample, 9.4 MB per image here)
-    for entry, form, chunk in ((FORMS[0], FORMS[0], args.chunk), (FORMS[1], FORMS[1], args.chunk),
-                               (FORMS[0] + "_one_round", FORMS[0], args.frames)):
+    entries = [(FORMS[0], FORMS[0], args.chunk, {}), (FORMS[1], FORMS[1], args.chunk, {}),
+               (FORMS[0] + "_one_round", FORMS[0], args.frames, {})]
+    for form in FORMS:
+        entries += [(f"{form}_{mode}", form, args.chunk, dict(entropy=mode)) for mode in ("serial", "parallel")]
+    entries += [(f"{FORMS[0]}_parallel_subsequence_{S}", FORMS[0], args.chunk, dict(entropy="parallel", subsequence=S)) for S in SWEEP]
+    for entry, form, chunk, kw in entries:
         files = files_of(forms[form], args.frames)
-        _, status = jpeg.decode(files, out=frames, chunk=chunk)              # warm-up: code objects, allocator
+        _, status = jpeg.decode(files, out=frames, chunk=chunk, **kw)        # warm-up: code objects, allocator
         torch.cuda.synchronize()
         assert not status.any().item(), "a bench frame has a status"
         walls = []
         for _ in range(args.passes):
             t0 = time.perf_counter()
-            jpeg.decode(files, out=frames, chunk=chunk)
+            jpeg.decode(files, out=frames, chunk=chunk, **kw)
             torch.cuda.synchronize()
             walls.append((time.perf_counter() - t0) * 1e3)
         clock = clock_now()
@@ -117,18 +126,25 @@ def step_device(args):
         stages = []
         for _ in range(args.passes):
             ev = []
-            jpeg.decode(files, out=frames, chunk=chunk, timings=ev)
+            jpeg.decode(files, out=frames, chunk=chunk, timings=ev, **kw)
             torch.cuda.synchronize()
             acc = {}
             for stage, a, b in ev:
                 acc[stage] = acc.get(stage, 0.0) + a.elapsed_time(b)
+                if stage.startswith("entropy_"):                    # the parallel stage's launches: "entropy" is their sum
+                    acc["entropy"] = acc.get("entropy", 0.0) + a.elapsed_time(b)
             stages.append(acc)
         med = float(np.median(walls))
         res = {"frames": args.frames, "passes": args.passes, "chunk": chunk, "bytes_in": int(sum(len(f) for f in files)),
                "segments": int(len(rec["segments"])), "decode_ms_median": round(med, 2), "decode_ms_min": round(min(walls), 2),
                "frames_per_s": round(args.frames / (med * 1e-3), 1), "host_parse_and_records_ms": round(host_ms, 2),
-               "stage_ms_median": {k: round(float(np.median([s[k] for s in stages])), 3) for k in ("entropy", "idct", "colour")},
-               "sclk_after": clock}
+               "stage_ms_median": {k: round(float(np.median([s[k] for s in stages])), 3) for k in stages[0]},
+               "entropy": kw.get("entropy", "auto"), "subsequence": kw.get("subsequence", 0) or jpeg.DEFAULT_SUBSEQUENCE,
+               "auto_threshold": jpeg.AUTO_THRESHOLD, "sclk_after": clock}
+        if any(k.startswith("entropy_") for k in stages[0]):
+            diag = []
+            jpeg.decode(files, out=frames, chunk=chunk, diagnostics=diag, **kw)
+            res["synchronisation"] = jpeg.parallel_diagnostics(diag)
         if pillow is not None:
             got = frames[:4].cpu().numpy()[..., ::-1]
             res["differing_samples_vs_pillow_on_the_four_frames"] = int((got != pillow[form]).sum())
