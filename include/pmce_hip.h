@@ -734,7 +734,7 @@ int pmce_hmr_joints_f32(const float* joints, const float* verts, const int* sel,
  *   calling thread's overflow sink.  Buffers 16-byte aligned.
  * pmce_layernorm_rows_f32: y = x + add[row % add_mod] (add NULL: y = x); out1 = y (optional; may be x);
  *   out = LayerNorm(y; w, b, eps) as fp32 [rows][C] or, out_split != 0, as planes.  C % 16 == 0, C <= 2048, any rows >= 1;
- *   two-pass fp32 mean and (biased) variance, one wave per row.
+ *   two-pass fp32 mean and (biased) variance, one wave per row.  A row whose variance overflows fp32 is NaN, not b.
  * pmce_deconv4x4s2_gather_f32: the gather half of ConvTranspose2d(Cin, Cout, 4, stride 2, padding 1) + BatchNorm + ReLU.  With
  *   Y[n H W][16 Cout] = X[n H W][Cin] W'^T, W'[(ky, kx, co)][ci] = W[ci][co][ky][kx] s[co] (one pmce_gemm_nt_split_f16 on the packed W'),
  *   out[n][oy][ox][co] = relu(sum Y[n][iy][ix][(ky, kx, co)] + bias[co]) over the pairs with oy = 2 iy - 1 + ky, ox = 2 ix - 1 + kx, summed

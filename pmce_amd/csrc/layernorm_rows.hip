@@ -54,7 +54,10 @@ __global__ __launch_bounds__(256) void layernorm_rows_kernel(const float* x, lon
       ss += (d0 * d0 + d1 * d1) + (d2 * d2 + d3 * d3);
     }
   }
-  const float inv = 1.0f / sqrtf(wave_sum(ss) / (float)C + eps);
+  // A variance beyond fp32 (one |x| past 1.8e19) makes the row NaN like any other overflow: 1 / sqrt(inf) = 0 would return b, a finite row
+  // that no check downstream could tell from a result.  Every finite variance takes the same arithmetic as before.
+  const float var = wave_sum(ss) / (float)C;
+  const float inv = var <= 3.402823466e+38f ? 1.0f / sqrtf(var + eps) : __builtin_nanf("");
 #pragma unroll
   for (int i = 0; i < NP; ++i) {
     const int p = lane + 64 * i;

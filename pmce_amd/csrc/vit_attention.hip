@@ -26,6 +26,7 @@
 // Bounds.  Keys and queries at or beyond N read the image's row N - 1 (clamped, never another image's rows or memory past the
 // tensor); such keys get a score of -inf and a zero V, such queries are not stored.  Nothing of an (image, head) depends on another
 // image or on n: a result row has the same bits wherever its image sits.
+// Every NT at its full tile and one past it, exact gathers and the fences: tests/test_gpu_vitpose_edges.py.
 #include "gemm_split_common.hpp"
 
 namespace {

@@ -177,6 +177,8 @@ def deconv_gather_host(y, bias, n, h, w):
         for kx in range(4):
             ix = [i for i in range(w) if 0 <= 2 * i - 1 + kx < 2 * w]
             ox = [2 * i - 1 + kx for i in ix]
+            if not iy or not ix:        # a one-pixel side: ky = 0 / 3 (kx = 0 / 3) falls outside the output
+                continue
             out[:, oy[0]:oy[-1] + 1:2, ox[0]:ox[-1] + 1:2] += y[:, iy[0]:iy[-1] + 1, ix[0]:ix[-1] + 1, ky, kx]
     return torch.relu(out + bias.to(y.dtype))
 

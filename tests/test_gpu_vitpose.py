@@ -17,6 +17,7 @@ FACTOR = VR.FACTOR
 NETS = {
     "hd80": dict(H=256, W=192, C=160, depth=2, heads=2, F1=32, F2=32, K=17),
     "hd64": dict(H=64, W=48, C=128, depth=1, heads=2, F1=32, F2=32, K=17),
+    "hd64_80tok": dict(H=160, W=128, C=128, depth=1, heads=2, F1=32, F2=32, K=17),     # 80 tokens: three key tiles inside the network
 }
 
 

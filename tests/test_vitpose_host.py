@@ -89,6 +89,25 @@ def test_deconvolution_is_a_product_and_a_gather(h, w):
         vitpose.deconv_weight_as_product(torch.zeros(3, 2, 3, 3))
 
 
+@pytest.mark.parametrize("h,w", [(1, 1), (1, 3), (3, 1)])
+def test_gather_definition_at_a_one_pixel_side(h, w):
+    """H = 1 or W = 1: every output pixel is a border pixel and ky = 0 / 3 (kx = 0 / 3) reaches no output row (column) at all."""
+    from pmce_amd import vitpose
+    g = torch.Generator().manual_seed(10 * h + w)
+    n, cin, cout = 2, 24, 16
+    x = torch.randn(n, cin, h, w, generator=g, dtype=torch.float64)
+    wt = torch.randn(cin, cout, 4, 4, generator=g, dtype=torch.float64) / 8
+    bias = torch.randn(cout, generator=g, dtype=torch.float64) * 0.3
+    want = F.relu(F.conv_transpose2d(x, wt, bias, stride=2, padding=1))
+    y = x.permute(0, 2, 3, 1).reshape(n * h * w, cin) @ vitpose.deconv_weight_as_product(wt).T
+    got = vitpose.deconv_gather_host(y, bias, n, h, w).permute(0, 3, 1, 2)
+    assert got.shape == want.shape == (n, cout, 2 * h, 2 * w)
+    err = float((got - want).abs().max())
+    print(f"deconvolution {h} x {w}: max error {err:.2e}")
+    assert err <= 1e-12
+    assert 0.2 < float((want > 0).double().mean()) < 0.8
+
+
 def test_synthetic_attention_is_neither_uniform_nor_one_hot():
     """The reference's attention rows at the demo's 192 tokens, on the synthetic spec: the median of their largest probability lies
     between 0.02 (well above the uniform 1 / 192) and 0.9 (below one-hot)."""
