@@ -967,6 +967,42 @@ int pmce_jpeg_colour(const unsigned char* planes, long long plane_bytes, const i
                      const int* segment_status, int n_segments_total, int width, int height, int rgb, unsigned char* frames, int* status,
                      pmce_stream_t stream);
 
+/* ---------------------------------------------------------------------------------------------------------
+ * The demo's frames written as JPEG files (csrc/jpeg_encode.hip, csrc/jpeg_encode.hpp): baseline Huffman JFIF, YCbCr 4:4:4 / 4:2:2 /
+ * 4:2:0 in one interleaved scan, Annex K's Huffman tables, the bytes that libjpeg's default compressor (and with it cv2.imwrite) writes:
+ * jccolor's fixed-point conversion, jcsample's box filter, jccoefct's dummy blocks, jfdctint "islow", the rounding quantiser.  Integer
+ * arithmetic, no host wait; the same bytes whatever the batch.  pmce_amd/jpeg.py builds the header and the quantisation tables on the host.
+ *
+ * coefficients             int16 [frames][blocks][64] in ZIGZAG order; a frame's blocks in scan order: MCU by MCU, inside an MCU the
+ *                          luma blocks (v rows of h), then Cb, then Cr; the dummy blocks of the right and bottom edge included.
+ * workspace                16-byte aligned, pmce_jpeg_encode_workspace_bytes(): the unstuffed stream - per restart interval (per frame
+ *                          without one) a slot of 208 bytes per block, rounded up to 256 - then per block its bits (int32) and its bit
+ *                          offset in the slot (int64), per interval its bits (int64), per 256-byte piece of a slot its bytes in the file
+ *                          (int32) and its place in the file (int64), per frame the scan's length (int64).
+ * data, offsets, status    the files back to back: frame f is data[offsets[f] .. offsets[f + 1]); offsets int64 [all frames + 1],
+ *                          status int32 [all frames], both indexed by the absolute frame number.  A frame whose file would be longer
+ *                          than `capacity`, or end beyond data_bytes, has length 0 and PMCE_JPEG_ENCODE_STATUS_CAPACITY.
+ *
+ * pmce_jpeg_encode_coefficients: frames [first_frame, first_frame + n_frames) of uint8 frames[..][height][width][3] (B, G, R; R, G, B with
+ *   rgb != 0) -> coefficients (16-byte aligned, room for n_blocks >= n_frames * blocks); quant: uint16 [2][64], natural order, luma then
+ *   chroma, entries 1 .. 255; h, v: the luma sampling, 1x1, 2x1 or 2x2.
+ * pmce_jpeg_encode_entropy: the entropy stages alone, on coefficients as above (n_frames of mcus_per_frame MCUs, luma_blocks = h v luma
+ *   blocks each; values beyond +-2047 (DC difference) and +-1023 (AC) are clamped) -> data, offsets[first_frame + 1 ..], status[first_frame ..];
+ *   offsets[first_frame] is read (written as 0 for first_frame 0), so calls follow each other on one stream.  header: the file's bytes up to
+ *   the scan, on the device, the same for every frame; restart_interval in MCUs, 0: none.  stage: -1 everything; 0 .. pmce_jpeg_encode_stages()
+ *   - 1: that launch alone, for timing - 0 lengths, 1 offsets, 2 bits (with the stream's memset), 3 count, 4 place, 5 frames, 6 write.
+ * pmce_jpeg_encode_scan_pass(): entries per pass of the offset scan (an interval with more blocks takes several passes). */
+#define PMCE_JPEG_ENCODE_STATUS_CAPACITY 1
+int pmce_jpeg_encode_scan_pass(void);
+int pmce_jpeg_encode_stages(void);
+size_t pmce_jpeg_encode_workspace_bytes(int n_frames, long long mcus_per_frame, int luma_blocks, int restart_interval);
+int pmce_jpeg_encode_coefficients(const unsigned char* frames, long long first_frame, int n_frames, int width, int height, int h, int v,
+                                  int rgb, const unsigned short* quant, short* coefficients, long long n_blocks, pmce_stream_t stream);
+int pmce_jpeg_encode_entropy(const short* coefficients, int n_frames, long long mcus_per_frame, int luma_blocks, int restart_interval,
+                             const unsigned char* header, int header_bytes, long long capacity, void* workspace, size_t workspace_bytes,
+                             unsigned char* data, long long data_bytes, long long* offsets, int* status, long long first_frame, int stage,
+                             pmce_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif

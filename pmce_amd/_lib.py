@@ -179,6 +179,11 @@ PROTOTYPES = {
     "pmce_jpeg_parallel_stages": [],
     "pmce_jpeg_idct": [_f, _f, _i, _i, _i, _f, _i, _l, _f, _l, _s],
     "pmce_jpeg_colour": [_f, _l, _f, _i, _i, _f, _i, _i, _i, _i, _f, _f, _s],
+    "pmce_jpeg_encode_scan_pass": [],
+    "pmce_jpeg_encode_stages": [],
+    "pmce_jpeg_encode_workspace_bytes": [_i, _l, _i, _i],
+    "pmce_jpeg_encode_coefficients": [_f, _l, _i, _i, _i, _i, _i, _i, _f, _f, _l, _s],
+    "pmce_jpeg_encode_entropy": [_f, _i, _l, _i, _i, _f, _i, _l, C.c_void_p, C.c_size_t, _f, _l, _f, _f, _l, _i, _s],
 }
 _RESTYPES = {
     "pmce_last_error_string": C.c_char_p,
@@ -201,6 +206,7 @@ _RESTYPES = {
     "pmce_yolo_destroy": None,
     "pmce_yolo_workspace_units": C.c_longlong,
     "pmce_yolo_workspace_bytes": C.c_size_t,
+    "pmce_jpeg_encode_workspace_bytes": C.c_size_t,
 }
 
 _lib = None

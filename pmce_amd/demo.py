@@ -11,6 +11,8 @@ in, what the demo saves per person out - ``pred_cam``, ``mesh``, ``bboxes`` (``f
     outs = demo.run_frames(model, frames_u8, tracker.Tracker(yolo_net), pose, extractor, img_wh=(1920, 1080))   # the demo up to rendering
     frames_u8, (w, h), names = demo.load_frames("video_frames/")                               # a folder of .jpg files, decoded on the device
     outs = demo.run_folder(model, "video_frames/", tracker.Tracker(yolo_net), pose, extractor)  # load_frames, then run_frames
+    names = demo.save_frames("out_frames/", video)                                             # %06d.jpg, encoded on the device
+    outs = demo.render_folder(model, "video_frames/", "out_frames/", trk, pose, extractor, renderer, input_folder="in_frames/")   # folder in, folders out
 
 Per frame k the demo builds one window (``streaming.demo_window_list``), prepares the fit target from the window's middle frame
 (csrc/demo_prep.hip: add_pelvis_and_neck, get_bbox, process_bbox, j2d_processing), runs the model on the window and fits the
@@ -354,6 +356,42 @@ def run_folder(model, folder, tracker, pose, extractor, device=None, strict: boo
     ``load_frames``; None leaves it at ``load_frames``' default ("auto")."""
     frames, img_wh, _ = load_frames(folder, device=device, strict=strict, chunk=chunk, **({} if entropy is None else dict(entropy=entropy)))
     return run_frames(model, frames, tracker, pose, extractor, img_wh, **run_frames_kwargs)
+
+
+def save_frames(folder, frames, first: int = 0, names=None, **encode_kwargs):
+    """Write frames uint8 [F, H, W, 3] (device, B, G, R as every stage here holds them) into ``folder`` as JPEG files, encoded on the
+    device by ``jpeg.encode`` (csrc/jpeg_encode.hip): what main/run_demo.py:424-426 does with ``cv2.imwrite`` per frame.  The files are
+    named ``%06d.jpg`` counting from ``first``, as the reference names them, or by ``names`` (one per frame).  ``encode_kwargs`` go to
+    ``jpeg.encode`` (quality 95, 4:2:0 and no restart markers by default: ``cv2.imwrite``'s).  Only the files' bytes cross to the host.
+    A frame that did not fit ``capacity`` raises ``jpeg.files``' ValueError before anything is written.  -> the file names."""
+    import os
+    from . import jpeg
+    F = int(frames.shape[0])
+    names = [f"{int(first) + i:06d}.jpg" for i in range(F)] if names is None else [str(x) for x in names]
+    if len(names) != F:
+        raise ValueError(f"save_frames: {F} frames but {len(names)} names")
+    blobs = jpeg.files(*jpeg.encode(frames, **encode_kwargs))
+    os.makedirs(folder, exist_ok=True)
+    for name, blob in zip(names, blobs):
+        with open(os.path.join(folder, name), "wb") as fh:
+            fh.write(blob)
+    return names
+
+
+def render_folder(model, folder, out_folder, tracker, pose, extractor, renderer, input_folder=None, device=None, strict: bool = True,
+                  chunk: int = 32, entropy=None, order: str = "reference", encode_kwargs=None, **run_frames_kwargs):
+    """Folder in, folder out: ``load_frames``, ``run_frames``, ``render_tracklets`` and ``save_frames`` - the frames are decoded, drawn on
+    and encoded on the device.  The overlaid frames go to ``out_folder``; ``input_folder``, if given, receives the input frames again, as
+    main/run_demo.py:424-426 writes both folders for ffmpeg.  Both are named ``%06d.jpg`` from 0.  ``renderer``: a ``render.Renderer``
+    or the mesh's face array; ``encode_kwargs``: a dict for ``jpeg.encode``.  -> ``run_frames``' dicts."""
+    frames, img_wh, _ = load_frames(folder, device=device, strict=strict, chunk=chunk, **({} if entropy is None else dict(entropy=entropy)))
+    outs = run_frames(model, frames, tracker, pose, extractor, img_wh, **run_frames_kwargs)
+    rendered = render_tracklets(outs, frames, img_wh, renderer=renderer, order=order)
+    kw = dict(encode_kwargs or {})
+    save_frames(out_folder, rendered, **kw)
+    if input_folder is not None:
+        save_frames(input_folder, frames, **kw)
+    return outs
 
 
 @torch.no_grad()

@@ -18,6 +18,15 @@ An Exif orientation tag is NOT read: ``cv2.imread`` would rotate such a file, th
 ``status[f]`` is an OR of STATUS_TRUNCATED (the scan ended before its last MCU; zero bits are supplied beyond the end) and
 STATUS_CORRUPT (a code of no table, a run past coefficient 63, a marker inside a restart interval); ``decode`` does not read it.
 There is no fallback: without the library's kernels a call raises.
+
+The way back (csrc/jpeg_encode.hip), what the reference does with ``cv2.imwrite`` twice per frame (main/run_demo.py:424-426):
+
+    data, offsets, status = jpeg.encode(frames)                 # uint8 [F, H, W, 3] on the device -> baseline JFIF files on the device
+    blobs = jpeg.files(data, offsets, status)                   # list[bytes]: the one host read
+    header = jpeg.encode_header(width, height, quality, subsampling, restart_interval)      # host only
+
+YCbCr 4:4:4, 4:2:2 or 4:2:0, quality 1..100, Annex K's Huffman tables, restart intervals; the files are those of libjpeg's default
+compressor at the same settings, byte for byte.  Grey files, optimised or progressive tables and Exif are not written.
 """
 from __future__ import annotations
 
@@ -517,3 +526,228 @@ def dump_records(files, path, coefficients=None, names=None):
         if coefficients is not None:
             fh.write(coefficients.astype("<i2", copy=False).tobytes())
     return rec
+
+
+# ---------------------------------------------------------------------------------------------------------------------------------------
+# the writer (csrc/jpeg_encode.hip): frames on the device -> baseline JFIF files on the device, byte for byte libjpeg's default compressor
+# ---------------------------------------------------------------------------------------------------------------------------------------
+SUBSAMPLINGS = {"4:4:4": (1, 1), "4:2:2": (2, 1), "4:2:0": (2, 2)}
+STATUS_CAPACITY = 1                    # encode: the frame's file is longer than ``capacity``; it is served with length 0
+MAX_BLOCK_BYTES = 208                  # a block's code before stuffing: 20 bits of DC and 63 x 26 bits of AC (csrc/jpeg_encode.hpp)
+ENCODE_PIECE = 256                     # bytes of the unstuffed stream per lane group of the stuffing stage (csrc/jpeg_encode.hpp, PIECE)
+ENCODE_STAGES = ("lengths", "offsets", "bits", "count", "place", "frames", "write")        # the entropy entry's launches, as ``timings`` names them
+# T.81 Annex K.1 (natural order) and K.3 (counts of the lengths 1..16, values)
+K_LUMA_QUANT = (16, 11, 10, 16, 24, 40, 51, 61, 12, 12, 14, 19, 26, 58, 60, 55, 14, 13, 16, 24, 40, 57, 69, 56, 14, 17, 22, 29, 51, 87, 80,
+                62, 18, 22, 37, 56, 68, 109, 103, 77, 24, 35, 55, 64, 81, 104, 113, 92, 49, 64, 78, 87, 103, 121, 120, 101, 72, 92, 95, 98,
+                112, 100, 103, 99)
+K_CHROMA_QUANT = (17, 18, 24, 47, 99, 99, 99, 99, 18, 21, 26, 66, 99, 99, 99, 99, 24, 26, 56, 99, 99, 99, 99, 99, 47, 66, 99, 99, 99, 99,
+                  99, 99) + (99,) * 32
+K_ZIGZAG = (0, 1, 8, 16, 9, 2, 3, 10, 17, 24, 32, 25, 18, 11, 4, 5, 12, 19, 26, 33, 40, 48, 41, 34, 27, 20, 13, 6, 7, 14, 21, 28, 35, 42, 49,
+            56, 57, 50, 43, 36, 29, 22, 15, 23, 30, 37, 44, 51, 58, 59, 52, 45, 38, 31, 39, 46, 53, 60, 61, 54, 47, 55, 62, 63)
+K_DC_LUMA = ((0, 1, 5, 1, 1, 1, 1, 1, 1, 0, 0, 0, 0, 0, 0, 0), tuple(range(12)))
+K_DC_CHROMA = ((0, 3, 1, 1, 1, 1, 1, 1, 1, 1, 1, 0, 0, 0, 0, 0), tuple(range(12)))
+K_AC_LUMA = ((0, 2, 1, 3, 3, 2, 4, 3, 5, 5, 4, 4, 0, 0, 1, 125),
+             (0x01, 0x02, 0x03, 0x00, 0x04, 0x11, 0x05, 0x12, 0x21, 0x31, 0x41, 0x06, 0x13, 0x51, 0x61, 0x07, 0x22, 0x71, 0x14, 0x32, 0x81,
+              0x91, 0xA1, 0x08, 0x23, 0x42, 0xB1, 0xC1, 0x15, 0x52, 0xD1, 0xF0, 0x24, 0x33, 0x62, 0x72, 0x82, 0x09, 0x0A, 0x16, 0x17, 0x18,
+              0x19, 0x1A, 0x25, 0x26, 0x27, 0x28, 0x29, 0x2A, 0x34, 0x35, 0x36, 0x37, 0x38, 0x39, 0x3A, 0x43, 0x44, 0x45, 0x46, 0x47, 0x48,
+              0x49, 0x4A, 0x53, 0x54, 0x55, 0x56, 0x57, 0x58, 0x59, 0x5A, 0x63, 0x64, 0x65, 0x66, 0x67, 0x68, 0x69, 0x6A, 0x73, 0x74, 0x75,
+              0x76, 0x77, 0x78, 0x79, 0x7A, 0x83, 0x84, 0x85, 0x86, 0x87, 0x88, 0x89, 0x8A, 0x92, 0x93, 0x94, 0x95, 0x96, 0x97, 0x98, 0x99,
+              0x9A, 0xA2, 0xA3, 0xA4, 0xA5, 0xA6, 0xA7, 0xA8, 0xA9, 0xAA, 0xB2, 0xB3, 0xB4, 0xB5, 0xB6, 0xB7, 0xB8, 0xB9, 0xBA, 0xC2, 0xC3,
+              0xC4, 0xC5, 0xC6, 0xC7, 0xC8, 0xC9, 0xCA, 0xD2, 0xD3, 0xD4, 0xD5, 0xD6, 0xD7, 0xD8, 0xD9, 0xDA, 0xE1, 0xE2, 0xE3, 0xE4, 0xE5,
+              0xE6, 0xE7, 0xE8, 0xE9, 0xEA, 0xF1, 0xF2, 0xF3, 0xF4, 0xF5, 0xF6, 0xF7, 0xF8, 0xF9, 0xFA))
+K_AC_CHROMA = ((0, 2, 1, 2, 4, 4, 3, 4, 7, 5, 4, 4, 0, 1, 2, 119),
+               (0x00, 0x01, 0x02, 0x03, 0x11, 0x04, 0x05, 0x21, 0x31, 0x06, 0x12, 0x41, 0x51, 0x07, 0x61, 0x71, 0x13, 0x22, 0x32, 0x81,
+                0x08, 0x14, 0x42, 0x91, 0xA1, 0xB1, 0xC1, 0x09, 0x23, 0x33, 0x52, 0xF0, 0x15, 0x62, 0x72, 0xD1, 0x0A, 0x16, 0x24, 0x34,
+                0xE1, 0x25, 0xF1, 0x17, 0x18, 0x19, 0x1A, 0x26, 0x27, 0x28, 0x29, 0x2A, 0x35, 0x36, 0x37, 0x38, 0x39, 0x3A, 0x43, 0x44,
+                0x45, 0x46, 0x47, 0x48, 0x49, 0x4A, 0x53, 0x54, 0x55, 0x56, 0x57, 0x58, 0x59, 0x5A, 0x63, 0x64, 0x65, 0x66, 0x67, 0x68,
+                0x69, 0x6A, 0x73, 0x74, 0x75, 0x76, 0x77, 0x78, 0x79, 0x7A, 0x82, 0x83, 0x84, 0x85, 0x86, 0x87, 0x88, 0x89, 0x8A, 0x92,
+                0x93, 0x94, 0x95, 0x96, 0x97, 0x98, 0x99, 0x9A, 0xA2, 0xA3, 0xA4, 0xA5, 0xA6, 0xA7, 0xA8, 0xA9, 0xAA, 0xB2, 0xB3, 0xB4,
+                0xB5, 0xB6, 0xB7, 0xB8, 0xB9, 0xBA, 0xC2, 0xC3, 0xC4, 0xC5, 0xC6, 0xC7, 0xC8, 0xC9, 0xCA, 0xD2, 0xD3, 0xD4, 0xD5, 0xD6,
+                0xD7, 0xD8, 0xD9, 0xDA, 0xE2, 0xE3, 0xE4, 0xE5, 0xE6, 0xE7, 0xE8, 0xE9, 0xEA, 0xF2, 0xF3, 0xF4, 0xF5, 0xF6, 0xF7, 0xF8,
+                0xF9, 0xFA))
+
+
+def quant_tables(quality: int):
+    """``jpeg_set_quality(quality, force_baseline)`` on Annex K.1's tables -> (luma, chroma), int64 [64] each, natural order."""
+    if isinstance(quality, bool) or int(quality) != quality or not 1 <= int(quality) <= 100:
+        raise ValueError(f"quality must be a whole number in 1..100 (got {quality!r})")
+    quality = int(quality)
+    scale = 5000 // quality if quality < 50 else 200 - 2 * quality
+    return tuple(np.clip((np.array(base, dtype=np.int64) * scale + 50) // 100, 1, 255) for base in (K_LUMA_QUANT, K_CHROMA_QUANT))
+
+
+def _encode_geometry(width, height, subsampling, restart_interval):
+    if subsampling not in SUBSAMPLINGS:
+        raise ValueError(f"subsampling must be one of {tuple(SUBSAMPLINGS)} (got {subsampling!r})")
+    for what, x in (("width", width), ("height", height)):
+        if isinstance(x, bool) or int(x) != x or not 1 <= int(x) <= MAX_DIM:
+            raise ValueError(f"{what} must be a whole number in 1..{MAX_DIM} (got {x!r})")
+    if isinstance(restart_interval, bool) or int(restart_interval) != restart_interval or not 0 <= int(restart_interval) <= 65535:
+        raise ValueError(f"restart_interval must be a whole number of MCUs in 0..65535 (got {restart_interval!r})")
+    h, v = SUBSAMPLINGS[subsampling]
+    mcus = -(-int(width) // (8 * h)) * -(-int(height) // (8 * v))
+    return h, v, mcus
+
+
+def encode_header(width: int, height: int, quality: int = 95, subsampling: str = "4:2:0", restart_interval: int = 0) -> bytes:
+    """The file up to its scan, as libjpeg writes it: SOI, APP0 (JFIF 1.01, density 1 x 1, no unit), DQT 0 and 1, SOF0, the four DHT of
+    Annex K.3 (DC 0, AC 0, DC 1, AC 1), DRI if ``restart_interval`` (MCUs) is not 0, SOS.  Host only."""
+    h, v, _ = _encode_geometry(width, height, subsampling, restart_interval)
+    luma, chroma = quant_tables(quality)
+
+    def seg(marker, body):
+        return bytes([0xFF, marker]) + (len(body) + 2).to_bytes(2, "big") + bytes(body)
+
+    out = b"\xff\xd8" + seg(0xE0, b"JFIF\x00\x01\x01\x00\x00\x01\x00\x01\x00\x00")
+    for t, table in enumerate((luma, chroma)):
+        out += seg(0xDB, bytes([t]) + bytes(int(table[n]) for n in K_ZIGZAG))
+    out += seg(0xC0, bytes([8]) + int(height).to_bytes(2, "big") + int(width).to_bytes(2, "big")
+               + bytes([3, 1, (h << 4) | v, 0, 2, 0x11, 1, 3, 0x11, 1]))
+    for ident, (counts, values) in ((0x00, K_DC_LUMA), (0x10, K_AC_LUMA), (0x01, K_DC_CHROMA), (0x11, K_AC_CHROMA)):
+        out += seg(0xC4, bytes([ident]) + bytes(counts) + bytes(values))
+    if restart_interval:
+        out += seg(0xDD, int(restart_interval).to_bytes(2, "big"))
+    return out + seg(0xDA, bytes([3, 1, 0x00, 2, 0x11, 3, 0x11, 0, 63, 0]))
+
+
+def encode_capacity(width: int, height: int, subsampling: str = "4:2:0", restart_interval: int = 0, worst_case: bool = False) -> int:
+    """Bytes per frame of ``encode``'s ``data``.  The default: the header and 1.5 bytes per padded luma sample (far above what quality 95
+    gives a photograph).  ``worst_case``: what no frame can exceed - every block ``MAX_BLOCK_BYTES`` long and every byte stuffed, a
+    padding byte and a marker per restart interval, EOI."""
+    h, v, mcus = _encode_geometry(width, height, subsampling, restart_interval)
+    header = len(encode_header(width, height, 95, subsampling, restart_interval))
+    if not worst_case:
+        return header + 3 * (mcus * h * v * 64) // 2 + 2
+    intervals = -(-mcus // int(restart_interval)) if restart_interval else 1
+    return header + 2 * mcus * (h * v + 2) * MAX_BLOCK_BYTES + 3 * intervals
+
+
+def encode(frames, quality: int = 95, subsampling: str = "4:2:0", channel_order: str = "bgr", restart_interval: int = 0, chunk: int = 32,
+           capacity=None, timings=None, return_coefficients: bool = False, guard: int = 0):
+    """frames: a contiguous uint8 [F, H, W, 3] device tensor (B, G, R as the demo's stages hold them, or R, G, B with
+    ``channel_order="rgb"``) -> (data uint8: the JPEG files back to back, offsets int64 [F + 1], status int32 [F]), all on the device:
+    frame f's file is ``data[offsets[f]:offsets[f + 1]]``.  By pmce_jpeg_encode_coefficients / _entropy on the current stream, ``chunk``
+    frames at a time through one workspace (2 bytes of coefficients per padded sample and ``MAX_BLOCK_BYTES`` per block of unstuffed
+    stream: 16.5 MB per 1080p 4:2:0 frame); no wait for the device, nothing is read back.  The files are those of libjpeg's default
+    compressor at the same settings, byte for byte - ``cv2.imwrite``'s are quality 95, 4:2:0, no restart markers,
+    the defaults here.  ``restart_interval`` is in MCUs (0: no DRI, no markers).  ``capacity``: bytes per frame of ``data`` (default
+    ``encode_capacity``; ``encode_capacity(..., worst_case=True)`` bounds every frame); a frame whose file is longer gets length 0 and
+    ``STATUS_CAPACITY`` in ``status`` - never a partial file - and nothing is written beyond ``offsets[F]``.  ``timings``: a list that
+    receives (stage, start event, end event) per launch, for scripts/bench_jpeg_encode.py.  ``return_coefficients`` (one round only:
+    F <= chunk) adds the coefficient stage's int16 [F, blocks, 64] (zigzag order) as a fourth result.  ``guard``: for the tests - ``data`` is
+    filled with 0xA5 first and has that many bytes more than F x capacity.  ``files`` reads the result back."""
+    import torch
+    if channel_order not in CHANNEL_ORDERS:
+        raise ValueError(f"channel_order must be one of {CHANNEL_ORDERS} (got {channel_order!r})")
+    if isinstance(chunk, bool) or int(chunk) != chunk or not 1 <= int(chunk) <= 65535:
+        raise ValueError(f"chunk must be a whole number in 1..65535 (got {chunk!r})")
+    if not isinstance(frames, torch.Tensor) or frames.dtype != torch.uint8 or frames.ndim != 4 or frames.shape[3] != 3 or frames.shape[0] < 1:
+        raise ValueError("frames must be a uint8 tensor [F, H, W, 3] with F >= 1")
+    F, H, W = (int(x) for x in frames.shape[:3])
+    h, v, mcus = _encode_geometry(W, H, subsampling, restart_interval)
+    header = encode_header(W, H, quality, subsampling, restart_interval)
+    if capacity is None:
+        capacity = encode_capacity(W, H, subsampling, restart_interval)
+    if isinstance(capacity, bool) or int(capacity) != capacity or int(capacity) < 1:
+        raise ValueError(f"capacity must be a whole number of bytes >= 1 (got {capacity!r})")
+    chunk, capacity, restart_interval = min(int(chunk), F), int(capacity), int(restart_interval)
+    if return_coefficients and F > chunk:
+        raise ValueError(f"return_coefficients needs one round: {F} frames, chunk {chunk}")
+    if not frames.is_cuda or not frames.is_contiguous():
+        raise ValueError("frames must be a contiguous device tensor")
+    n_blocks = mcus * (h * v + 2)
+    lib = _lib.load()
+    ws_bytes = lib.pmce_jpeg_encode_workspace_bytes(chunk, mcus, h * v, restart_interval)
+    if ws_bytes == 0 or chunk * n_blocks >= 2 ** 31:
+        raise ValueError(f"{chunk} frames of {W} x {H} per round need a workspace past its limits: use a smaller chunk or a restart interval")
+    tables = np.concatenate(quant_tables(quality)).astype(np.uint16)
+    host = np.concatenate([tables.view(np.uint8), np.frombuffer(header, dtype=np.uint8)])
+    pinned = torch.zeros(len(host), dtype=torch.uint8, pin_memory=True)
+    pinned.numpy()[:] = host
+    dev = frames.device
+    with torch.cuda.device(dev):
+        stream = _lib.current_stream()
+        consts = pinned.to(dev, non_blocking=True)
+        p_quant, p_header = C.c_void_p(consts.data_ptr()), C.c_void_p(consts.data_ptr() + 256)
+        data = (torch.full((F * capacity + int(guard),), 0xA5, device=dev, dtype=torch.uint8) if guard
+                else torch.empty(F * capacity, device=dev, dtype=torch.uint8))
+        offsets = torch.empty(F + 1, device=dev, dtype=torch.int64)
+        status = torch.empty(F, device=dev, dtype=torch.int32)
+        coef = torch.empty(chunk, n_blocks, 64, device=dev, dtype=torch.int16)
+        workspace = torch.empty(ws_bytes, device=dev, dtype=torch.uint8)
+
+        def timed(stage, fn):
+            if timings is None:
+                return fn()
+            e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+            e0.record()
+            fn()
+            e1.record()
+            timings.append((stage, e0, e1))
+
+        def entropy(f0, n, stage):
+            _lib.check(lib.pmce_jpeg_encode_entropy(
+                _lib.ptr(coef), n, mcus, h * v, restart_interval, p_header, len(header), capacity, _lib.ptr(workspace), ws_bytes,
+                _lib.ptr(data), F * capacity, _lib.ptr(offsets), _lib.ptr(status), f0, stage, stream), "jpeg_encode_entropy")
+
+        for f0 in range(0, F, chunk):
+            n = min(chunk, F - f0)
+            timed("coefficients", lambda: _lib.check(lib.pmce_jpeg_encode_coefficients(
+                _lib.ptr(frames), f0, n, W, H, h, v, 1 if channel_order == "rgb" else 0, p_quant, _lib.ptr(coef), chunk * n_blocks, stream),
+                "jpeg_encode_coefficients"))
+            if timings is None:
+                entropy(f0, n, -1)
+            else:                                  # launch by launch, so that each has its events
+                for stage, name in enumerate(ENCODE_STAGES):
+                    timed(name, lambda: entropy(f0, n, stage))
+    if return_coefficients:
+        return data, offsets, status, coef[:F]
+    return data, offsets, status
+
+
+def encode_entropy(coefficients, luma_blocks: int, header: bytes, restart_interval: int = 0, capacity=None, guard: int = 0):
+    """The entropy stages alone (pmce_jpeg_encode_entropy): coefficients int16 [F, blocks, 64] on the device, zigzag order, blocks in scan
+    order with ``luma_blocks`` (1, 2 or 4) luma blocks, Cb and Cr per MCU -> (data, offsets, status) as ``encode`` gives them, the files
+    beginning with ``header``.  ``guard``: that many bytes of 0xA5 are allocated behind ``data`` (the returned tensor includes them)."""
+    import torch
+    c = coefficients
+    if not isinstance(c, torch.Tensor) or c.dtype != torch.int16 or c.ndim != 3 or c.shape[2] != 64 or c.shape[0] < 1:
+        raise ValueError("coefficients must be an int16 tensor [F, blocks, 64]")
+    if luma_blocks not in (1, 2, 4) or c.shape[1] < 1 or c.shape[1] % (luma_blocks + 2):
+        raise ValueError(f"{c.shape[1]} blocks per frame are no whole number of MCUs of {luma_blocks} + 2 blocks")
+    if isinstance(restart_interval, bool) or int(restart_interval) != restart_interval or not 0 <= int(restart_interval) <= 65535:
+        raise ValueError(f"restart_interval must be a whole number of MCUs in 0..65535 (got {restart_interval!r})")
+    if not c.is_cuda or not c.is_contiguous():
+        raise ValueError("coefficients must be a contiguous device tensor")
+    F, mcus = int(c.shape[0]), int(c.shape[1]) // (luma_blocks + 2)
+    header = bytes(header)
+    intervals = -(-mcus // int(restart_interval)) if restart_interval else 1
+    if capacity is None:
+        capacity = len(header) + 2 * int(c.shape[1]) * MAX_BLOCK_BYTES + 3 * intervals
+    lib = _lib.load()
+    ws_bytes = lib.pmce_jpeg_encode_workspace_bytes(F, mcus, luma_blocks, int(restart_interval))
+    if ws_bytes == 0:
+        raise ValueError(f"{F} frames of {mcus} MCUs need a workspace past its limits")
+    with torch.cuda.device(c.device):
+        hdr = torch.frombuffer(bytearray(header), dtype=torch.uint8).to(c.device)
+        data = torch.full((F * int(capacity) + int(guard),), 0xA5, device=c.device, dtype=torch.uint8)
+        offsets = torch.empty(F + 1, device=c.device, dtype=torch.int64)
+        status = torch.empty(F, device=c.device, dtype=torch.int32)
+        workspace = torch.empty(ws_bytes, device=c.device, dtype=torch.uint8)
+        _lib.check(lib.pmce_jpeg_encode_entropy(_lib.ptr(c), F, mcus, luma_blocks, int(restart_interval), _lib.ptr(hdr), len(header),
+                                                int(capacity), _lib.ptr(workspace), ws_bytes, _lib.ptr(data), F * int(capacity),
+                                                _lib.ptr(offsets), _lib.ptr(status), 0, -1, _lib.current_stream()), "jpeg_encode_entropy")
+    return data, offsets, status
+
+
+def files(data, offsets, status) -> list:
+    """What ``encode`` returned, as a list of ``bytes``, one file per frame.  The one host read: the offsets and the status words, then
+    only the bytes in use.  A frame with a status bit raises ValueError, naming the frame."""
+    off = offsets.cpu().numpy()
+    st = status.cpu().numpy()
+    bad = np.flatnonzero(st)
+    if len(bad):
+        raise ValueError(f"frame {int(bad[0])}: its file is longer than the capacity per frame (status {int(st[bad[0]])}): "
+                         "encode with a larger capacity (encode_capacity(..., worst_case=True) holds every frame)")
+    raw = data[:int(off[-1])].cpu().numpy().tobytes()
+    return [raw[int(off[f]):int(off[f + 1])] for f in range(len(st))]
