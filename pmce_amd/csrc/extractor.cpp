@@ -1,7 +1,7 @@
 // The demo's feature extractor as one call: the backbone of the reference's HMR (lib/models/spin.py:61-143 - stem, max pool, four stages
 // of [3, 4, 6, 3] bottlenecks, the 7 x 7 average; 53 convolutions) on the operators of conv.hip.  Host code only: a table of the 53
-// convolutions in the order of the forward, the packed weights and the launch sequence.  Eval-mode BatchNorm arrives folded into each
-// convolution's weight and bias (pmce_amd/extractor.py folds on the host in fp64).
+// convolutions in the order of the forward and the launch sequence (the weights' storage: net_weights.hpp).  Eval-mode BatchNorm arrives
+// folded into each convolution's weight and bias (pmce_amd/extractor.py folds on the host in fp64).
 #include <hip/hip_runtime.h>
 #include <string.h>
 
@@ -9,18 +9,17 @@
 #include <vector>
 
 #include "common.hpp"
+#include "net_weights.hpp"
 #include "../../include/pmce_hip.h"
 
 namespace {
 
+using pmce_net::Param;
+
 struct ConvLayer {
   std::string name;
   int cout, cin, k, stride, pad;
-  const float* w_src = nullptr;  // caller's folded OIHW weight and bias (device), read by finalize
-  const float* b_src = nullptr;
-  float* wp = nullptr;  // inside the arena
-  float* wscale = nullptr;
-  float* bias = nullptr;
+  Param w, b;  // the folded OIHW weight and its bias
 };
 
 constexpr int STAGE_PLANES[4] = {64, 128, 256, 512}, STAGE_BLOCKS[4] = {3, 4, 6, 3}, STAGE_STRIDE[4] = {1, 2, 2, 2};
@@ -28,23 +27,18 @@ constexpr int SIDE = 224;
 constexpr size_t FULL = 112 * 112 * 64;  // floats per image of the largest activation (the stem's output; also 56 x 56 x 256)
 constexpr size_t HALF = 56 * 56 * 128;   // of the largest inner activation of a bottleneck (layer2.0.conv1)
 
-size_t align64(size_t floats) { return (floats + 63) / 64 * 64; }
-
 }  // namespace
 
 struct pmce_extractor {
   std::vector<ConvLayer> convs;
-  float* arena = nullptr;
-  bool finalized = false;
+  pmce_net::Arena arena;
 };
 
 extern "C" int pmce_extractor_create(pmce_extractor** out) {
   PMCE_REQUIRE(out, "extractor_create: null pointer");
   pmce_extractor* e = new pmce_extractor();
   auto add = [&](const std::string& name, int cout, int cin, int k, int stride, int pad) {
-    ConvLayer c;
-    c.name = name; c.cout = cout; c.cin = cin; c.k = k; c.stride = stride; c.pad = pad;
-    e->convs.push_back(c);
+    e->convs.push_back({name, cout, cin, k, stride, pad, Param(pmce_net::CONV, 4, cout, cin, k, k), Param(pmce_net::PLAIN, 1, cout)});
   };
   add("conv1", 64, 3, 7, 2, 3);
   int inplanes = 64;
@@ -62,11 +56,7 @@ extern "C" int pmce_extractor_create(pmce_extractor** out) {
   return PMCE_OK;
 }
 
-extern "C" void pmce_extractor_destroy(pmce_extractor* e) {
-  if (!e) return;
-  if (e->arena) (void)hipFree(e->arena);
-  delete e;
-}
+extern "C" void pmce_extractor_destroy(pmce_extractor* e) { delete e; }
 
 extern "C" int pmce_extractor_conv_count(const pmce_extractor* e) { return e ? (int)e->convs.size() : 0; }
 
@@ -83,11 +73,11 @@ extern "C" int pmce_extractor_conv_shape(const pmce_extractor* e, int i, int* sh
 
 extern "C" int pmce_extractor_set_conv(pmce_extractor* e, const char* name, const float* folded_weight, const float* folded_bias) {
   PMCE_REQUIRE(e && name && folded_weight && folded_bias, "extractor_set_conv: null pointer");
-  PMCE_REQUIRE(!e->finalized, "extractor_set_conv: the extractor is finalized");
+  PMCE_REQUIRE(!e->arena.ready(), "extractor_set_conv: the extractor is finalized");
   for (ConvLayer& c : e->convs)
     if (c.name == name) {
-      c.w_src = folded_weight;
-      c.b_src = folded_bias;
+      c.w.src = folded_weight;
+      c.b.src = folded_bias;
       return PMCE_OK;
     }
   pmce_set_error("extractor_set_conv: no convolution named '%s'", name);
@@ -96,37 +86,13 @@ extern "C" int pmce_extractor_set_conv(pmce_extractor* e, const char* name, cons
 
 extern "C" int pmce_extractor_finalize_on(pmce_extractor* e, pmce_stream_t stream) {
   PMCE_REQUIRE(e, "extractor_finalize: null pointer");
-  PMCE_REQUIRE(!e->finalized, "extractor_finalize: already finalized");
-  size_t floats = 0;
-  for (const ConvLayer& c : e->convs) {
-    PMCE_REQUIRE(c.w_src && c.b_src, "extractor_finalize: convolution '%s' was not set", c.name.c_str());
-    floats += align64((size_t)pmce_conv_packed_floats(c.cout, c.cin, c.k, c.k)) + 2 * align64((size_t)c.cout);
-  }
-  const hipError_t rc = hipMalloc(reinterpret_cast<void**>(&e->arena), floats * sizeof(float));
-  if (rc != hipSuccess) {
-    e->arena = nullptr;
-    pmce_set_error("extractor_finalize: hipMalloc(%zu bytes) for the split weights failed: %s", floats * sizeof(float), hipGetErrorString(rc));
-    return PMCE_ERR_WORKSPACE;
-  }
-  float* at = e->arena;
+  std::vector<Param*> params;
   for (ConvLayer& c : e->convs) {
-    c.wp = at; at += align64((size_t)pmce_conv_packed_floats(c.cout, c.cin, c.k, c.k));
-    c.wscale = at; at += align64((size_t)c.cout);
-    c.bias = at; at += align64((size_t)c.cout);
-    PMCE_TRY(pmce_conv_pack_split_f16(c.w_src, c.cout, c.cin, c.k, c.k, c.wp, c.wscale, stream));
-    if (hipMemcpyAsync(c.bias, c.b_src, (size_t)c.cout * sizeof(float), hipMemcpyDeviceToDevice, stream) != hipSuccess) {
-      pmce_set_error("extractor_finalize: copying the bias of '%s' failed", c.name.c_str());
-      return PMCE_ERR_LAUNCH;
-    }
+    params.push_back(&c.w);
+    params.push_back(&c.b);
   }
-  // the caller may free its folded tensors when this returns
-  if (hipStreamSynchronize(stream) != hipSuccess) {
-    pmce_set_error("extractor_finalize: the packing kernels failed: %s", hipGetErrorString(hipGetLastError()));
-    return PMCE_ERR_LAUNCH;
-  }
-  for (ConvLayer& c : e->convs) c.w_src = c.b_src = nullptr;
-  e->finalized = true;
-  return PMCE_OK;
+  auto label = [&](size_t i) { return "convolution '" + e->convs[i / 2].name + "'"; };
+  return pmce_net::finalize("extractor_finalize", params, label, e->arena, stream);
 }
 
 extern "C" size_t pmce_extractor_workspace_bytes(int n) {
@@ -141,10 +107,9 @@ extern "C" int pmce_extractor_forward(const pmce_extractor* e, const float* patc
                                       float* feats, int n, float* tap1, float* tap2, float* tap3, float* tap4, void* workspace,
                                       size_t workspace_bytes, pmce_stream_t stream) {
   PMCE_REQUIRE(e && patches && feats && workspace, "extractor_forward: null pointer");
-  PMCE_REQUIRE(e->finalized, "extractor_forward: the extractor is not finalized");
+  PMCE_REQUIRE(e->arena.ready(), "extractor_forward: the extractor is not finalized");
   PMCE_REQUIRE(n >= 1 && n <= 4096, "extractor_forward: n must be in 1..4096 (got %d)", n);
-  PMCE_REQUIRE((reinterpret_cast<uintptr_t>(workspace) & 15) == 0 && workspace_bytes >= pmce_extractor_workspace_bytes(n),
-               "extractor_forward: the workspace must be 16-byte aligned and hold %zu bytes (got %zu)", pmce_extractor_workspace_bytes(n), workspace_bytes);
+  PMCE_TRY(pmce_net::check_workspace("extractor_forward", workspace, workspace_bytes, pmce_extractor_workspace_bytes(n)));
   float* ws = static_cast<float*>(workspace);
   float* full[3] = {ws, ws + (size_t)n * FULL, ws + 2 * (size_t)n * FULL};
   float* t1 = ws + 3 * (size_t)n * FULL;
@@ -154,12 +119,12 @@ extern "C" int pmce_extractor_forward(const pmce_extractor* e, const float* patc
   // NHWC convolution of layer ci on [n][h][w][cin]
   auto conv = [&](int ci, const float* x, int h, int w, const float* res, float* out, bool relu) {
     const ConvLayer& c = e->convs[ci];
-    return pmce_conv2d_split_f16(x, (long long)h * w * c.cin, 1, (long long)w * c.cin, c.cin, n, c.cin, h, w, c.wp, c.wscale, c.bias, res, out,
+    return pmce_conv2d_split_f16(x, (long long)h * w * c.cin, 1, (long long)w * c.cin, c.cin, n, c.cin, h, w, c.w.dev, c.w.wscale, c.b.dev, res, out,
                                  c.cout, c.k, c.k, c.stride, c.pad, relu ? 1 : 0, stream);
   };
   {  // the stem reads the patches through the caller's strides
     const ConvLayer& c = e->convs[0];
-    PMCE_TRY(pmce_conv2d_split_f16(patches, sn, sc, sy, sx, n, 3, SIDE, SIDE, c.wp, c.wscale, c.bias, nullptr, full[0], 64, 7, 7, 2, 3, 1, stream));
+    PMCE_TRY(pmce_conv2d_split_f16(patches, sn, sc, sy, sx, n, 3, SIDE, SIDE, c.w.dev, c.w.wscale, c.b.dev, nullptr, full[0], 64, 7, 7, 2, 3, 1, stream));
   }
   PMCE_TRY(pmce_maxpool3x3s2_nhwc_f32(full[0], full[1], n, 112, 112, 64, stream));
   int cur = 1, side = 56, ci = 1;

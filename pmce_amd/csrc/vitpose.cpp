@@ -1,8 +1,8 @@
 // ViTPose's network as one call: normalised person patches -> keypoint heatmaps.  The structure is that of ViTPose's published ViT
 // backbone (patch embedding with padding 2, no class token, `depth` pre-norm blocks, last_norm) and TopdownHeatmapSimpleHead (two
 // ConvTranspose2d(4, 2, 1) + BatchNorm + ReLU, a 1 x 1 convolution), with the hyper-parameters of the demo's config
-// (pose_detector/ViTPose_huge_coco_256x192.py).  Host code only: the table of tensors, the packed weights and the launch sequence on
-// the operators of gemm_split_f16.hip, conv.hip, vit_attention.hip, layernorm_rows.hip and deconv_gather.hip.
+// (pose_detector/ViTPose_huge_coco_256x192.py).  Host code only: the table of tensors and the launch sequence on the operators of
+// gemm_split_f16.hip, conv.hip, vit_attention.hip, layernorm_rows.hip and deconv_gather.hip (the weights' storage: net_weights.hpp).
 // Three tensors arrive prepared by the host (pmce_amd/vitpose.py, in fp64 rounded once): the position table pos_embed[1:] + pos_embed[:1],
 // and each deconvolution as the weight of its product with the BatchNorm scale folded in, plus the folded BatchNorm bias.
 #include <hip/hip_runtime.h>
@@ -12,28 +12,19 @@
 #include <vector>
 
 #include "common.hpp"
+#include "net_weights.hpp"
 #include "../../include/pmce_hip.h"
 
 namespace {
 
-enum Kind { PLAIN, LINEAR, CONV };  // PLAIN: copied as it is; LINEAR: [N][K] packed for the product; CONV: OIHW packed for the convolution
+using pmce_net::CONV;
+using pmce_net::Kind;
+using pmce_net::LINEAR;
+using pmce_net::PLAIN;
 
-struct Tensor {
+struct Tensor : pmce_net::Param {
   std::string name;
-  int shape[4] = {0, 0, 0, 0};
-  int rank = 0;
-  Kind kind = PLAIN;
-  const float* src = nullptr;  // the caller's tensor (device), read by finalize
-  float* dev = nullptr;        // inside the arena: the copy (PLAIN) or the planes
-  float* wscale = nullptr;     // packed tensors: one power of two per output row
-  size_t floats() const {
-    size_t f = 1;
-    for (int i = 0; i < rank; ++i) f *= (size_t)shape[i];
-    return f;
-  }
 };
-
-size_t align64(size_t floats) { return (floats + 63) / 64 * 64; }
 
 constexpr int MAX_N = 256;
 constexpr int PATCH = 16, PATCH_PAD = 2;
@@ -45,8 +36,7 @@ struct pmce_vitpose {
   int H, W, C, depth, heads, F1, F2, K;
   int Hp, Wp, N;
   std::vector<Tensor> t;
-  float* arena = nullptr;
-  bool finalized = false;
+  pmce_net::Arena arena;
 
   // floats per image: the token stream, the normalised planes, the attention planes, then max(body, head)
   size_t body_floats() const { return (size_t)N * 3 * C + (size_t)N * 4 * C; }
@@ -70,10 +60,7 @@ extern "C" int pmce_vitpose_create(int H, int W, int C, int depth, int heads, in
   v->H = H; v->W = W; v->C = C; v->depth = depth; v->heads = heads; v->F1 = F1; v->F2 = F2; v->K = K;
   v->Hp = Hp; v->Wp = Wp; v->N = N;
   auto add = [&](const std::string& name, Kind kind, int rank, int s0, int s1 = 0, int s2 = 0, int s3 = 0) {
-    Tensor x;
-    x.name = name; x.kind = kind; x.rank = rank;
-    x.shape[0] = s0; x.shape[1] = s1; x.shape[2] = s2; x.shape[3] = s3;
-    v->t.push_back(x);
+    v->t.push_back({pmce_net::Param(kind, rank, s0, s1, s2, s3), name});
   };
   auto lin = [&](const std::string& p, int nout, int nin) {
     add(p + ".weight", LINEAR, 2, nout, nin);
@@ -106,11 +93,7 @@ extern "C" int pmce_vitpose_create(int H, int W, int C, int depth, int heads, in
   return PMCE_OK;
 }
 
-extern "C" void pmce_vitpose_destroy(pmce_vitpose* v) {
-  if (!v) return;
-  if (v->arena) (void)hipFree(v->arena);
-  delete v;
-}
+extern "C" void pmce_vitpose_destroy(pmce_vitpose* v) { delete v; }
 
 extern "C" int pmce_vitpose_tensor_count(const pmce_vitpose* v) { return v ? (int)v->t.size() : 0; }
 
@@ -126,7 +109,7 @@ extern "C" int pmce_vitpose_tensor_shape(const pmce_vitpose* v, int i, int* shap
 
 extern "C" int pmce_vitpose_set_tensor(pmce_vitpose* v, const char* name, const float* dev_ptr) {
   PMCE_REQUIRE(v && name && dev_ptr, "vitpose_set_tensor: null pointer");
-  PMCE_REQUIRE(!v->finalized, "vitpose_set_tensor: the network is finalized");
+  PMCE_REQUIRE(!v->arena.ready(), "vitpose_set_tensor: the network is finalized");
   PMCE_REQUIRE((reinterpret_cast<uintptr_t>(dev_ptr) & 15) == 0, "vitpose_set_tensor: tensor '%s' must be 16-byte aligned", name);
   for (Tensor& x : v->t)
     if (x.name == name) {
@@ -139,46 +122,10 @@ extern "C" int pmce_vitpose_set_tensor(pmce_vitpose* v, const char* name, const 
 
 extern "C" int pmce_vitpose_finalize_on(pmce_vitpose* v, pmce_stream_t stream) {
   PMCE_REQUIRE(v, "vitpose_finalize: null pointer");
-  PMCE_REQUIRE(!v->finalized, "vitpose_finalize: already finalized");
-  auto storage = [](const Tensor& x) -> size_t {
-    if (x.kind == LINEAR) return align64(((size_t)x.shape[0] + 63) / 64 * 64 * (size_t)x.shape[1]) + align64((size_t)x.shape[0]);
-    if (x.kind == CONV) return align64((size_t)pmce_conv_packed_floats(x.shape[0], x.shape[1], x.shape[2], x.shape[3])) + align64((size_t)x.shape[0]);
-    return align64(x.floats());
-  };
-  size_t floats = 0;
-  for (const Tensor& x : v->t) {
-    PMCE_REQUIRE(x.src, "vitpose_finalize: tensor '%s' was not set", x.name.c_str());
-    floats += storage(x);
-  }
-  const hipError_t rc = hipMalloc(reinterpret_cast<void**>(&v->arena), floats * sizeof(float));
-  if (rc != hipSuccess) {
-    v->arena = nullptr;
-    pmce_set_error("vitpose_finalize: hipMalloc(%zu bytes) for the weights failed: %s", floats * sizeof(float), hipGetErrorString(rc));
-    return PMCE_ERR_WORKSPACE;
-  }
-  float* at = v->arena;
-  for (Tensor& x : v->t) {
-    x.dev = at;
-    if (x.kind == LINEAR) {
-      x.wscale = at + align64(((size_t)x.shape[0] + 63) / 64 * 64 * (size_t)x.shape[1]);
-      PMCE_TRY(pmce_gemm_pack_split_f16(x.src, x.shape[0], x.shape[1], x.shape[1], x.dev, x.wscale, 1, stream));
-    } else if (x.kind == CONV) {
-      x.wscale = at + align64((size_t)pmce_conv_packed_floats(x.shape[0], x.shape[1], x.shape[2], x.shape[3]));
-      PMCE_TRY(pmce_conv_pack_split_f16(x.src, x.shape[0], x.shape[1], x.shape[2], x.shape[3], x.dev, x.wscale, stream));
-    } else if (hipMemcpyAsync(x.dev, x.src, x.floats() * sizeof(float), hipMemcpyDeviceToDevice, stream) != hipSuccess) {
-      pmce_set_error("vitpose_finalize: copying '%s' failed", x.name.c_str());
-      return PMCE_ERR_LAUNCH;
-    }
-    at += storage(x);
-  }
-  // the caller may free its tensors when this returns
-  if (hipStreamSynchronize(stream) != hipSuccess) {
-    pmce_set_error("vitpose_finalize: the packing kernels failed: %s", hipGetErrorString(hipGetLastError()));
-    return PMCE_ERR_LAUNCH;
-  }
-  for (Tensor& x : v->t) x.src = nullptr;
-  v->finalized = true;
-  return PMCE_OK;
+  std::vector<pmce_net::Param*> params;
+  for (Tensor& x : v->t) params.push_back(&x);
+  auto label = [&](size_t i) { return "tensor '" + v->t[i].name + "'"; };
+  return pmce_net::finalize("vitpose_finalize", params, label, v->arena, stream);
 }
 
 extern "C" size_t pmce_vitpose_workspace_bytes(const pmce_vitpose* v, int n) {
@@ -192,10 +139,9 @@ extern "C" size_t pmce_vitpose_workspace_bytes(const pmce_vitpose* v, int n) {
 extern "C" int pmce_vitpose_forward(const pmce_vitpose* v, const float* patches, long long sn, long long sc, long long sy, long long sx, int n,
                                     float* heat, float* feat, void* workspace, size_t workspace_bytes, pmce_stream_t stream) {
   PMCE_REQUIRE(v && patches && heat && workspace, "vitpose_forward: null pointer");
-  PMCE_REQUIRE(v->finalized, "vitpose_forward: the network is not finalized");
+  PMCE_REQUIRE(v->arena.ready(), "vitpose_forward: the network is not finalized");
   PMCE_REQUIRE(n >= 1 && n <= MAX_N, "vitpose_forward: n must be in 1..%d (got %d)", MAX_N, n);
-  PMCE_REQUIRE((reinterpret_cast<uintptr_t>(workspace) & 15) == 0 && workspace_bytes >= pmce_vitpose_workspace_bytes(v, n),
-               "vitpose_forward: the workspace must be 16-byte aligned and hold %zu bytes (got %zu)", pmce_vitpose_workspace_bytes(v, n), workspace_bytes);
+  PMCE_TRY(pmce_net::check_workspace("vitpose_forward", workspace, workspace_bytes, pmce_vitpose_workspace_bytes(v, n)));
   const int C = v->C, N = v->N, F1 = v->F1, F2 = v->F2;
   const int M = n * N;
   float* ws = static_cast<float*>(workspace);

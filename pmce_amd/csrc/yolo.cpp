@@ -1,7 +1,7 @@
 // The tracker's detector as one call: a darknet-style network (convolutional, shortcut, route, upsample and yolo sections; the published
 // yolov3.cfg is the table pmce_amd/yolo.py passes) on the convolution of conv.hip and the kernels of yolo.hip.  Host code only: the
-// table, the buffer plan made from it, the packed weights and the launch sequence.  Eval-mode BatchNorm arrives folded into each
-// convolution's weight and bias (pmce_amd/yolo.py folds on the host in fp64).
+// table, the buffer plan made from it and the launch sequence (the weights' storage: net_weights.hpp).  Eval-mode BatchNorm arrives
+// folded into each convolution's weight and bias (pmce_amd/yolo.py folds on the host in fp64).
 //
 // The plan.  A shortcut is the epilogue of the convolution before it (out = from + leaky(conv)), so that convolution has no map of its
 // own.  A route with one source is another name for that source.  A route with two sources [upsample, tap] owns ONE buffer of the summed
@@ -12,9 +12,11 @@
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
+#include <string>
 #include <vector>
 
 #include "common.hpp"
+#include "net_weights.hpp"
 #include "../../include/pmce_hip.h"
 
 namespace {
@@ -32,19 +34,13 @@ struct Layer {
   int root = -1;                // the layer whose storage this one names (itself unless a one-source route)
   int buf = BUF_NONE, coff = 0, pitch = 0;
   int det = -1;                 // detection convolution: which of the caller's maps
-  const float* w_src = nullptr;
-  const float* b_src = nullptr;
-  float* wp = nullptr;
-  float* wscale = nullptr;
-  float* bias = nullptr;
+  pmce_net::Param w, b;         // convolutions: the folded OIHW weight and its bias (shaped by plan())
 };
 
 struct Buffer {
   long long units = 0, offset = -1;
   int birth = 1 << 30, death = -1;
 };
-
-size_t align64(size_t floats) { return (floats + 63) / 64 * 64; }
 
 }  // namespace
 
@@ -55,8 +51,7 @@ struct pmce_yolo {
   int yolo_layer[3];
   int nc = 0;
   long long total_units = 0;
-  float* arena = nullptr;
-  bool finalized = false;
+  pmce_net::Arena arena;
 };
 
 namespace {
@@ -80,6 +75,8 @@ int plan(pmce_yolo* y) {
         l.C = l.filters;
         l.ds = (i == 0 ? 1 : L[i - 1].ds) * l.stride;
         PMCE_REQUIRE(l.ds <= 32, "yolo_create: layer %d: the map is smaller than 1/32 of the input", i);
+        l.w = pmce_net::Param(pmce_net::CONV, 4, l.filters, l.cin, l.size, l.size);
+        l.b = pmce_net::Param(pmce_net::PLAIN, 1, l.filters);
         break;
       }
       case K_SHORTCUT: {
@@ -277,11 +274,7 @@ extern "C" int pmce_yolo_create(const int* table, int n_layers, const float* anc
   return PMCE_OK;
 }
 
-extern "C" void pmce_yolo_destroy(pmce_yolo* y) {
-  if (!y) return;
-  if (y->arena) (void)hipFree(y->arena);
-  delete y;
-}
+extern "C" void pmce_yolo_destroy(pmce_yolo* y) { delete y; }
 
 extern "C" int pmce_yolo_layer_count(const pmce_yolo* y) { return y ? (int)y->layers.size() : 0; }
 
@@ -306,48 +299,26 @@ extern "C" long long pmce_yolo_workspace_units(const pmce_yolo* y) { return y ? 
 
 extern "C" int pmce_yolo_set_conv(pmce_yolo* y, int layer, const float* folded_weight, const float* folded_bias) {
   PMCE_REQUIRE(y && folded_weight && folded_bias, "yolo_set_conv: null pointer");
-  PMCE_REQUIRE(!y->finalized, "yolo_set_conv: the network is finalized");
+  PMCE_REQUIRE(!y->arena.ready(), "yolo_set_conv: the network is finalized");
   PMCE_REQUIRE(layer >= 0 && layer < (int)y->layers.size() && y->layers[layer].kind == K_CONV, "yolo_set_conv: layer %d is not a convolution", layer);
-  y->layers[layer].w_src = folded_weight;
-  y->layers[layer].b_src = folded_bias;
+  y->layers[layer].w.src = folded_weight;
+  y->layers[layer].b.src = folded_bias;
   return PMCE_OK;
 }
 
 extern "C" int pmce_yolo_finalize_on(pmce_yolo* y, pmce_stream_t stream) {
   PMCE_REQUIRE(y, "yolo_finalize: null pointer");
-  PMCE_REQUIRE(!y->finalized, "yolo_finalize: already finalized");
-  size_t floats = 0;
+  std::vector<pmce_net::Param*> params;
+  std::vector<int> layer_of;
   for (size_t i = 0; i < y->layers.size(); ++i) {
-    const Layer& l = y->layers[i];
+    Layer& l = y->layers[i];
     if (l.kind != K_CONV) continue;
-    PMCE_REQUIRE(l.w_src && l.b_src, "yolo_finalize: the convolution of layer %d was not set", (int)i);
-    floats += align64((size_t)pmce_conv_packed_floats(l.filters, l.cin, l.size, l.size)) + 2 * align64((size_t)l.filters);
+    params.push_back(&l.w);
+    params.push_back(&l.b);
+    layer_of.insert(layer_of.end(), 2, (int)i);
   }
-  const hipError_t rc = hipMalloc(reinterpret_cast<void**>(&y->arena), floats * sizeof(float));
-  if (rc != hipSuccess) {
-    y->arena = nullptr;
-    pmce_set_error("yolo_finalize: hipMalloc(%zu bytes) for the split weights failed: %s", floats * sizeof(float), hipGetErrorString(rc));
-    return PMCE_ERR_WORKSPACE;
-  }
-  float* at = y->arena;
-  for (Layer& l : y->layers) {
-    if (l.kind != K_CONV) continue;
-    l.wp = at; at += align64((size_t)pmce_conv_packed_floats(l.filters, l.cin, l.size, l.size));
-    l.wscale = at; at += align64((size_t)l.filters);
-    l.bias = at; at += align64((size_t)l.filters);
-    PMCE_TRY(pmce_conv_pack_split_f16(l.w_src, l.filters, l.cin, l.size, l.size, l.wp, l.wscale, stream));
-    if (hipMemcpyAsync(l.bias, l.b_src, (size_t)l.filters * sizeof(float), hipMemcpyDeviceToDevice, stream) != hipSuccess) {
-      pmce_set_error("yolo_finalize: copying a bias failed");
-      return PMCE_ERR_LAUNCH;
-    }
-  }
-  if (hipStreamSynchronize(stream) != hipSuccess) {  // the caller may free its folded tensors when this returns
-    pmce_set_error("yolo_finalize: the packing kernels failed: %s", hipGetErrorString(hipGetLastError()));
-    return PMCE_ERR_LAUNCH;
-  }
-  for (Layer& l : y->layers) l.w_src = l.b_src = nullptr;
-  y->finalized = true;
-  return PMCE_OK;
+  auto label = [&](size_t i) { return "the convolution of layer " + std::to_string(layer_of[i]); };
+  return pmce_net::finalize("yolo_finalize", params, label, y->arena, stream);
 }
 
 extern "C" size_t pmce_yolo_workspace_bytes(const pmce_yolo* y, int n, int S) {
@@ -362,11 +333,10 @@ extern "C" int pmce_yolo_forward(const pmce_yolo* y, const float* images, long l
                                  float* map0, float* map1, float* map2, float* rows, void* workspace, size_t workspace_bytes,
                                  pmce_stream_t stream) {
   PMCE_REQUIRE(y && images && map0 && map1 && map2 && workspace, "yolo_forward: null pointer");
-  PMCE_REQUIRE(y->finalized, "yolo_forward: the network is not finalized");
+  PMCE_REQUIRE(y->arena.ready(), "yolo_forward: the network is not finalized");
   PMCE_REQUIRE(n >= 1 && n <= 1024 && S >= 32 && S <= 1024 && S % 32 == 0,
                "yolo_forward: n must be in 1..1024 and the side a multiple of 32 in 32..1024 (got n=%d S=%d)", n, S);
-  PMCE_REQUIRE((reinterpret_cast<uintptr_t>(workspace) & 15) == 0 && workspace_bytes >= pmce_yolo_workspace_bytes(y, n, S),
-               "yolo_forward: the workspace must be 16-byte aligned and hold %zu bytes (got %zu)", pmce_yolo_workspace_bytes(y, n, S), workspace_bytes);
+  PMCE_TRY(pmce_net::check_workspace("yolo_forward", workspace, workspace_bytes, pmce_yolo_workspace_bytes(y, n, S)));
   float* ws = static_cast<float*>(workspace);
   float* maps[3] = {map0, map1, map2};
   const size_t unit = (size_t)n * (size_t)(S / 32) * (size_t)(S / 32);
@@ -388,7 +358,7 @@ extern "C" int pmce_yolo_forward(const pmce_yolo* y, const float* images, long l
       x = at(ci - 1);
       xc = 1; xx = in.pitch; xy = (long long)side * in.pitch; xn = (long long)side * side * in.pitch;
     }
-    return pmce_conv2d_act_split_f16(x, xn, xc, xy, xx, n, c.cin, side, side, c.wp, c.wscale, c.bias, res >= 0 ? at(res) : nullptr,
+    return pmce_conv2d_act_split_f16(x, xn, xc, xy, xx, n, c.cin, side, side, c.w.dev, c.w.wscale, c.b.dev, res >= 0 ? at(res) : nullptr,
                                      res >= 0 ? L[res].pitch : 0, at(dst), o.pitch, c.filters, c.size, c.size, c.stride, (c.size - 1) / 2,
                                      c.leaky ? 2 : 0, LEAKY_SLOPE, 1, stream);
   };

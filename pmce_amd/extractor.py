@@ -19,6 +19,7 @@ from collections import OrderedDict
 import torch
 
 from . import _lib
+from ._net import DeviceNetwork, clean_state_dict, take_tensors
 
 BN_EPS = 1e-5
 SIDE = 224
@@ -56,26 +57,10 @@ def required_keys():
 
 
 def select_state_dict(sd):
-    """The extractor's tensors of a state dict (an optional ``module.`` prefix stripped; ``num_batches_tracked`` and the regression head
+    """The extractor's tensors of a state dict (cleaned as ``_net.clean_state_dict`` cleans; the regression head's
     ``fc1``, ``fc2``, ``dec*``, ``init_*``, ``smpl.*`` ignored) as fp32 CPU tensors.  A missing or mis-shaped tensor raises a ValueError
     that names it - the reference loads with strict=False and would keep random weights."""
-    if not hasattr(sd, "items"):
-        raise ValueError(f"a state dict is a mapping of names to tensors (got {type(sd).__name__})")
-    clean = {}
-    for k, v in sd.items():
-        k = k[len("module."):] if k.startswith("module.") else k
-        if k.endswith("num_batches_tracked") or k.startswith(IGNORED_PREFIXES):
-            continue
-        clean[k] = v
-    out = OrderedDict()
-    for name, shape in required_keys().items():
-        if name not in clean:
-            raise ValueError(f"the state dict has no tensor '{name}' (expected shape {tuple(shape)})")
-        t = torch.as_tensor(clean[name])
-        if tuple(t.shape) != tuple(shape):
-            raise ValueError(f"tensor '{name}' has shape {tuple(t.shape)}, expected {tuple(shape)}")
-        out[name] = t.detach().to(device="cpu", dtype=torch.float32)
-    return out
+    return take_tensors(clean_state_dict(sd, lambda k: not k.startswith(IGNORED_PREFIXES)), required_keys(), torch.float32)
 
 
 def fold_bn(w, gamma, beta, mean, var, eps: float = BN_EPS):
@@ -160,37 +145,27 @@ def avgpool(x):
 # the network
 # ----------------------------------------------------------------------------------------------
 
-class FeatureExtractor:
+class FeatureExtractor(DeviceNetwork):
     """SPIN's ResNet-50 backbone as HIP convolutions.  ``max_batch``: patches per launch sequence (the workspace, 12.8 MB per patch, is
     allocated once for it and reused); ``check_finite``: raise when a feature is not finite, naming the first such patch."""
+    NAME = "extractor"
+    MAX_BATCH = 4096
 
     def __init__(self, folded, device, max_batch: int = 64, check_finite: bool = True):
-        if int(max_batch) != max_batch or not 1 <= int(max_batch) <= 4096:
-            raise ValueError(f"max_batch must be a whole number in 1..4096 (got {max_batch!r})")
-        self.device = torch.device(device)
-        self.max_batch = int(max_batch)
-        self.check_finite = bool(check_finite)
-        self._ws = None
+        super().__init__(device, max_batch, check_finite)
         lib = _lib.load()
         h = C.c_void_p()
         _lib.check(lib.pmce_extractor_create(C.byref(h)), "extractor_create")
         self._h = h
-        with torch.cuda.device(self.device):
-            keep = []
+
+        def uploads():
             for ck, _, shape in conv_table():
                 w, b = folded[ck]
                 assert tuple(w.shape) == tuple(shape) and tuple(b.shape) == (shape[0],)
-                wd, bd = w.to(self.device).contiguous(), b.to(self.device).contiguous()
-                keep.append((wd, bd))
-                _lib.check(lib.pmce_extractor_set_conv(h, ck.encode(), _lib.ptr(wd), _lib.ptr(bd)), "extractor_set_conv")
-            torch.cuda.current_stream().synchronize()        # the uploads (pageable copies run on the legacy stream) are done
-            _lib.check(lib.pmce_extractor_finalize_on(h, _lib.current_stream()), "extractor_finalize")
-            del keep
+                set_conv = lambda wp, bp, ck=ck: _lib.check(lib.pmce_extractor_set_conv(h, ck.encode(), wp, bp), "extractor_set_conv")  # noqa: E731
+                yield set_conv, (w, b)
 
-    def __del__(self):
-        h, self._h = getattr(self, "_h", None), None
-        if h and _lib._lib is not None:
-            _lib._lib.pmce_extractor_destroy(h)
+        self._finalize(uploads())
 
     @classmethod
     def from_state_dict(cls, sd, device="cuda", **kw):
@@ -207,14 +182,6 @@ class FeatureExtractor:
             raise ValueError(f"{path}: the checkpoint has no 'model' entry")
         return cls.from_state_dict(ckpt["model"], device, **kw)
 
-    def _workspace(self):
-        if self._ws is None:
-            nbytes = _lib.load().pmce_extractor_workspace_bytes(self.max_batch)
-            if nbytes == 0:
-                raise _lib.PmceError(_lib.last_error())
-            self._ws = torch.empty(nbytes // 4, device=self.device, dtype=torch.float32)
-        return self._ws
-
     @torch.no_grad()
     def forward(self, patches, taps=()):
         """patches fp32 [n,3,224,224] (a host tensor is uploaded; any strides) -> features [n,2048][, {name: NCHW stage output} for the
@@ -223,27 +190,17 @@ class FeatureExtractor:
         for t in taps:
             if t not in TAPS:
                 raise ValueError(f"taps must be among {TAPS} (got {t!r})")
-        x = patches.to(self.device)
-        if any(s < 1 for s in x.stride()):
-            x = x.contiguous()
         feats = torch.empty(n, FEAT_DIM, device=self.device, dtype=torch.float32)
         tap_out = {t: torch.empty(n, TAP_SHAPES[t][0], TAP_SHAPES[t][0], TAP_SHAPES[t][1], device=self.device, dtype=torch.float32)
                    for t in taps}
         lib = _lib.load()
         with torch.cuda.device(self.device):
-            ws = self._workspace() if n else None
-            for i0 in range(0, n, self.max_batch):
-                m = min(self.max_batch, n - i0)
-                xi = x[i0:i0 + m]
-                sn, sc, sy, sx = xi.stride()
+            ws = self._workspace(lib.pmce_extractor_workspace_bytes(self.max_batch)) if n else None
+            for i0, m, xi, (sn, sc, sy, sx) in self._chunks(patches):
                 tp = [C.c_void_p(tap_out[t][i0:].data_ptr()) if t in tap_out else None for t in TAPS]
                 _lib.check(lib.pmce_extractor_forward(self._h, C.c_void_p(xi.data_ptr()), sn, sc, sy, sx, C.c_void_p(feats[i0:].data_ptr()), m,
                                                       *tp, _lib.ptr(ws), ws.numel() * 4, _lib.current_stream()), "extractor_forward")
-        if self.check_finite and n:
-            bad = ~torch.isfinite(feats).all(dim=1)
-            if bool(bad.any()):
-                raise _lib.PmceError(f"extractor: patch {int(bad.nonzero()[0])} has non-finite features (an input that is not finite, or an "
-                                     "activation beyond the f16 range of the split)")
+        self._require_finite(feats, "patch", "features")
         if taps:
             return feats, {t: v.permute(0, 3, 1, 2) for t, v in tap_out.items()}
         return feats

@@ -20,6 +20,7 @@ import numpy as np
 import torch
 
 from . import _lib, ops
+from ._net import clean_state_dict, take_tensors
 from .extractor import FEAT_DIM, FeatureExtractor
 
 NPOSE, NSHAPE, NCAM = 144, 10, 3
@@ -72,18 +73,7 @@ def fold_regressor(fc1_w, fc1_b, fc2_w, fc2_b, dec_w, dec_b, n_iter=3):
 def select_head_state_dict(sd):
     """The head's thirteen tensors of a state dict (an optional ``module.`` prefix stripped) as fp64 CPU tensors.  A missing or
     mis-shaped tensor raises a ValueError that names it."""
-    if not hasattr(sd, "items"):
-        raise ValueError(f"a state dict is a mapping of names to tensors (got {type(sd).__name__})")
-    clean = {(k[len("module."):] if k.startswith("module.") else k): v for k, v in sd.items()}
-    out = OrderedDict()
-    for name, shape in HEAD_KEYS.items():
-        if name not in clean:
-            raise ValueError(f"the state dict has no tensor '{name}' (expected shape {tuple(shape)})")
-        t = torch.as_tensor(clean[name])
-        if tuple(t.shape) != tuple(shape):
-            raise ValueError(f"tensor '{name}' has shape {tuple(t.shape)}, expected {tuple(shape)}")
-        out[name] = t.detach().to(device="cpu", dtype=torch.float64)
-    return out
+    return take_tensors(clean_state_dict(sd), HEAD_KEYS, torch.float64)
 
 
 def spin_joint_table(extra_vertex_ids, J_regressor_extra, n_verts=None):

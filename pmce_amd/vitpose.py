@@ -22,6 +22,7 @@ from collections import OrderedDict
 import torch
 
 from . import _lib
+from ._net import DeviceNetwork, clean_state_dict, take_tensors
 
 BN_EPS = 1e-5
 LN_EPS = 1e-6
@@ -37,15 +38,7 @@ PREFIXES = ("backbone.", "keypoint_head.")
 # ----------------------------------------------------------------------------------------------
 
 def _clean(sd):
-    if not hasattr(sd, "items"):
-        raise ValueError(f"a state dict is a mapping of names to tensors (got {type(sd).__name__})")
-    clean = {}
-    for k, v in sd.items():
-        k = k[len("module."):] if k.startswith("module.") else k
-        if k.endswith("num_batches_tracked") or not k.startswith(PREFIXES):
-            continue
-        clean[k] = v
-    return clean
+    return clean_state_dict(sd, lambda k: k.startswith(PREFIXES))
 
 
 def infer_config(sd, img_size=IMG_SIZE, num_heads=None):
@@ -128,20 +121,11 @@ def required_keys(cfg):
 
 
 def select_state_dict(sd, img_size=IMG_SIZE, num_heads=None):
-    """-> (cfg, tensors): the network's tensors of a state dict as fp32 CPU tensors (an optional ``module.`` prefix stripped; keys outside
-    ``backbone.`` / ``keypoint_head.`` - the multi-dataset checkpoint's ``associate_keypoint_heads.*`` - and ``num_batches_tracked``
-    ignored).  A missing or mis-shaped tensor raises a ValueError that names it."""
+    """-> (cfg, tensors): the network's tensors of a state dict as fp32 CPU tensors (cleaned as ``_net.clean_state_dict`` cleans; keys
+    outside ``backbone.`` / ``keypoint_head.`` - the multi-dataset checkpoint's ``associate_keypoint_heads.*`` - ignored).  A missing or
+    mis-shaped tensor raises a ValueError that names it."""
     cfg = infer_config(sd, img_size, num_heads)
-    clean = _clean(sd)
-    out = OrderedDict()
-    for name, shape in required_keys(cfg).items():
-        if name not in clean:
-            raise ValueError(f"the state dict has no tensor '{name}' (expected shape {tuple(shape)})")
-        t = torch.as_tensor(clean[name])
-        if tuple(t.shape) != tuple(shape):
-            raise ValueError(f"tensor '{name}' has shape {tuple(t.shape)}, expected {tuple(shape)}")
-        out[name] = t.detach().to(device="cpu", dtype=torch.float32)
-    return cfg, out
+    return cfg, take_tensors(_clean(sd), required_keys(cfg), torch.float32)
 
 
 # ----------------------------------------------------------------------------------------------
@@ -261,28 +245,25 @@ def prepare_tensors(cfg, t):
     return out
 
 
-class ViTPose:
+class ViTPose(DeviceNetwork):
     """ViTPose as HIP kernels.  ``max_batch``: patches per launch sequence (the workspace is allocated once for it and reused; 22.6 MB
     per patch for ViTPose-H); ``check_finite``: raise when a heatmap is not finite, naming the first such patch."""
+    NAME = "vitpose"
+    MAX_BATCH = MAX_BATCH
 
     def __init__(self, cfg, tensors, device, max_batch: int = 64, check_finite: bool = True):
-        if int(max_batch) != max_batch or not 1 <= int(max_batch) <= MAX_BATCH:
-            raise ValueError(f"max_batch must be a whole number in 1..{MAX_BATCH} (got {max_batch!r})")
+        super().__init__(device, max_batch, check_finite)
         check_config(cfg)
         self.cfg = dict(cfg)
-        self.device = torch.device(device)
-        self.max_batch = int(max_batch)
-        self.check_finite = bool(check_finite)
         self.Hp, self.Wp = cfg["H"] // PATCH, cfg["W"] // PATCH
-        self._ws = None
         lib = _lib.load()
         h = C.c_void_p()
         _lib.check(lib.pmce_vitpose_create(cfg["H"], cfg["W"], cfg["C"], cfg["depth"], cfg["heads"], cfg["F1"], cfg["F2"], cfg["K"], C.byref(h)),
                    "vitpose_create")
         self._h = h
         prepared = prepare_tensors(cfg, tensors)
-        with torch.cuda.device(self.device):
-            keep = []
+
+        def uploads():
             shape4 = (C.c_int * 4)()
             for i in range(lib.pmce_vitpose_tensor_count(h)):
                 name = lib.pmce_vitpose_tensor_name(h, i).decode()
@@ -290,17 +271,10 @@ class ViTPose:
                 want = tuple(shape4[:rank])
                 if name not in prepared or tuple(prepared[name].shape) != want:
                     raise ValueError(f"tensor '{name}' must have shape {want} (got {tuple(prepared[name].shape) if name in prepared else None})")
-                d = prepared[name].to(self.device, torch.float32).contiguous()
-                keep.append(d)
-                _lib.check(lib.pmce_vitpose_set_tensor(h, name.encode(), _lib.ptr(d)), "vitpose_set_tensor")
-            torch.cuda.current_stream().synchronize()        # the uploads (pageable copies run on the legacy stream) are done
-            _lib.check(lib.pmce_vitpose_finalize_on(h, _lib.current_stream()), "vitpose_finalize")
-            del keep
+                set_tensor = lambda p, name=name: _lib.check(lib.pmce_vitpose_set_tensor(h, name.encode(), p), "vitpose_set_tensor")  # noqa: E731
+                yield set_tensor, (prepared[name],)
 
-    def __del__(self):
-        h, self._h = getattr(self, "_h", None), None
-        if h and _lib._lib is not None:
-            _lib._lib.pmce_vitpose_destroy(h)
+        self._finalize(uploads())
 
     @classmethod
     def from_state_dict(cls, sd, device="cuda", img_size=IMG_SIZE, num_heads=None, **kw):
@@ -324,41 +298,23 @@ class ViTPose:
                              f"{shape})")
         return int(shape[0])
 
-    def _workspace(self):
-        if self._ws is None:
-            nbytes = _lib.load().pmce_vitpose_workspace_bytes(self._h, self.max_batch)
-            if nbytes == 0:
-                raise _lib.PmceError(_lib.last_error())
-            self._ws = torch.empty(nbytes // 4, device=self.device, dtype=torch.float32)
-        return self._ws
-
     @torch.no_grad()
     def forward(self, patches, return_features=False):
         """patches fp32 [n,3,H,W] (a host tensor is uploaded; any strides) -> heatmaps [n,K,4 Hp,4 Wp][, the backbone's map [n,C,Hp,Wp]], by
         pmce_vitpose_forward on the current stream, ``max_batch`` patches at a time.  Both are NCHW views of the NHWC tensors the device
         code writes."""
         n = self.check_patches(patches)
-        x = patches.to(self.device)
-        if any(s < 1 for s in x.stride()):
-            x = x.contiguous()
         k, c = self.cfg["K"], self.cfg["C"]
         heat = torch.empty(n, 4 * self.Hp, 4 * self.Wp, k, device=self.device, dtype=torch.float32)
         feat = torch.empty(n, self.Hp, self.Wp, c, device=self.device, dtype=torch.float32) if return_features else None
         lib = _lib.load()
         with torch.cuda.device(self.device):
-            ws = self._workspace() if n else None
-            for i0 in range(0, n, self.max_batch):
-                m = min(self.max_batch, n - i0)
-                xi = x[i0:i0 + m]
-                sn, sc, sy, sx = xi.stride()
+            ws = self._workspace(lib.pmce_vitpose_workspace_bytes(self._h, self.max_batch)) if n else None
+            for i0, m, xi, (sn, sc, sy, sx) in self._chunks(patches):
                 fp = C.c_void_p(feat[i0:].data_ptr()) if feat is not None else None
                 _lib.check(lib.pmce_vitpose_forward(self._h, C.c_void_p(xi.data_ptr()), sn, sc, sy, sx, m, C.c_void_p(heat[i0:].data_ptr()), fp,
                                                     _lib.ptr(ws), ws.numel() * 4, _lib.current_stream()), "vitpose_forward")
-        if self.check_finite and n:
-            bad = ~torch.isfinite(heat).reshape(n, -1).all(dim=1)
-            if bool(bad.any()):
-                raise _lib.PmceError(f"vitpose: patch {int(bad.nonzero()[0])} has non-finite heatmaps (an input that is not finite, or an "
-                                     "activation beyond the f16 range of the split)")
+        self._require_finite(heat, "patch", "heatmaps")
         heat = heat.permute(0, 3, 1, 2)
         if return_features:
             return heat, feat.permute(0, 3, 1, 2)

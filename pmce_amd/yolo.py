@@ -20,6 +20,7 @@ import numpy as np
 import torch
 
 from . import _lib
+from ._net import DeviceNetwork, clean_state_dict, take_tensors
 from .crops import CHANNEL_ORDERS, MAX_DIM, _device_of
 from .extractor import BN_EPS, fold_bn
 
@@ -176,24 +177,9 @@ def required_keys(spec):
 
 
 def select_state_dict(sd, spec):
-    """The detector's tensors of a state dict (an optional ``module.`` prefix stripped, ``num_batches_tracked`` ignored) as fp32 CPU
+    """The detector's tensors of a state dict (cleaned as ``_net.clean_state_dict`` cleans) as fp32 CPU
     tensors.  A missing or mis-shaped tensor raises a ValueError that names it."""
-    if not hasattr(sd, "items"):
-        raise ValueError(f"a state dict is a mapping of names to tensors (got {type(sd).__name__})")
-    clean = {}
-    for k, v in sd.items():
-        k = k[len("module."):] if k.startswith("module.") else k
-        if not k.endswith("num_batches_tracked"):
-            clean[k] = v
-    out = OrderedDict()
-    for name, shape in required_keys(spec).items():
-        if name not in clean:
-            raise ValueError(f"the state dict has no tensor '{name}' (expected shape {tuple(shape)})")
-        t = torch.as_tensor(clean[name])
-        if tuple(t.shape) != tuple(shape):
-            raise ValueError(f"tensor '{name}' has shape {tuple(t.shape)}, expected {tuple(shape)}")
-        out[name] = t.detach().to(device="cpu", dtype=torch.float32)
-    return out
+    return take_tensors(clean_state_dict(sd), required_keys(spec), torch.float32)
 
 
 def read_darknet_weights(path, spec):
@@ -441,39 +427,29 @@ def _create(spec):
     return h
 
 
-class YOLOv3:
+class YOLOv3(DeviceNetwork):
     """A darknet-style detector as HIP convolutions.  ``max_batch``: images per launch sequence (the workspace is allocated for it and
     the largest side seen, and reused); ``check_finite``: raise when a row is not finite, naming the first such image."""
+    NAME = "yolo"
+    MAX_BATCH = 1024
 
     def __init__(self, folded, device, spec=None, max_batch: int = 12, check_finite: bool = True):
-        if int(max_batch) != max_batch or not 1 <= int(max_batch) <= 1024:
-            raise ValueError(f"max_batch must be a whole number in 1..1024 (got {max_batch!r})")
+        super().__init__(device, max_batch, check_finite)
         self.spec = spec if spec is not None else yolov3_spec()
-        self.device = torch.device(device)
-        self.max_batch = int(max_batch)
-        self.check_finite = bool(check_finite)
         self.num_classes = int(self.spec["num_classes"])
-        self._ws = None
         lib = _lib.load()
-        self._h = _create(self.spec)
-        shape = (C.c_int * 4)()
-        with torch.cuda.device(self.device):
-            keep = []
+        self._h = h = _create(self.spec)
+
+        def uploads():
+            shape = (C.c_int * 4)()
             for i, want, _, _, _ in conv_table(self.spec):
-                _lib.check(lib.pmce_yolo_conv_shape(self._h, i, shape), "yolo_conv_shape")
+                _lib.check(lib.pmce_yolo_conv_shape(h, i, shape), "yolo_conv_shape")
                 w, b = folded[i]
                 assert tuple(shape) == tuple(want) == tuple(w.shape) and tuple(b.shape) == (want[0],), f"layer {i}"
-                wd, bd = w.to(self.device).contiguous(), b.to(self.device).contiguous()
-                keep.append((wd, bd))
-                _lib.check(lib.pmce_yolo_set_conv(self._h, i, _lib.ptr(wd), _lib.ptr(bd)), "yolo_set_conv")
-            torch.cuda.current_stream().synchronize()        # the uploads (pageable copies run on the legacy stream) are done
-            _lib.check(lib.pmce_yolo_finalize_on(self._h, _lib.current_stream()), "yolo_finalize")
-            del keep
+                set_conv = lambda wp, bp, i=i: _lib.check(lib.pmce_yolo_set_conv(h, i, wp, bp), "yolo_set_conv")  # noqa: E731
+                yield set_conv, (w, b)
 
-    def __del__(self):
-        h, self._h = getattr(self, "_h", None), None
-        if h and _lib._lib is not None:
-            _lib._lib.pmce_yolo_destroy(h)
+        self._finalize(uploads())
 
     @classmethod
     def from_state_dict(cls, sd, device="cuda", spec=None, **kw):
@@ -497,43 +473,24 @@ class YOLOv3:
                 ckpt = ckpt[key]
         return cls.from_state_dict(ckpt, device, spec=spec, **kw)
 
-    def _workspace(self, S):
-        nbytes = _lib.load().pmce_yolo_workspace_bytes(self._h, self.max_batch, S)
-        if nbytes == 0:
-            raise _lib.PmceError(_lib.last_error())
-        if self._ws is None or self._ws.numel() * 4 < nbytes:
-            self._ws = None
-            self._ws = torch.empty(nbytes // 4, device=self.device, dtype=torch.float32)
-        return self._ws
-
     @torch.no_grad()
     def forward(self, images, return_maps: bool = False):
         """images fp32 [n,3,S,S] in [0, 1] (a host tensor is uploaded; any strides) -> rows fp32 [n, R, 5 + nc] = (cx, cy, w, h, conf,
         classes) in pixels of the S x S input, ordered stride 32, 16, 8, then anchor, gy, gx [, the three raw detection maps as NCHW
         views [n, 3 (5 + nc), g, g]], by pmce_yolo_forward on the current stream, ``max_batch`` images at a time."""
         n, S = check_images(images)
-        x = images.to(self.device)
-        if any(s < 1 for s in x.stride()):
-            x = x.contiguous()
         E = 5 + self.num_classes
         gs = grids(self.spec, S)
         rows = torch.empty(n, 3 * sum(g * g for g in gs), E, device=self.device, dtype=torch.float32)
         maps = [torch.empty(n, g, g, 3 * E, device=self.device, dtype=torch.float32) for g in gs]
         lib = _lib.load()
         with torch.cuda.device(self.device):
-            ws = self._workspace(S) if n else None
-            for i0 in range(0, n, self.max_batch):
-                m = min(self.max_batch, n - i0)
-                xi = x[i0:i0 + m]
-                sn, sc, sy, sx = xi.stride()
+            ws = self._workspace(lib.pmce_yolo_workspace_bytes(self._h, self.max_batch, S)) if n else None
+            for i0, m, xi, (sn, sc, sy, sx) in self._chunks(images):
                 _lib.check(lib.pmce_yolo_forward(self._h, C.c_void_p(xi.data_ptr()), sn, sc, sy, sx, m, S,
                                                  *[C.c_void_p(t[i0:].data_ptr()) for t in maps], C.c_void_p(rows[i0:].data_ptr()), _lib.ptr(ws),
                                                  ws.numel() * 4, _lib.current_stream()), "yolo_forward")
-        if self.check_finite and n:
-            bad = ~torch.isfinite(rows).all(dim=2).all(dim=1)
-            if bool(bad.any()):
-                raise _lib.PmceError(f"yolo: image {int(bad.nonzero()[0])} has non-finite predictions (an input that is not finite, or an "
-                                     "activation beyond the f16 range of the split)")
+        self._require_finite(rows, "image", "predictions")
         if return_maps:
             return rows, [t.permute(0, 3, 1, 2) for t in maps]
         return rows
