@@ -56,7 +56,7 @@ const char* pmce_last_error_string(void);
  * ------------------------------------------------------------------------------------------------------- */
 typedef struct pmce_model pmce_model;
 
-/* num_joint: J (17, or 19 for COCO-input checkpoints); embed_dim: C (256|512); depth: lifter depth (3).
+/* num_joint: J (17, or 19 for COCO-input checkpoints); embed_dim: C (a multiple of 128 from 128 to 512: 128|256|384|512); depth: lifter depth (3).
  * ENVIRONMENT: the library reads exactly five variables, all here, once per handle; each only sets the initial value of a setting that has an
  * API setter and a getter (tests/test_host_logic.py flips every one):
  *   PMCE_SPLIT_F16=0        initial gemm mode fp32 pipe           (pmce_model_set_gemm_mode / pmce_model_gemm_mode)
@@ -272,21 +272,26 @@ int pmce_embed_tokens_f32(const float* pose2d, const float* E, const float* Wje,
                           float* x, long long ntok, int J, int C, pmce_stream_t stream);
 /* The same followed by LayerNorm(w2, b2, eps2) of every token row (SpatialBlocks[0].norm1, PoseEstimation.py:13-29 via :83) in ONE launch:
  * x = the tokens (fp32 [ntok, C]), xn = their LayerNorm - fp32, or pre-split [row][C/16][16 hi | 16 lo*2^11] f16 when xn_split (the operand of a
- * three-product f16 GEMM).  Bit-identical to pmce_embed_tokens_f32 + pmce_ln_chain_f32(out2).  C = 256 or 512. */
+ * three-product f16 GEMM).  Bit-identical to pmce_embed_tokens_f32 + pmce_ln_chain_f32(out2).  C = 128, 256, 384 or 512. */
 int pmce_embed_ln_f32(const float* pose2d, const float* E, const float* Wje, const float* bje, const float* spos, float* x,
                       long long ntok, int J, int C, const float* w2, const float* b2, float eps2, float* xn, int xn_split,
                       pmce_stream_t stream);
-/* nn.LayerNorm chain over rows of C channels: y1 = (w1 ? LN(x;w1,b1,eps1) : x) + add[(row/add_div)%add_mod];
+/* nn.LayerNorm chain over rows of C channels (C = 128, 256, 384 or 512, as for every row kernel of the lifter): y1 = (w1 ? LN(x;w1,b1,eps1) : x) + add[(row/add_div)%add_mod];
  * out1 = y1 (optional); out2 = LN(y1;w2,b2,eps2) (optional).  norm1/norm2/norm_s/norm_t (PoseEstimation.py:17,23,58-59).
  * out2_split (and out_split / xn_split of the entries below) != 0: out2 / out / XN written pre-split ([row][C/16][16 hi | 16 lo*2^11] f16
  * in the bytes of the fp32 row), i.e. directly as the A operand of pmce_gemm_nt_split_f16(a_packed = 1). */
 int pmce_ln_chain_f32(const float* x, long long rows, int C, const float* w1, const float* b1, float eps1, const float* add,
                       int add_div, int add_mod, float* out1, const float* w2, const float* b2, float eps2, float* out2,
                       int out2_split, pmce_stream_t stream);
-/* timm Attention core on qkv[tok][3C] for sequences of N <= 32 tokens, 8 heads (PoseEstimation.py:19 / CoevoDecoder.py:118-131).
+/* timm Attention core on qkv[tok][3C] for sequences of N <= 32 tokens, 8 heads of 32 or 64 channels (C = 256 or 512;
+ * PoseEstimation.py:19 / CoevoDecoder.py:118-131).
  * sequence s, position i -> token (s % seq_div)*seq_lo + (s / seq_div)*seq_hi + i*tok_stride. */
 int pmce_seq_attention_f32(const float* qkv, float* out, int nseq, int N, int C, int seq_div, long long seq_lo,
                            long long seq_hi, long long tok_stride, int out_split, pmce_stream_t stream);
+/* The same for every width pmce_model_create accepts - what the model calls: C = 256 and 512 are pmce_seq_attention_f32's launches (the same
+ * bits), C = 128 and 384 (heads of 16 and 48 channels) the same kernel at those head sizes.  Any other C returns PMCE_ERR_ARG before any launch. */
+int pmce_lifter_attention_f32(const float* qkv, float* out, int nseq, int N, int C, int seq_div, long long seq_lo,
+                              long long seq_hi, long long tok_stride, int out_split, pmce_stream_t stream);
 /* The same attention (timm Attention of PoseEstimation.py:78-104) on the f16 matrix pipe in the three-product form: q, k, v read
  * as fp32 (split into f16 (hi, lo) planes inside the kernel), the result WRITTEN pre-split ([row][C/16][16 hi | 16 lo*2^11] f16 in
  * the bytes of the fp32 row) as the A operand of proj.  Sequence / token addressing as pmce_seq_attention_f32.  C = 256 or 512 (8 heads),
@@ -295,6 +300,12 @@ int pmce_seq_attention_f32(const float* qkv, float* out, int nseq, int N, int C,
 int pmce_seq_attention_split_supported(int N, int C);
 int pmce_seq_attention_split_f16(const float* qkv, float* out_planes, int nseq, int N, int C, int seq_div, long long seq_lo,
                                  long long seq_hi, long long tok_stride, pmce_stream_t stream);
+/* The matrix-pipe attention for every width pmce_model_create accepts - what the model calls.  C = 256 and 512 are forwarded to pmce_seq_attention_split_f16 (the
+ * same launch, the same bits); C = 128 and 384 (heads of 16 and 48 channels) run the same arithmetic on units of 512 / 768 bytes per row
+ * (lifter_attention_mfma.hip).  N = 16, 17 or 19; anything else returns PMCE_ERR_ARG before any launch. */
+int pmce_lifter_attention_split_supported(int N, int C);
+int pmce_lifter_attention_split_f16(const float* qkv, float* out_planes, int nseq, int N, int C, int seq_div, long long seq_lo,
+                                    long long seq_hi, long long tok_stride, pmce_stream_t stream);
 /* Temporal block, C = 512, split-f16 form: AO = attention(XN Wqkv^T + b) in ONE kernel - what pmce_gemm_nt_split_f16 (a_packed, blocked weight)
  * into fp32 qkv[M][3C] followed by pmce_seq_attention_split_f16(nseq = B*J, N = 16, seq_div = J, seq_lo = 1, seq_hi = 16*J, tok_stride = J) compute,
  * bit for bit, without the qkv tensor.  xn_planes / out_planes: pre-split rows [B*16*J][C/16][16 hi | 16 lo*2^11] f16; Wp / wscale: the [3C][C]

@@ -41,21 +41,45 @@ __global__ __launch_bounds__(256) void embed_tokens_kernel(const float* __restri
 //   out1 = y1 (if out1) ;  out2 = LN(y1; w2,b2,eps2) (if out2)
 // covers norm_s/norm_t (shared across depth, eps 1e-6, :38,84,92) fused with the NEXT block's norm1/norm2.
 // ------------------------------------------------------------------------------------------------------
-// mean and 1 / sqrt(biased variance + eps) of the row a wavefront holds as v[C / 64]
+// Lane layout of a row (every row kernel of this file): lane l holds channels 256 i4 + 4 l + [0, 4) of each 256-channel group i4 - 16-byte
+// accesses, four consecutive channels per lane (what store4_split_f16 needs), and sums that are whole-wavefront reductions.  At C = 128 and
+// 384 the last group is half filled: lanes 32..63 hold none of its channels (lane_on false).  Such a slot is never loaded or stored, holds 0
+// wherever a sum runs over it, and is left out of the variance.  At C = 256 and 512 lane_on is the constant true and the code is what it
+// was before the other widths existed.
+template <int C>
+constexpr int row_nv = 4 * ((C + 255) / 256);  // registers of a row per lane
+template <int C>
+__device__ __forceinline__ bool lane_on(int i4) {
+  if constexpr (C % 256 == 0) return true;
+  else return i4 * 256 + (int)(threadIdx.x & 63) * 4 < C;
+}
+// mean and 1 / sqrt(biased variance + eps) of the row a wavefront holds as v[row_nv<C>]
 template <int C>
 __device__ __forceinline__ void ln_stats(const float* v, float eps, float& mean_, float& inv_) {
-  constexpr int NV = C / 64;
+  constexpr int NV = row_nv<C>;
   float s = 0.f;
 #pragma unroll
   for (int i = 0; i < NV; ++i) s += v[i];
-  const float mean = wave_sum(s) * (1.0f / C);
+  float mean = wave_sum(s) * (1.0f / C);
+  // 1 / C is a power of two at 128, 256 and 512: folding the product into the subtraction below (-ffp-contract=fast) changes no bit there.  At
+  // 384 it does, and hipcc folds it in one kernel and not in another (embed_ln_kernel against ln_chain_kernel, which promise the same bits):
+  // the mean, and the variance below, are ONE fp32 value each (pinned, common.hpp).
+  if constexpr ((C & (C - 1)) != 0) mean = pinned(mean);
   float ss = 0.f;
 #pragma unroll
   for (int i = 0; i < NV; ++i) {
     const float d = v[i] - mean;
-    ss += d * d;
+    if constexpr (C % 256 == 0) {
+      ss += d * d;
+    } else {
+      // an empty slot adds fma(0, 0, ss) = ss; the fused multiply-add is spelled out so that the mask cannot come between product and sum
+      // in one kernel and not in another
+      const float dm = lane_on<C>(i >> 2) ? d : 0.f;
+      ss = fmaf(dm, dm, ss);
+    }
   }
-  const float var = wave_sum(ss) * (1.0f / C);
+  float var = wave_sum(ss) * (1.0f / C);
+  if constexpr ((C & (C - 1)) != 0) var = pinned(var);
   const float inv = 1.0f / sqrtf(var + eps);
   mean_ = mean;
   inv_ = inv;
@@ -66,12 +90,17 @@ __device__ __forceinline__ void ln_regs(float* v, const float* __restrict__ w, c
   float mean, inv;
   ln_stats<C>(v, eps, mean, inv);
 #pragma unroll
-  for (int i4 = 0; i4 < C / 256; ++i4) {
-    const int c = i4 * 256 + lane * 4;
-    const f32x4 wv = *reinterpret_cast<const f32x4*>(w + c);
-    const f32x4 bv = *reinterpret_cast<const f32x4*>(b + c);
+  for (int i4 = 0; i4 < row_nv<C> / 4; ++i4) {
+    if (lane_on<C>(i4)) {
+      const int c = i4 * 256 + lane * 4;
+      const f32x4 wv = *reinterpret_cast<const f32x4*>(w + c);
+      const f32x4 bv = *reinterpret_cast<const f32x4*>(b + c);
 #pragma unroll
-    for (int i = 0; i < 4; ++i) v[i4 * 4 + i] = (v[i4 * 4 + i] - mean) * inv * wv[i] + bv[i];
+      for (int i = 0; i < 4; ++i) v[i4 * 4 + i] = (v[i4 * 4 + i] - mean) * inv * wv[i] + bv[i];
+    } else {
+#pragma unroll
+      for (int i = 0; i < 4; ++i) v[i4 * 4 + i] = 0.f;
+    }
   }
 }
 
@@ -82,14 +111,15 @@ __device__ __forceinline__ void ln_regs_pre(float* v, const float* wreg, const f
   float mean, inv;
   ln_stats<C>(v, eps, mean, inv);
 #pragma unroll
-  for (int i = 0; i < C / 64; ++i) v[i] = (v[i] - mean) * inv * wreg[i] + breg[i];
+  for (int i = 0; i < row_nv<C>; ++i) v[i] = lane_on<C>(i >> 2) ? (v[i] - mean) * inv * wreg[i] + breg[i] : 0.f;
 }
-// this lane's channels (256 i4 + 4 lane + [0, 4)) of a per-channel vector
+// this lane's channels (256 i4 + 4 lane + [0, 4)) of a per-channel vector; 0 in the slots the lane does not hold
 template <int C>
 __device__ __forceinline__ void lane_channels(const float* __restrict__ p, int lane, float* out) {
 #pragma unroll
-  for (int i4 = 0; i4 < C / 256; ++i4) {
-    const f32x4 t = *reinterpret_cast<const f32x4*>(p + i4 * 256 + lane * 4);
+  for (int i4 = 0; i4 < row_nv<C> / 4; ++i4) {
+    f32x4 t = {0.f, 0.f, 0.f, 0.f};
+    if (lane_on<C>(i4)) t = *reinterpret_cast<const f32x4*>(p + i4 * 256 + lane * 4);
 #pragma unroll
     for (int i = 0; i < 4; ++i) out[i4 * 4 + i] = t[i];
   }
@@ -110,7 +140,7 @@ __global__ __launch_bounds__(256) void ln_chain_kernel(const float* __restrict__
                                                        float* __restrict__ out1, const float* __restrict__ w2,
                                                        const float* __restrict__ b2, float eps2, float* __restrict__ out2,
                                                        const int* __restrict__ win, int nframes, int out2_split) {
-  constexpr int NV = C / 64;
+  constexpr int NV = row_nv<C>;
   const int lane = threadIdx.x & 63;
   const long long row = (long long)blockIdx.x * 4 + (threadIdx.x >> 6);
   if (row >= rows) return;
@@ -126,7 +156,8 @@ __global__ __launch_bounds__(256) void ln_chain_kernel(const float* __restrict__
     // Streaming (non-temporal) accesses for the row itself and for the fp32 residual stream out1 (round 4): read once / next touched a
     // product later.  NOT for out2: it is the NEXT product's A operand, and written back normally that product finds it in the Infinity
     // Cache (profiles/r04_g_ln_chain_nontemporal_ab.txt: ln_chain -13 %, the attention after it -5 %, the lifter products -1.6 %).
-    const f32x4 t = __builtin_nontemporal_load(reinterpret_cast<const f32x4*>(x + src * C + i4 * 256 + lane * 4));
+    f32x4 t = {0.f, 0.f, 0.f, 0.f};
+    if (lane_on<C>(i4)) t = __builtin_nontemporal_load(reinterpret_cast<const f32x4*>(x + src * C + i4 * 256 + lane * 4));
 #pragma unroll
     for (int i = 0; i < 4; ++i) v[i4 * 4 + i] = t[i];
   }
@@ -135,6 +166,7 @@ __global__ __launch_bounds__(256) void ln_chain_kernel(const float* __restrict__
     const float* a = add + (long long)((row / add_div) % add_mod) * C;
 #pragma unroll
     for (int i4 = 0; i4 < NV / 4; ++i4) {
+      if (!lane_on<C>(i4)) continue;
       const f32x4 t = *reinterpret_cast<const f32x4*>(a + i4 * 256 + lane * 4);
 #pragma unroll
       for (int i = 0; i < 4; ++i) v[i4 * 4 + i] += t[i];
@@ -146,7 +178,7 @@ __global__ __launch_bounds__(256) void ln_chain_kernel(const float* __restrict__
       f32x4 t;
 #pragma unroll
       for (int i = 0; i < 4; ++i) t[i] = v[i4 * 4 + i];
-      __builtin_nontemporal_store(t, reinterpret_cast<f32x4*>(out1 + row * C + i4 * 256 + lane * 4));
+      if (lane_on<C>(i4)) __builtin_nontemporal_store(t, reinterpret_cast<f32x4*>(out1 + row * C + i4 * 256 + lane * 4));
     }
   }
   if (out2) {
@@ -156,6 +188,7 @@ __global__ __launch_bounds__(256) void ln_chain_kernel(const float* __restrict__
       f32x4 t;
 #pragma unroll
       for (int i = 0; i < 4; ++i) t[i] = v[i4 * 4 + i];
+      if (!lane_on<C>(i4)) continue;
       if (out2_split) store4_split_f16(out2 + row * C, i4 * 256 + lane * 4, t);  // operand of a three-product f16 GEMM
       else *reinterpret_cast<f32x4*>(out2 + row * C + i4 * 256 + lane * 4) = t;
     }
@@ -179,7 +212,7 @@ __global__ __launch_bounds__(256) void embed_ln_kernel(const float* __restrict__
                                                        const float* __restrict__ spos, float* __restrict__ x, long long nframes, int J,
                                                        const float* __restrict__ w2, const float* __restrict__ b2, float eps2,
                                                        float* __restrict__ xn, int xn_split, int wpf) {
-  constexpr int NV = C / 64;
+  constexpr int NV = row_nv<C>;
   const int lane = threadIdx.x & 63;
   const unsigned wid = blockIdx.x * 4u + (threadIdx.x >> 6);  // (ntok < 2^31: 32-bit division)
   const long long bt = wid / (unsigned)wpf;
@@ -192,7 +225,11 @@ __global__ __launch_bounds__(256) void embed_ln_kernel(const float* __restrict__
 #pragma unroll
   for (int i4 = 0; i4 < NV / 4; ++i4) {
     const int c = i4 * 256 + lane * 4;
-    const f32x4 w01 = *reinterpret_cast<const f32x4*>(Wje + c * 2), w23 = *reinterpret_cast<const f32x4*>(Wje + c * 2 + 4);
+    f32x4 w01 = {0.f, 0.f, 0.f, 0.f}, w23 = {0.f, 0.f, 0.f, 0.f};
+    if (lane_on<C>(i4)) {
+      w01 = *reinterpret_cast<const f32x4*>(Wje + c * 2);
+      w23 = *reinterpret_cast<const f32x4*>(Wje + c * 2 + 4);
+    }
     wa[i4 * 4 + 0] = w01[0]; wa[i4 * 4 + 1] = w01[2]; wa[i4 * 4 + 2] = w23[0]; wa[i4 * 4 + 3] = w23[2];
     wb[i4 * 4 + 0] = w01[1]; wb[i4 * 4 + 1] = w01[3]; wb[i4 * 4 + 2] = w23[1]; wb[i4 * 4 + 3] = w23[3];
   }
@@ -203,6 +240,11 @@ __global__ __launch_bounds__(256) void embed_ln_kernel(const float* __restrict__
 #pragma unroll
     for (int i4 = 0; i4 < NV / 4; ++i4) {
       const int c = i4 * 256 + lane * 4;
+      if (!lane_on<C>(i4)) {
+#pragma unroll
+        for (int i = 0; i < 4; ++i) v[i4 * 4 + i] = 0.f;
+        continue;
+      }
       const f32x4 sp = *reinterpret_cast<const f32x4*>(spos + (long long)j * C + c);
       f32x4 o;
 #pragma unroll
@@ -220,6 +262,7 @@ __global__ __launch_bounds__(256) void embed_ln_kernel(const float* __restrict__
       f32x4 t;
 #pragma unroll
       for (int i = 0; i < 4; ++i) t[i] = v[i4 * 4 + i];
+      if (!lane_on<C>(i4)) continue;
       if (xn_split) store4_split_f16(xn + tok * C, i4 * 256 + lane * 4, t);
       else *reinterpret_cast<f32x4*>(xn + tok * C + i4 * 256 + lane * 4) = t;
     }
@@ -501,7 +544,7 @@ __global__ __launch_bounds__(256) void lifter_head_kernel(const float* __restric
   // One WORKGROUP per (b, j); wavefront w takes the frames t = w, w + 4, ... and has FOUR of their rows in flight before it touches the
   // first (round 6; until then one wavefront walked the T rows one after the other - sixteen dependent row fetches, 17 wavefronts per CU:
   // 54 us for a 142 MB read).  The per-frame results meet in LDS and are added in the order of t, as the serial loop added them.
-  constexpr int NV = C / 64, RPW = 4;
+  constexpr int NV = row_nv<C>, RPW = 4;
   __shared__ float part[64][3];
   const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
   const int bj = blockIdx.x;
@@ -524,7 +567,10 @@ __global__ __launch_bounds__(256) void lifter_head_kernel(const float* __restric
       const int t = min(t0 + wave + 4 * k, T - 1);
       const float* row = x + ((long long)(b * T + t) * J + j) * C;
 #pragma unroll
-      for (int i4 = 0; i4 < NV / 4; ++i4) raw[k][i4] = *reinterpret_cast<const f32x4*>(row + i4 * 256 + lane * 4);
+      for (int i4 = 0; i4 < NV / 4; ++i4) {
+        raw[k][i4] = f32x4{0.f, 0.f, 0.f, 0.f};
+        if (lane_on<C>(i4)) raw[k][i4] = *reinterpret_cast<const f32x4*>(row + i4 * 256 + lane * 4);
+      }
     }
 #pragma unroll
     for (int k = 0; k < RPW; ++k) {
@@ -564,10 +610,13 @@ __global__ __launch_bounds__(256) void lifter_head_kernel(const float* __restric
 // ------------------------------------------------------------------------------------------------------
 // C-ABI launchers
 // ------------------------------------------------------------------------------------------------------
-// the row kernels exist for C = 256 and C = 512 (the caller has checked C), four wavefronts per workgroup
+// the row kernels exist for the lifter's widths, C = 128, 256, 384 and 512 (the caller has checked C), four wavefronts per workgroup
+static inline bool row_width_ok(int C) { return C >= 128 && C <= 512 && C % 128 == 0; }
 #define PMCE_LAUNCH_C(kernel, C_, grid, stream, ...)                                          \
   do {                                                                                        \
     if ((C_) == 256) hipLaunchKernelGGL((kernel<256>), dim3(grid), dim3(256), 0, stream, __VA_ARGS__); \
+    else if ((C_) == 128) hipLaunchKernelGGL((kernel<128>), dim3(grid), dim3(256), 0, stream, __VA_ARGS__); \
+    else if ((C_) == 384) hipLaunchKernelGGL((kernel<384>), dim3(grid), dim3(256), 0, stream, __VA_ARGS__); \
     else hipLaunchKernelGGL((kernel<512>), dim3(grid), dim3(256), 0, stream, __VA_ARGS__);    \
   } while (0)
 
@@ -581,13 +630,13 @@ extern "C" int pmce_embed_tokens_f32(const float* pose2d, const float* E, const 
 }
 
 // The same followed by LayerNorm(w2, b2, eps2) of every token row in one launch: x = the tokens (fp32), xn = their LayerNorm (pre-split [row][C/16][16 hi |
-// 16 lo*2^11] f16 when xn_split) - pmce_embed_tokens_f32 + pmce_ln_chain_f32(out2) without the round trip of the tokens.  C = 256 or 512.
+// 16 lo*2^11] f16 when xn_split) - pmce_embed_tokens_f32 + pmce_ln_chain_f32(out2) without the round trip of the tokens.  C = 128, 256, 384 or 512.
 extern "C" int pmce_embed_ln_f32(const float* pose2d, const float* E, const float* Wje, const float* bje, const float* spos, float* x,
                                  long long ntok, int J, int C, const float* w2, const float* b2, float eps2, float* xn, int xn_split,
                                  hipStream_t stream) {
   PMCE_REQUIRE(pose2d && E && Wje && bje && spos && x && w2 && b2 && xn, "embed_ln: null pointer");
-  PMCE_REQUIRE((C == 256 || C == 512) && J > 0 && ntok > 0 && ntok % J == 0 && ntok < (1ll << 31),
-               "embed_ln: C must be 256 or 512, J positive, ntok a positive multiple of J (whole frames) below 2^31");
+  PMCE_REQUIRE(row_width_ok(C) && J > 0 && ntok > 0 && ntok % J == 0 && ntok < (1ll << 31),
+               "embed_ln: C must be 128, 256, 384 or 512, J positive, ntok a positive multiple of J (whole frames) below 2^31");
   const long long nframes = ntok / J;
   // wavefronts per frame: enough wavefronts for the chip (8 per SIMD of 256 CUs), as few as that allows
   long long wpf = (8192 + nframes - 1) / nframes;
@@ -600,7 +649,7 @@ extern "C" int pmce_embed_ln_f32(const float* pose2d, const float* E, const floa
 extern "C" int pmce_ln_chain_f32(const float* x, long long rows, int C, const float* w1, const float* b1, float eps1,
                                  const float* add, int add_div, int add_mod, float* out1, const float* w2, const float* b2,
                                  float eps2, float* out2, int out2_split, hipStream_t stream) {
-  PMCE_REQUIRE(C == 256 || C == 512, "ln_chain: C must be 256 or 512 (got %d)", C);
+  PMCE_REQUIRE(row_width_ok(C), "ln_chain: C must be 128, 256, 384 or 512 (got %d)", C);
   PMCE_REQUIRE(rows > 0 && (out1 || out2), "ln_chain: nothing to do");
   PMCE_REQUIRE(!out2 || (w2 && b2), "ln_chain: out2 needs w2/b2");
   if (add_div <= 0) add_div = 1;
@@ -615,7 +664,7 @@ extern "C" int pmce_ln_chain_f32(const float* x, long long rows, int C, const fl
 extern "C" int pmce_window_tokens_f32(const float* x0, const int* win, const float* tpos, const float* w2, const float* b2,
                                       float eps2, float* X, float* XN, int W, int L, int T, int J, int C, int xn_split,
                                       hipStream_t stream) {
-  PMCE_REQUIRE(C == 256 || C == 512, "window_tokens: C must be 256 or 512");
+  PMCE_REQUIRE(row_width_ok(C), "window_tokens: C must be 128, 256, 384 or 512");
   PMCE_REQUIRE(x0 && win && tpos && w2 && b2 && X && XN && W > 0 && L > 0 && T > 0 && J > 0, "window_tokens: bad args");
   const long long rows = (long long)W * T * J;
   const unsigned grid = (unsigned)((rows + 3) / 4);
@@ -634,7 +683,7 @@ __global__ __launch_bounds__(256) void window_mid_tokens_kernel(const float* __r
                                                                 const float* __restrict__ b2, float eps2, float* __restrict__ X,
                                                                 float* __restrict__ XN, int W, int nframes, int T, int J, int t_mid,
                                                                 int xn_split) {
-  constexpr int NV = C / 64;
+  constexpr int NV = row_nv<C>;
   const int lane = threadIdx.x & 63;
   const long long r = (long long)blockIdx.x * 4 + (threadIdx.x >> 6);  // (w, j)
   if (r >= (long long)W * J) return;
@@ -644,13 +693,15 @@ __global__ __launch_bounds__(256) void window_mid_tokens_kernel(const float* __r
   float v[NV];
 #pragma unroll
   for (int i4 = 0; i4 < NV / 4; ++i4) {
-    const f32x4 t = __builtin_nontemporal_load(reinterpret_cast<const f32x4*>(x0_mid + src * C + i4 * 256 + lane * 4));
+    f32x4 t = {0.f, 0.f, 0.f, 0.f};
+    if (lane_on<C>(i4)) t = __builtin_nontemporal_load(reinterpret_cast<const f32x4*>(x0_mid + src * C + i4 * 256 + lane * 4));
 #pragma unroll
     for (int i = 0; i < 4; ++i) v[i4 * 4 + i] = t[i];
   }
   const float* a = tpos + (long long)t_mid * C;
 #pragma unroll
   for (int i4 = 0; i4 < NV / 4; ++i4) {
+    if (!lane_on<C>(i4)) continue;
     const f32x4 t = *reinterpret_cast<const f32x4*>(a + i4 * 256 + lane * 4);
 #pragma unroll
     for (int i = 0; i < 4; ++i) v[i4 * 4 + i] += t[i];
@@ -660,7 +711,7 @@ __global__ __launch_bounds__(256) void window_mid_tokens_kernel(const float* __r
     f32x4 t;
 #pragma unroll
     for (int i = 0; i < 4; ++i) t[i] = v[i4 * 4 + i];
-    __builtin_nontemporal_store(t, reinterpret_cast<f32x4*>(X + row * C + i4 * 256 + lane * 4));
+    if (lane_on<C>(i4)) __builtin_nontemporal_store(t, reinterpret_cast<f32x4*>(X + row * C + i4 * 256 + lane * 4));
   }
   ln_regs<C>(v, w2, b2, eps2, lane);
 #pragma unroll
@@ -668,6 +719,7 @@ __global__ __launch_bounds__(256) void window_mid_tokens_kernel(const float* __r
     f32x4 t;
 #pragma unroll
     for (int i = 0; i < 4; ++i) t[i] = v[i4 * 4 + i];
+    if (!lane_on<C>(i4)) continue;
     if (xn_split) store4_split_f16(XN + row * C, i4 * 256 + lane * 4, t);
     else *reinterpret_cast<f32x4*>(XN + row * C + i4 * 256 + lane * 4) = t;
   }
@@ -676,7 +728,7 @@ __global__ __launch_bounds__(256) void window_mid_tokens_kernel(const float* __r
 extern "C" int pmce_window_mid_tokens_f32(const float* x0_mid, const int* win, const float* tpos, const float* w2, const float* b2,
                                           float eps2, float* X, float* XN, int W, int L, int T, int J, int C, int t_mid, int xn_split,
                                           hipStream_t stream) {
-  PMCE_REQUIRE(C == 256 || C == 512, "window_mid_tokens: C must be 256 or 512");
+  PMCE_REQUIRE(row_width_ok(C), "window_mid_tokens: C must be 128, 256, 384 or 512");
   PMCE_REQUIRE(x0_mid && win && tpos && w2 && b2 && X && XN && W > 0 && L > 0 && T > 0 && J > 0 && t_mid >= 0 && t_mid < T,
                "window_mid_tokens: bad args");
   const long long rows = (long long)W * J;
@@ -722,10 +774,9 @@ static int launch_seq_attention_pair(const float* qkv, float* out, int nseq, int
   return pmce_check_launch("seq_attention");
 }
 
-extern "C" int pmce_seq_attention_f32(const float* qkv, float* out, int nseq, int N, int C, int seq_div, long long seq_lo,
-                                      long long seq_hi, long long tok_stride, int out_split, hipStream_t stream) {
-  PMCE_REQUIRE(C == 256 || C == 512, "seq_attention: C must be 256 or 512 (8 heads of 32/64)");
-  PMCE_REQUIRE(N >= 1 && N <= 32 && nseq > 0, "seq_attention: N must be in 1..32 (got %d)", N);
+// every width of the lifter (the two entries below have checked C and N)
+static int launch_seq_attention(const float* qkv, float* out, int nseq, int N, int C, int seq_div, long long seq_lo, long long seq_hi,
+                                long long tok_stride, int out_split, hipStream_t stream) {
   if (seq_div <= 0) seq_div = 0x7fffffff;
   {  // the sequence lengths of the path: 16 frames, 17 (H36M) or 19 (COCO + pelvis, neck) joints
     // C = 512 only: at C = 256 both kernels sit at the same ~4 TB/s (the first one already has 16 waves per CU there)
@@ -737,7 +788,15 @@ extern "C" int pmce_seq_attention_f32(const float* qkv, float* out, int nseq, in
 #undef PMCE_PAIR
   }
   const size_t lds = (size_t)2 * N * C * sizeof(float);
-  if (C == 256) {
+  if (C == 128) {  // 2 N C floats: 32 KB at N = 32, inside the default limit
+    hipLaunchKernelGGL((seq_attention_kernel<16>), dim3(nseq), dim3(256), lds, stream, qkv, out, N, seq_div, seq_lo, seq_hi,
+                       tok_stride, out_split);
+  } else if (C == 384) {
+    static std::atomic<unsigned long long> attr384{0};
+    PMCE_TRY(pmce_opt_in_lds((const void*)seq_attention_kernel<48>, 98304, attr384, "seq_attention"));
+    hipLaunchKernelGGL((seq_attention_kernel<48>), dim3(nseq), dim3(256), lds, stream, qkv, out, N, seq_div, seq_lo, seq_hi,
+                       tok_stride, out_split);
+  } else if (C == 256) {
     static std::atomic<unsigned long long> attr256{0};
     PMCE_TRY(pmce_opt_in_lds((const void*)seq_attention_kernel<32>, 65536, attr256, "seq_attention"));
     hipLaunchKernelGGL((seq_attention_kernel<32>), dim3(nseq), dim3(256), lds, stream, qkv, out, N, seq_div, seq_lo, seq_hi,
@@ -751,12 +810,29 @@ extern "C" int pmce_seq_attention_f32(const float* qkv, float* out, int nseq, in
   return pmce_check_launch("seq_attention");
 }
 
+extern "C" int pmce_seq_attention_f32(const float* qkv, float* out, int nseq, int N, int C, int seq_div, long long seq_lo,
+                                      long long seq_hi, long long tok_stride, int out_split, hipStream_t stream) {
+  PMCE_REQUIRE(C == 256 || C == 512, "seq_attention: C must be 256 or 512 (8 heads of 32/64)");
+  PMCE_REQUIRE(N >= 1 && N <= 32 && nseq > 0, "seq_attention: N must be in 1..32 (got %d)", N);
+  return launch_seq_attention(qkv, out, nseq, N, C, seq_div, seq_lo, seq_hi, tok_stride, out_split, stream);
+}
+
+// The same at every width pmce_model_create accepts - what the model calls: 256 and 512 are the launches above (the same bits), 128 and 384 run
+// seq_attention_kernel<16> / <48>.  (An entry of its own because pmce_seq_attention_f32's refusal of every other width is part of its contract.)
+extern "C" int pmce_lifter_attention_f32(const float* qkv, float* out, int nseq, int N, int C, int seq_div, long long seq_lo,
+                                         long long seq_hi, long long tok_stride, int out_split, hipStream_t stream) {
+  PMCE_REQUIRE(qkv && out, "lifter_attention: null pointer");
+  PMCE_REQUIRE(row_width_ok(C), "lifter_attention: C must be 128, 256, 384 or 512 (8 heads of 16, 32, 48 or 64; got %d)", C);
+  PMCE_REQUIRE(N >= 1 && N <= 32 && nseq > 0, "lifter_attention: N must be in 1..32 (got %d)", N);
+  return launch_seq_attention(qkv, out, nseq, N, C, seq_div, seq_lo, seq_hi, tok_stride, out_split, stream);
+}
+
 // prew != null: x holds the LAST TemporalBlock's output BEFORE its post-norm; the rows pass through LayerNorm(prew, preb, pre_eps) (norm_t,
 // PoseEstimation.py:92) on the way in - the head then needs no ln_chain launch (and no 2 x 143 MB round trip at B = 256, C = 512) in front of it.
 extern "C" int pmce_lifter_head_f32(const float* x, const float* prew, const float* preb, float pre_eps, const float* lnw,
                                     const float* lnb, const float* Wr, const float* br, const float* wf, const float* bf,
                                     float* pose3d, int B, int T, int J, int C, hipStream_t stream) {
-  PMCE_REQUIRE(C == 256 || C == 512, "lifter_head: C must be 256 or 512");
+  PMCE_REQUIRE(row_width_ok(C), "lifter_head: C must be 128, 256, 384 or 512");
   PMCE_REQUIRE((prew == nullptr) == (preb == nullptr), "lifter_head: the pre-norm needs weight and bias");
   PMCE_REQUIRE(T > 0 && T <= 64, "lifter_head: 1..64 frames per clip");
   const unsigned grid = (unsigned)(B * J);

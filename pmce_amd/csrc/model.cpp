@@ -437,9 +437,10 @@ int lifter_block_body(pmce_model* m, int kind, int i, long long M, int nframes, 
   const int J = m->J, C = m->C;
   const LifterBlockW& bw = m->w.blk[kind][i];
   const LifterBlockSplit& sw = m->sp.sblk[kind][i];
-  // split mode: the attention runs on the f16 matrix pipe too (seq_attention_mfma.hip; reads the fp32 q, k, v, writes AO pre-split)
+  // split mode: the attention runs on the f16 matrix pipe too (seq_attention_mfma.hip, lifter_attention_mfma.hip at C = 128 / 384; reads the
+  // fp32 q, k, v, writes AO pre-split)
   const int N_seq = kind == 0 ? J : T;
-  const bool mfma_attn = m->split_now && pmce_seq_attention_split_supported(N_seq, C);
+  const bool mfma_attn = m->split_now && pmce_lifter_attention_split_supported(N_seq, C);
   const bool fused_attn = sw.qkv.wp && qkv_attn_fused_now(m, kind, B);
   if (fused_attn) {  // XN -> AO in one launch, timed with the products; w.QKV is not touched
     RUN(P_GEMM_LIFTER, stream, pmce_qkv_attention_fused_split_f16(w.XN, sw.qkv.wp, sw.qkv.scale, bw.qkv_b, w.AO, B, J, C, nullptr, stream));
@@ -447,11 +448,11 @@ int lifter_block_body(pmce_model* m, int kind, int i, long long M, int nframes, 
     RUN(P_GEMM_LIFTER, stream, lgemm(m, w.XN, bw.qkv_w, sw.qkv, bw.qkv_b, nullptr, w.QKV,
                                      (int)M, 3 * C, C, C, 3 * C, 0, stream, pk(m)));
     if (kind == 0) {  // sequences = frames, tokens j contiguous                      (PoseEstimation.py:78,101)
-      if (mfma_attn) RUN(P_SEQ_ATTN, stream, pmce_seq_attention_split_f16(w.QKV, w.AO, nframes, J, C, 0, J, 0, 1, stream));
-      else RUN(P_SEQ_ATTN, stream, pmce_seq_attention_f32(w.QKV, w.AO, nframes, J, C, 0, J, 0, 1, pk(m), stream));
+      if (mfma_attn) RUN(P_SEQ_ATTN, stream, pmce_lifter_attention_split_f16(w.QKV, w.AO, nframes, J, C, 0, J, 0, 1, stream));
+      else RUN(P_SEQ_ATTN, stream, pmce_lifter_attention_f32(w.QKV, w.AO, nframes, J, C, 0, J, 0, 1, pk(m), stream));
     } else {  // sequences = (b,j), tokens t at stride J                              (PoseEstimation.py:87,104)
-      if (mfma_attn) RUN(P_SEQ_ATTN, stream, pmce_seq_attention_split_f16(w.QKV, w.AO, B * J, T, C, J, 1, (long long)T * J, J, stream));
-      else RUN(P_SEQ_ATTN, stream, pmce_seq_attention_f32(w.QKV, w.AO, B * J, T, C, J, 1, (long long)T * J, J, pk(m), stream));
+      if (mfma_attn) RUN(P_SEQ_ATTN, stream, pmce_lifter_attention_split_f16(w.QKV, w.AO, B * J, T, C, J, 1, (long long)T * J, J, stream));
+      else RUN(P_SEQ_ATTN, stream, pmce_lifter_attention_f32(w.QKV, w.AO, B * J, T, C, J, 1, (long long)T * J, J, pk(m), stream));
     }
   }
   const bool fuse = ln_in_product(m) && sw.proj.wp && sw.fc2.wp;
@@ -911,7 +912,8 @@ extern "C" {
 int pmce_model_create(int num_joint, int embed_dim, int depth, pmce_model** out) {
   PMCE_REQUIRE(out, "model_create: null out");
   PMCE_REQUIRE(num_joint >= 17 && num_joint <= 32, "model_create: num_joint must be in 17..32 (vj_relation indexes 0..16)");
-  PMCE_REQUIRE(embed_dim == 256 || embed_dim == 512, "model_create: embed_dim must be 256 or 512");
+  PMCE_REQUIRE(embed_dim >= 128 && embed_dim <= 512 && embed_dim % 128 == 0,
+               "model_create: embed_dim must be a multiple of 128 from 128 to 512 (128, 256, 384 or 512; got %d)", embed_dim);
   PMCE_REQUIRE(depth >= 1 && depth <= 8, "model_create: depth must be in 1..8");
   pmce_model* m = new pmce_model();
   m->J = num_joint;

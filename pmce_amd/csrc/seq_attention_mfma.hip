@@ -334,6 +334,10 @@ extern "C" int pmce_seq_attention_split_f16(const float* qkv, float* out, int ns
 // and spells the same softmax.
 #include "qkv_attention_fused.hip"
 
+// The same attention at the lifter's other head sizes (16 and 48 channels: chunks of 512 and 768 bytes), and the entry pair that serves
+// every width the model accepts: it shares split8_fused and spells the same softmax too.
+#include "lifter_attention_mfma.hip"
+
 // The feature extractor's convolution (the same three-product split on the same matrix instruction) and its pools are compiled here as
 // well: the library's f16 matrix code stays in the translation units it was in.
 #include "conv.hip"

@@ -295,6 +295,26 @@ def seq_attention_split(qkv, nseq, N, Cc, seq_div, seq_lo, seq_hi, tok_stride, o
     return out
 
 
+def lifter_attention(qkv, nseq, N, Cc, seq_div, seq_lo, seq_hi, tok_stride, out_split=False, out=None):
+    """:func:`seq_attention` at every width the model accepts (C = 128, 256, 384, 512): the entry the model calls."""
+    lib = _lib.load()
+    qkv = _c(qkv)
+    out = _attention_out(qkv, Cc, out)
+    _lib.check(lib.pmce_lifter_attention_f32(P(qkv), P(out), nseq, N, Cc, seq_div, seq_lo, seq_hi, tok_stride,
+                                             1 if out_split else 0, _st()), "lifter_attention")
+    return out
+
+
+def lifter_attention_split(qkv, nseq, N, Cc, seq_div, seq_lo, seq_hi, tok_stride, out=None):
+    """:func:`seq_attention_split` at every width the model accepts (C = 128, 256, 384, 512): the entry the model calls."""
+    lib = _lib.load()
+    qkv = _c(qkv)
+    out = _attention_out(qkv, Cc, out)
+    _lib.check(lib.pmce_lifter_attention_split_f16(P(qkv), P(out), nseq, N, Cc, seq_div, seq_lo, seq_hi, tok_stride, _st()),
+               "lifter_attention_split_f16")
+    return out
+
+
 def qkv_attention_fused(xn_planes, Wblk, wscale, bias, B, J, overflow_word=None):
     """Temporal block at C = 512: pre-split XN [B*16*J, 512] -> pre-split attention output, one kernel (qkv_attention_fused.hip).
     overflow_word: optional int32 device tensor of one element, set to 1 when a result is not finite."""
