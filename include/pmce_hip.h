@@ -301,8 +301,8 @@ int pmce_seq_attention_split_supported(int N, int C);
 int pmce_seq_attention_split_f16(const float* qkv, float* out_planes, int nseq, int N, int C, int seq_div, long long seq_lo,
                                  long long seq_hi, long long tok_stride, pmce_stream_t stream);
 /* The matrix-pipe attention for every width pmce_model_create accepts - what the model calls.  C = 256 and 512 are forwarded to pmce_seq_attention_split_f16 (the
- * same launch, the same bits); C = 128 and 384 (heads of 16 and 48 channels) run the same arithmetic on units of 512 / 768 bytes per row
- * (lifter_attention_mfma.hip).  N = 16, 17 or 19; anything else returns PMCE_ERR_ARG before any launch. */
+ * same launch, the same bits); C = 128 and 384 (heads of 16 and 48 channels) run the same head stage (attention_head of
+ * seq_attention_mfma.hip) on units of 512 / 768 bytes per row (lifter_attention_mfma.hip).  N = 16, 17 or 19; anything else returns PMCE_ERR_ARG before any launch. */
 int pmce_lifter_attention_split_supported(int N, int C);
 int pmce_lifter_attention_split_f16(const float* qkv, float* out_planes, int nseq, int N, int C, int seq_div, long long seq_lo,
                                     long long seq_hi, long long tok_stride, pmce_stream_t stream);

@@ -51,6 +51,134 @@ __device__ __forceinline__ void split8_fused(const f32x4& x0, const f32x4& x1, f
   for (int e = 0; e < 8; ++e) lo[e] = lo_plane(v[e], hi[e]);
 }
 
+// One head of one sequence, shared by seq_attention_mfma_kernel (HD = 32, 64) and lifter_attention_mfma_kernel (HD = 16, 48;
+// lifter_attention_mfma.hip): its tile counts and constants, and the stage from "K and V rows of the head are in LDS as (hi, lo) planes,
+// Q is split in registers" to "the result is written pre-split into the dead K rows".  The staging around it is each kernel's own.
+template <int HD, int N>
+struct HeadCfg {
+  static_assert(HD == 16 || HD == 32 || HD == 48 || HD == 64, "head sizes with a scale below");
+  static constexpr int KSTEPS = HD / 16, DBLK = (HD + 31) / 32, PSTEPS = N > 16 ? 2 : 1;
+  // hd^-0.5 * log2(e): scores in log2 units, softmax on the hardware 2^x
+  static constexpr float scale =
+      (HD == 16 ? 0.25f : HD == 32 ? 0.17677669529663688110f : HD == 48 ? 0.14433756729740643f : 0.125f) * 1.44269504088896340736f;
+  static constexpr float two_m11 = 0.00048828125f;
+};
+
+// U: the LDS region that holds N K rows, then N V rows, at a stride of RS bytes; hoff: the head's byte offset inside a row; rowc, l31, hb:
+// the lane's clamped row, lane & 31 and lane >> 5; qh, ql: the head's KSTEPS Q fragments.  Out blocks: out^T has HD rows, the matrix tile
+// 32 - where HD is no multiple of 32 the last tile's rows past the head repeat its last channel (computed, never stored).
+// SCHED_BARRIER: a scheduling barrier between the head's LDS reads and the dependent chain (scores -> softmax -> P V).
+template <int HD, int N, int RS, bool SCHED_BARRIER>
+__device__ __forceinline__ void attention_head(unsigned char* U, int hoff, int rowc, int l31, int hb, const f16x8* qh, const f16x8* ql,
+                                               bool& bad) {
+  using Cfg = HeadCfg<HD, N>;
+  constexpr float scale = Cfg::scale, two_m11 = Cfg::two_m11;
+  // Every LDS read of the head - the K fragments and the gathered V^T fragments - is issued here, ahead of the dependent chain.
+  const unsigned char* pk = U + rowc * RS + hoff + hb * 16;
+  f16x8 kh[Cfg::KSTEPS], kl[Cfg::KSTEPS];
+#pragma unroll
+  for (int ks = 0; ks < Cfg::KSTEPS; ++ks) {
+    kh[ks] = *reinterpret_cast<const f16x8*>(pk + ks * 64);
+    kl[ks] = *reinterpret_cast<const f16x8*>(pk + ks * 64 + 32);
+  }
+  f16x8 vh[Cfg::DBLK][Cfg::PSTEPS], vl[Cfg::DBLK][Cfg::PSTEPS];
+#pragma unroll
+  for (int blk = 0; blk < Cfg::DBLK; ++blk) {
+    // f16 index of channel ch = 32 blk + l31 inside the row's planes: group ch >> 4 of 32 halves, hi at ch & 15, lo 16 further; the rows of
+    // the tile past the head's last channel repeat that channel
+    const int ch = min(32 * blk + l31, HD - 1);
+    const _Float16* pv = reinterpret_cast<const _Float16*>(U + N * RS + hoff) + (ch >> 4) * 32 + (ch & 15);
+#pragma unroll
+    for (int s = 0; s < Cfg::PSTEPS; ++s) {
+      // keys 16.. exist only up to N - 1 (and only in the hb = 0 half): the other slots carry p = 0 and may hold any finite v
+#pragma unroll
+      for (int e = 0; e < 8; ++e) {
+        const int key = 16 * s + (e & 3) + 8 * (e >> 2);  // + 4 hb
+        if (s == 0 || key < N) {
+          const _Float16* pr = pv + (size_t)min(key + 4 * hb, N - 1) * (RS / 2);
+          vh[blk][s][e] = pr[0];
+          vl[blk][s][e] = pr[16];
+        } else {
+          vh[blk][s][e] = vh[blk][s][0];
+          vl[blk][s][e] = vl[blk][s][0];
+        }
+      }
+    }
+  }
+  if constexpr (SCHED_BARRIER) __builtin_amdgcn_sched_barrier(0);
+  // ---- S^T = K Q^T ----
+  f32x16 s_main, s_cross;
+#pragma unroll
+  for (int r = 0; r < 16; ++r) s_main[r] = s_cross[r] = 0.f;
+#pragma unroll
+  for (int ks = 0; ks < Cfg::KSTEPS; ++ks) {
+    s_main = __builtin_amdgcn_mfma_f32_32x32x16_f16(kh[ks], qh[ks], s_main, 0, 0, 0);
+    s_cross = __builtin_amdgcn_mfma_f32_32x32x16_f16(kh[ks], ql[ks], s_cross, 0, 0, 0);
+    s_cross = __builtin_amdgcn_mfma_f32_32x32x16_f16(kl[ks], qh[ks], s_cross, 0, 0, 0);
+  }
+  // ---- softmax over the keys of this lane's query: register r is key 4 hb + (r & 3) + 8 (r >> 2) ----
+  float p[16];
+  float mx = -INFINITY;
+#pragma unroll
+  for (int r = 0; r < 16; ++r) {
+    const int key = 4 * hb + (r & 3) + 8 * (r >> 2);
+    const float sv = fmaf(s_cross[r], two_m11, s_main[r]) * scale;
+    p[r] = (r < 8 || N > 16) ? (key < N ? sv : -INFINITY) : -INFINITY;  // (N <= 16: registers 8..15 are keys >= 16)
+    mx = fmaxf(mx, p[r]);
+  }
+  mx = fmaxf(mx, __shfl_xor(mx, 32));
+  float sum = 0.f;
+#pragma unroll
+  for (int r = 0; r < 16; ++r) {
+    p[r] = __builtin_amdgcn_exp2f(p[r] - mx);
+    sum += p[r];
+  }
+  sum += __shfl_xor(sum, 32);
+  const float inv = 1.0f / sum;
+  // ---- out^T = V^T P^T, one 32-channel block at a time; P split ONCE for the head (it was split again for every block) ----
+  f16x8 ph[Cfg::PSTEPS], pl[Cfg::PSTEPS];
+#pragma unroll
+  for (int s = 0; s < Cfg::PSTEPS; ++s)
+#pragma unroll
+    for (int e = 0; e < 8; ++e) {
+      const float pv32 = pinned(p[8 * s + e]);
+      ph[s][e] = (_Float16)pv32;
+      pl[s][e] = lo_plane(pv32, ph[s][e]);
+    }
+#pragma unroll
+  for (int blk = 0; blk < Cfg::DBLK; ++blk) {
+    f32x16 o_main, o_cross;
+#pragma unroll
+    for (int r = 0; r < 16; ++r) o_main[r] = o_cross[r] = 0.f;
+#pragma unroll
+    for (int s = 0; s < Cfg::PSTEPS; ++s) {
+      o_main = __builtin_amdgcn_mfma_f32_32x32x16_f16(vh[blk][s], ph[s], o_main, 0, 0, 0);
+      o_cross = __builtin_amdgcn_mfma_f32_32x32x16_f16(vh[blk][s], pl[s], o_cross, 0, 0, 0);
+      o_cross = __builtin_amdgcn_mfma_f32_32x32x16_f16(vl[blk][s], ph[s], o_cross, 0, 0, 0);
+    }
+    // register r is channel 32 blk + 4 hb + (r & 3) + 8 (r >> 2) of query l31: four consecutive channels per r >> 2, written
+    // pre-split into this head's bytes of the (dead) K row of that query; the quads past the head's last channel are dropped
+    if (l31 < N) {
+      unsigned char* po = U + l31 * RS + hoff;
+#pragma unroll
+      for (int rq = 0; rq < 4; ++rq) {
+        if (32 * blk + 8 * rq >= HD) continue;
+        f16x4 oh, ol;
+#pragma unroll
+        for (int e = 0; e < 4; ++e) {
+          const float v = pinned(fmaf(o_cross[4 * rq + e], two_m11, o_main[4 * rq + e]) * inv);
+          bad = bad || nonfinite(v);
+          oh[e] = (_Float16)v;
+          ol[e] = lo_plane(v, oh[e]);
+        }
+        const int g16 = 2 * blk + (rq >> 1), idx = 8 * (rq & 1) + 4 * hb;
+        *reinterpret_cast<f16x4*>(po + g16 * 64 + idx * 2) = oh;
+        *reinterpret_cast<f16x4*>(po + g16 * 64 + 32 + idx * 2) = ol;
+      }
+    }
+  }
+}
+
 template <int HD, int N>
 struct AttnCfg {
   static constexpr int C = 8 * HD;
@@ -62,8 +190,7 @@ struct AttnCfg {
   static constexpr int DPW = (2 * N + 3) / 4;      // DMA instructions per wave and unit (the last ones may repeat a row)
   static constexpr int ST = (N + 3) / 4;           // result store instructions per wave and unit
   static constexpr int LDS_BYTES = NS * UNIT;
-  static constexpr int KSTEPS = HD / 16, DBLK = HD / 32, PSTEPS = N > 16 ? 2 : 1;
-  static constexpr int QL = 2 * KSTEPS * HPW;      // 16-byte Q loads per lane and unit
+  static constexpr int QL = 2 * HeadCfg<HD, N>::KSTEPS * HPW;  // 16-byte Q loads per lane and unit
 };
 
 template <int HD, int N>
@@ -72,6 +199,7 @@ __global__ __launch_bounds__(256, 2) void seq_attention_mfma_kernel(const float*
                                                                    long long tok_stride, unsigned* oflow) {
   using Cfg = AttnCfg<HD, N>;
   constexpr int C = Cfg::C, UPS = Cfg::UPS, HPW = Cfg::HPW, RS = Cfg::RS, UNIT = Cfg::UNIT, DPW = Cfg::DPW, ST = Cfg::ST, QL = Cfg::QL;
+  constexpr int KSTEPS = HeadCfg<HD, N>::KSTEPS;
   extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
   const int tid = threadIdx.x, lane = tid & 63, wave = __builtin_amdgcn_readfirstlane(tid >> 6);
   const int l31 = lane & 31, hb = lane >> 5;
@@ -114,13 +242,14 @@ __global__ __launch_bounds__(256, 2) void seq_attention_mfma_kernel(const float*
     }
   };
 
-  // hd^-0.5 * log2(e): scores in log2 units, softmax on the hardware 2^x
-  constexpr float scale = (HD == 32 ? 0.17677669529663688110f : 0.125f) * 1.44269504088896340736f;
-  constexpr float two_m11 = 0.00048828125f;
   bool bad = false;
-  f32x4 qraw[QL];
+  // The next unit's Q rows, carried around the unit loop.  In a struct on purpose: a bare array of this size is what the compiler's
+  // alloca-to-vector promotion turns into ONE 32-float value before the loops are unrolled (its register budget was used up by the head's
+  // own arrays while the head stage was written out in this kernel), and the loop's back edge then copies it dword by dword: +40
+  // instructions per unit, +1 to 2 % per launch at C = 512.  A struct is left for the pass that splits it by element.
+  struct { f32x4 v[QL]; } qraw;
   if (nmine > 0) {
-    load_q(0, qraw);
+    load_q(0, qraw.v);
     issue(0, 0);
   }
   int slot = 0;
@@ -131,9 +260,9 @@ __global__ __launch_bounds__(256, 2) void seq_attention_mfma_kernel(const float*
     __syncthreads();  // every wave's rows of unit `it` are in LDS; every wave is done with the other slot
     f16x8 qh[QL / 2], ql[QL / 2];
 #pragma unroll
-    for (int i = 0; i < QL / 2; ++i) split8_fused(qraw[2 * i], qraw[2 * i + 1], qh[i], ql[i]);
+    for (int i = 0; i < QL / 2; ++i) split8_fused(qraw.v[2 * i], qraw.v[2 * i + 1], qh[i], ql[i]);
     if (it + 1 < nmine) {
-      load_q(it + 1, qraw);
+      load_q(it + 1, qraw.v);
       issue(it + 1, slot ^ 1);
     }
     unsigned char* const U = smem + slot * UNIT;
@@ -169,111 +298,8 @@ __global__ __launch_bounds__(256, 2) void seq_attention_mfma_kernel(const float*
     __builtin_amdgcn_wave_barrier();
     __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
 #pragma unroll
-    for (int h = 0; h < HPW; ++h) {
-      const int hoff = (wave * HPW + h) * (HD * 4);  // this head's bytes inside a row of the unit
-      // Every LDS read of the head - the K fragments and the gathered V^T fragments - is issued here, ahead of the dependent
-      // chain (scores -> softmax -> P V).
-      const unsigned char* pk = U + rowc * RS + hoff + hb * 16;
-      f16x8 kh[Cfg::KSTEPS], kl[Cfg::KSTEPS];
-#pragma unroll
-      for (int ks = 0; ks < Cfg::KSTEPS; ++ks) {
-        kh[ks] = *reinterpret_cast<const f16x8*>(pk + ks * 64);
-        kl[ks] = *reinterpret_cast<const f16x8*>(pk + ks * 64 + 32);
-      }
-      f16x8 vh[Cfg::DBLK][Cfg::PSTEPS], vl[Cfg::DBLK][Cfg::PSTEPS];
-#pragma unroll
-      for (int blk = 0; blk < Cfg::DBLK; ++blk) {
-        // f16 index of channel 32 blk + l31 inside the row's planes: group (2 blk + (l31 >> 4)) of 32 halves, hi at (l31 & 15), lo 16 further
-        const _Float16* pv = reinterpret_cast<const _Float16*>(U + N * RS + hoff) + (2 * blk + (l31 >> 4)) * 32 + (l31 & 15);
-#pragma unroll
-        for (int s = 0; s < Cfg::PSTEPS; ++s) {
-          // keys 16.. exist only up to N - 1 (and only in the hb = 0 half): the other slots carry p = 0 and may hold any finite v
-#pragma unroll
-          for (int e = 0; e < 8; ++e) {
-            const int key = 16 * s + (e & 3) + 8 * (e >> 2);  // + 4 hb
-            if (s == 0 || key < N) {
-              const _Float16* pr = pv + (size_t)min(key + 4 * hb, N - 1) * (RS / 2);
-              vh[blk][s][e] = pr[0];
-              vl[blk][s][e] = pr[16];
-            } else {
-              vh[blk][s][e] = vh[blk][s][0];
-              vl[blk][s][e] = vl[blk][s][0];
-            }
-          }
-        }
-      }
-      __builtin_amdgcn_sched_barrier(0);
-      // ---- S^T = K Q^T ----
-      f32x16 s_main, s_cross;
-#pragma unroll
-      for (int r = 0; r < 16; ++r) s_main[r] = s_cross[r] = 0.f;
-#pragma unroll
-      for (int ks = 0; ks < Cfg::KSTEPS; ++ks) {
-        s_main = __builtin_amdgcn_mfma_f32_32x32x16_f16(kh[ks], qh[h * Cfg::KSTEPS + ks], s_main, 0, 0, 0);
-        s_cross = __builtin_amdgcn_mfma_f32_32x32x16_f16(kh[ks], ql[h * Cfg::KSTEPS + ks], s_cross, 0, 0, 0);
-        s_cross = __builtin_amdgcn_mfma_f32_32x32x16_f16(kl[ks], qh[h * Cfg::KSTEPS + ks], s_cross, 0, 0, 0);
-      }
-      // ---- softmax over the keys of this lane's query: register r is key 4 hb + (r & 3) + 8 (r >> 2) ----
-      float p[16];
-      float mx = -INFINITY;
-#pragma unroll
-      for (int r = 0; r < 16; ++r) {
-        const int key = 4 * hb + (r & 3) + 8 * (r >> 2);
-        const float sv = fmaf(s_cross[r], two_m11, s_main[r]) * scale;
-        p[r] = (r < 8 || N > 16) ? (key < N ? sv : -INFINITY) : -INFINITY;  // (N <= 16: registers 8..15 are keys >= 16)
-        mx = fmaxf(mx, p[r]);
-      }
-      mx = fmaxf(mx, __shfl_xor(mx, 32));
-      float sum = 0.f;
-#pragma unroll
-      for (int r = 0; r < 16; ++r) {
-        p[r] = __builtin_amdgcn_exp2f(p[r] - mx);
-        sum += p[r];
-      }
-      sum += __shfl_xor(sum, 32);
-      const float inv = 1.0f / sum;
-      // ---- out^T = V^T P^T, one 32-channel block at a time; P split ONCE for the head (it was split again for every block) ----
-      f16x8 ph[Cfg::PSTEPS], pl[Cfg::PSTEPS];
-#pragma unroll
-      for (int s = 0; s < Cfg::PSTEPS; ++s)
-#pragma unroll
-        for (int e = 0; e < 8; ++e) {
-          const float pv32 = pinned(p[8 * s + e]);
-          ph[s][e] = (_Float16)pv32;
-          pl[s][e] = lo_plane(pv32, ph[s][e]);
-        }
-#pragma unroll
-      for (int blk = 0; blk < Cfg::DBLK; ++blk) {
-        f32x16 o_main, o_cross;
-#pragma unroll
-        for (int r = 0; r < 16; ++r) o_main[r] = o_cross[r] = 0.f;
-#pragma unroll
-        for (int s = 0; s < Cfg::PSTEPS; ++s) {
-          o_main = __builtin_amdgcn_mfma_f32_32x32x16_f16(vh[blk][s], ph[s], o_main, 0, 0, 0);
-          o_cross = __builtin_amdgcn_mfma_f32_32x32x16_f16(vh[blk][s], pl[s], o_cross, 0, 0, 0);
-          o_cross = __builtin_amdgcn_mfma_f32_32x32x16_f16(vl[blk][s], ph[s], o_cross, 0, 0, 0);
-        }
-        // register r is channel 32 blk + 4 hb + (r & 3) + 8 (r >> 2) of query l31: four consecutive channels per r >> 2, written
-        // pre-split into this head's bytes of the (dead) K row of that query
-        if (l31 < N) {
-          unsigned char* po = U + l31 * RS + hoff;
-#pragma unroll
-          for (int rq = 0; rq < 4; ++rq) {
-            f16x4 oh, ol;
-#pragma unroll
-            for (int e = 0; e < 4; ++e) {
-              const float v = pinned(fmaf(o_cross[4 * rq + e], two_m11, o_main[4 * rq + e]) * inv);
-              bad = bad || nonfinite(v);
-              oh[e] = (_Float16)v;
-              ol[e] = lo_plane(v, oh[e]);
-            }
-            const int g16 = 2 * blk + (rq >> 1), idx = 8 * (rq & 1) + 4 * hb;
-            *reinterpret_cast<f16x4*>(po + g16 * 64 + idx * 2) = oh;
-            *reinterpret_cast<f16x4*>(po + g16 * 64 + 32 + idx * 2) = ol;
-          }
-        }
-      }
-    }
+    for (int h = 0; h < HPW; ++h)  // (wave * HPW + h) * HD * 4: this head's bytes inside a row of the unit
+      attention_head<HD, N, RS, true>(U, (wave * HPW + h) * (HD * 4), rowc, l31, hb, qh + h * KSTEPS, ql + h * KSTEPS, bad);
     // ---- this wave's 256 B of every result row: LDS (written by other lanes of the wave) -> global, full segments ----
     __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
     __builtin_amdgcn_wave_barrier();
@@ -330,12 +356,12 @@ extern "C" int pmce_seq_attention_split_f16(const float* qkv, float* out, int ns
   return PMCE_OK;
 }
 
-// The temporal blocks' fused form (qkv product + this attention in one kernel) is part of this translation unit: it shares split8_fused
-// and spells the same softmax.
+// The temporal blocks' fused form (qkv product + this attention in one kernel) is part of this translation unit: it shares split8_fused;
+// its softmax is its own (two sequences per tile, V from the accumulators), not attention_head.
 #include "qkv_attention_fused.hip"
 
 // The same attention at the lifter's other head sizes (16 and 48 channels: chunks of 512 and 768 bytes), and the entry pair that serves
-// every width the model accepts: it shares split8_fused and spells the same softmax too.
+// every width the model accepts: its own staging around split8_fused and attention_head.
 #include "lifter_attention_mfma.hip"
 
 // The feature extractor's convolution (the same three-product split on the same matrix instruction) and its pools are compiled here as

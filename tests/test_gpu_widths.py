@@ -5,7 +5,8 @@ new shapes, and the whole path through the drop-in modules against the oracle - 
 The row kernels keep one lane layout at every width (lane l holds channels 256 i + 4 l + [0, 4)); at 128 and 384 the last 256-channel
 group is half filled and lanes 32..63 hold nothing of it: a wrong variance count, a sum over a stale register or a store past the row
 shows in every case below.  The matrix-pipe attention at these widths is a kernel of its own (csrc/lifter_attention_mfma.hip: units of
-512 / 768 bytes per row, part of a 32 x 32 output tile unused)."""
+512 / 768 bytes per row, part of a 32 x 32 output tile unused) around the head stage it shares with the 256 / 512 kernel; its battery is
+tests/test_gpu_seq_attention.py ("lmfma"), here it keeps its fixed 5e-6."""
 import numpy as np
 import pytest
 import torch
@@ -213,11 +214,10 @@ def test_seq_attention_of_one_token_returns_v(C):
 
 @pytest.mark.parametrize("C,J,B", [(128, 17, 2), (384, 17, 2), (128, 19, 1), (384, 19, 3), (384, 17, 37)])
 def test_lifter_attention_split_f16(C, J, B):
-    """The matrix-pipe attention at heads of 16 and 48 channels, by the recipe of test_gpu_ops.py::test_seq_attention_split_f16: inputs x 1.7
-    (peaked softmax), the reference is the fp64 attention of the values the (hi, lo) planes of q, k, v hold, the vector-pipe kernel's error on
-    the same values printed beside it.  Bound: max(5e-6, 4 x the vector-pipe kernel's error) - the first term alone is asserted on too, so a
-    head size at which it does not hold fails here rather than hiding behind the second.  Bitwise repeatable; every sequence equals the same
-    sequence computed alone (B = 37: 1,184 / 1,258 units on 1,024 workgroups, so some walk two)."""
+    """The matrix-pipe attention at heads of 16 and 48 channels on the inputs of test_gpu_ops.py::test_seq_attention_split_f16 (x 1.7: a peaked
+    softmax) against the fp64 attention of the values the (hi, lo) planes of q, k, v hold: within 5e-6, a fixed bound stated for these head
+    sizes.  The analytic bound, the exact cases, repeatability, a sequence alone against its rows in a launch and the persistent workgroups
+    are the "lmfma" instances of tests/test_gpu_seq_attention.py."""
     from pmce_amd import ops
     Tn = 16
     M = B * Tn * J
@@ -226,22 +226,11 @@ def test_lifter_attention_split_f16(C, J, B):
     assert (exact - qkv.double()).abs().max().item() < 1e-5
     for name, args in layouts(B, Tn, J, C):
         want = attention_fp64(exact, B, Tn, J, C, name[0])
-        got_p = ops.lifter_attention_split(qkv, *args)
-        got = ops.unsplit_rows_f16(got_p)
-        vec = ops.lifter_attention(exact.float(), *args)
-        e, ev = (got - want).abs().max().item(), (vec.double() - want).abs().max().item()
-        print(f"lifter_attention_split_f16 C={C} J={J} B={B} {name}: {e:.2e} (vector-pipe kernel {ev:.2e}), |out| max {want.abs().max().item():.2f}")
+        got = ops.unsplit_rows_f16(ops.lifter_attention_split(qkv, *args))
+        e = (got - want).abs().max().item()
+        print(f"lifter_attention_split_f16 C={C} J={J} B={B} {name}: {e:.2e}, |out| max {want.abs().max().item():.2f}")
         assert bool(torch.isfinite(got).all())
-        assert e < max(5e-6, 4 * ev)
-        assert e < 5e-6, "the fixed term of the bound alone"
-        again = ops.lifter_attention_split(qkv, *args)
-        assert torch.equal(bits(again), bits(got_p))
-        # batch invariance: the last clip alone (its own launch: other unit numbers, another grid) gives the same bits
-        b = B - 1
-        rows = slice(b * Tn * J, (b + 1) * Tn * J)
-        one_args = dict(layouts(1, Tn, J, C))[name]
-        alone = ops.lifter_attention_split(qkv[rows].contiguous(), *one_args)
-        assert torch.equal(bits(alone), bits(got_p[rows]))
+        assert e < 5e-6
 
 
 @pytest.mark.parametrize("C,J", [(256, 17), (512, 19), (512, 16)])
