@@ -348,6 +348,7 @@ int pmce_vertex_init_gather_f32(const float* joints, const int* vj, float* vt, i
  * pmce_ca_image_floats() floats - s0, two scales, Kf and Vf as (hi | lo) f16 fragment planes scaled by one power of two each.  Kf / s0 / Vf may
  * each be NULL when only the image is wanted. */
 int pmce_ca_image_floats(void);
+int pmce_ca_image_floats_written(int J); /* of a clip's row, the floats pmce_ca_fold_f32 writes at J joints (J <= 23) */
 int pmce_ca_fold_f32(const float* xk, const float* xv, const float* GB, int gb_stride, int iq, int ik, int iv,
                      const float* Wq, const float* bq, const float* Wk, const float* bk, const float* Wv, const float* bv,
                      const float* Wp, float* Kf, float* s0, float* Vf, float* img, int B, int J, pmce_stream_t stream);
@@ -415,7 +416,8 @@ int pmce_tokens_kv_f32(const float* xk, const float* xv, const float* vt, const 
 /* Joint stream of a CoevoBlock (CoevoDecoder.py:183,187,189): stage 1 = joint<-vertex cross-attention +
  * residual only, 2 = + FFN, 3 = + self-attention block + coordinate head.  wptr: 18 weight pointers
  * (wq,bq,proj_w,proj_b,fc1_w,fc1_b,fc2_w,fc2_b,qkv_w,qkv_b,sproj_w,sproj_b,sfc1_w,sfc1_b,sfc2_w,sfc2_b,coor_w,coor_b);
- * inst: AdaLN instance ids (normq, norm2, SA.norm1, SA.norm2). */
+ * inst: AdaLN instance ids (normq, norm2, SA.norm1, SA.norm2).  Stage 4 = the self-attention block alone (kv may be NULL).  y_out is
+ * required at stages 1 and 2 and optional beyond; pose_out (stages 3, 4) needs jt. */
 int pmce_joint_stream_f32(const float* xq, const float* jQ, const float* kv, const float* GB, int gb_stride,
                           const float* const* wptr, const int* inst, const float* jt, float* y_out, float* pose_out, int B,
                           int J, int stage, pmce_stream_t stream);

@@ -88,6 +88,7 @@ PROTOTYPES = {
     "pmce_div_scalar_f32": [_f, _f, _l, _fl, _s],
     "pmce_vertex_init_gather_f32": [_f, _f, _f, _i, _i, _s],
     "pmce_ca_image_floats": [],
+    "pmce_ca_image_floats_written": [_i],
     "pmce_ca_fold_f32": [_f, _f, _f, _i, _i, _i, _i, _f, _f, _f, _f, _f, _f, _f, _f, _f, _f, _f, _i, _i, _s],
     "pmce_joint_prep_f32": [_f, _f, _f, _f, _f, _f, _f, _f, _f, _i, _i, _i, _i, _f, _f, _f, _f, _f, _f, _f, _f, _f, _f, _f, _i, _i, _s],
     "pmce_vertex_ca_f32": [_f, _f, _f, _f, _f, _f, _f, _f, _f, _i, _i, _s],

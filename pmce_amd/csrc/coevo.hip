@@ -126,7 +126,14 @@ __device__ __forceinline__ void adaln_small8(const float* in, float* out, const 
     const float mean = wave_sum(x) * (1.0f / 64.0f);
     const float d = x - mean;
     const float var = wave_sum(d * d) * (1.0f / 63.0f);
-    out[i * JLD + lane] = gam * d / (sqrtf(var) + 1e-6f) + bet;
+    float sd = sqrtf(var);
+    if (var == INFINITY) {  // (wave-uniform) squared deviations beyond fp32: the std from scaled deviations, as slots_std_scaled (common.hpp)
+      int e = 0;
+      frexpf(wave_max(fabsf(d)), &e);
+      const float ds = ldexpf(d, -e);
+      sd = ldexpf(sqrtf(wave_sum(ds * ds) * (1.0f / 63.0f)), e);
+    }
+    out[i * JLD + lane] = gam * d / (sd + 1e-6f) + bet;
   }
 }
 
@@ -292,12 +299,15 @@ __global__ __launch_bounds__(JS_THREADS) void ca_fold_kernel(CaFoldArgs a) {
     MV = fmaxf(MV, s_red[8 + w]);
   }
   int ek = 0, ev = 0;
-  if (MK > 0.f) frexpf(MK, &ek);
-  if (MV > 0.f) frexpf(MV, &ev);
-  const float upK = MK > 0.f ? ldexpf(1.f, 15 - ek) : 1.f, upV = MV > 0.f ? ldexpf(1.f, 15 - ev) : 1.f;
+  // (an operand that overflowed fp32 has an infinite maximum, whose exponent frexpf leaves unspecified: it gets no scaling, its infinities
+  // reach the planes as they are and the clip comes out non-finite; fmaxf drops a NaN, which reaches its own planes likewise)
+  const bool sk = MK > 0.f && MK < INFINITY, sv = MV > 0.f && MV < INFINITY;
+  if (sk) frexpf(MK, &ek);
+  if (sv) frexpf(MV, &ev);
+  const float upK = sk ? ldexpf(1.f, 15 - ek) : 1.f, upV = sv ? ldexpf(1.f, 15 - ev) : 1.f;
   if (tid == 0) {  // what the kernel multiplies its accumulators by: the operand's 2^-s and the 2^-10 of its register-side operand
-    s_img[64] = (MK > 0.f ? ldexpf(1.f, ek - 15) : 1.f) * 0.0009765625f;
-    s_img[65] = (MV > 0.f ? ldexpf(1.f, ev - 15) : 1.f) * 0.0009765625f;
+    s_img[64] = (sk ? ldexpf(1.f, ek - 15) : 1.f) * 0.0009765625f;
+    s_img[65] = (sv ? ldexpf(1.f, ev - 15) : 1.f) * 0.0009765625f;
   }
   _Float16* im = reinterpret_cast<_Float16*>(s_img);
 #pragma unroll
@@ -389,7 +399,10 @@ __global__ __launch_bounds__(448, 4) void vertex_ca_kernel(const float* __restri
       const float d = x[i] - mean;
       ss += d * d;
     }
-    const float inv = 1.0f / (sqrtf(pair_sum(ss) * (1.0f / 63.0f)) + 1e-6f);
+    const float var = pair_sum(ss) * (1.0f / 63.0f);
+    float sd = sqrtf(var);
+    if (var == INFINITY) sd = slots_std_scaled(x, mean);  // squared deviations beyond fp32 (common.hpp)
+    const float inv = 1.0f / (sd + 1e-6f);
 #pragma unroll
     for (int i = 0; i < 32; ++i) n[i] = (x[i] - mean) * inv;
   }
@@ -555,7 +568,7 @@ __device__ __forceinline__ void ffn_slots(const float* sW1, const float* sW2, co
 #pragma unroll
     for (int nt = 0; nt < 2; ++nt)
 #pragma unroll
-      for (int r = 0; r < 16; ++r) acc2[nt][r] = sB2[nt * 32 + (r & 3) + 8 * (r >> 2) + 4 * hb] + x[16 * nt + r];
+      for (int r = 0; r < 16; ++r) acc2[nt][r] = sB2[nt * 32 + (r & 3) + 8 * (r >> 2) + 4 * hb];
 #pragma unroll 1
     for (int ht = 0; ht < 8; ++ht) {
       f32x16 acc1;
@@ -571,6 +584,12 @@ __device__ __forceinline__ void ffn_slots(const float* sW1, const float* sW2, co
       }
       tl_gemm<4, 2, LDW256>(sW2 + ht * 32, hreg, acc2, n0, hb);
     }
+    // The residual is added LAST, as in the f16 form below: seeded into acc2, each of fc2's 128 matrix instructions rounded at the
+    // residual's size (12 x the fp32 reference's own deviation from fp64 against the f16 form's 0.8 x; tests/test_gpu_decoder_ops.py).
+#pragma unroll
+    for (int nt = 0; nt < 2; ++nt)
+#pragma unroll
+      for (int r = 0; r < 16; ++r) acc2[nt][r] = acc2[nt][r] + x[16 * nt + r];
   } else {
     const float down1 = sSc[1], down2 = sSc[3];
     tl_f16x8 ahi[4], alo[4];
@@ -1266,14 +1285,16 @@ __global__ __launch_bounds__(448) void vertex_sa_kernel(const float* __restrict_
 #pragma unroll
   for (int nt = 0; nt < 2; ++nt)
 #pragma unroll
-    for (int r = 0; r < 16; ++r) acc[nt][r] = bp[nt * 32 + (r & 3) + 8 * (r >> 2) + 4 * hb] + x[16 * nt + r];
+    for (int r = 0; r < 16; ++r) acc[nt][r] = bp[nt * 32 + (r & 3) + 8 * (r >> 2) + 4 * hb];
   tl_gemm<8, 2, LDW64>(sWp, att, acc, n0, hb);
   if (valid) {
+    // The residual is added LAST, as vertex_ca does: seeded into the accumulator, each of the projection's 32 matrix instructions rounded
+    // at the residual's size (5 - 6 x the fp32 reference's own deviation from fp64; tests/test_gpu_decoder_ops.py).
     float y[32];
 #pragma unroll
     for (int nt = 0; nt < 2; ++nt)
 #pragma unroll
-      for (int r = 0; r < 16; ++r) y[16 * nt + r] = acc[nt][r];
+      for (int r = 0; r < 16; ++r) y[16 * nt + r] = x[16 * nt + r] + acc[nt][r];
     store_slots(yout + tok * 64, y, hb);
   }
 }
@@ -2055,6 +2076,7 @@ static int launch_ca_fold(const CaFoldArgs& a, int B, hipStream_t stream, const 
   return pmce_check_launch(what);
 }
 extern "C" int pmce_ca_image_floats(void) { return CA_IMG_STRIDE; }
+extern "C" int pmce_ca_image_floats_written(int J) { return CA_IMG_FLOATS(J); }  // what a clip's row holds at J joints; the rest is never written
 // img (may be null): the operands' f16 image per clip for pmce_vertex_ca_mlp_f32's split_f16 form, [B][pmce_ca_image_floats()], J <= 23.
 // Kf / s0 / Vf may each be null when only the image is wanted.
 extern "C" int pmce_ca_fold_f32(const float* xk, const float* xv, const float* GB, int gb_stride, int iq, int ik, int iv,
@@ -2099,7 +2121,9 @@ extern "C" int pmce_adaln_mlp_f32(const float* xin, const float* GB, int gb_stri
                                   const float* bc, const float* vt_in, float* vt_out, int B, int split_f16,
                                   const float* ffn_img, hipStream_t stream) {
   PMCE_REQUIRE(xin && GB && W1 && b1 && W2 && b2 && (yout || vt_out), "adaln_mlp: null pointer");
+  PMCE_REQUIRE(B > 0, "adaln_mlp: B must be positive");
   PMCE_REQUIRE(!vt_out || (Wc && bc && vt_in), "adaln_mlp: coordinate head needs Wc, bc, vt_in");
+  PMCE_REQUIRE(!ffn_img || (reinterpret_cast<uintptr_t>(ffn_img) & 15) == 0, "adaln_mlp: unaligned FFN image");
   const size_t lds = (size_t)(256 * LDW64 + 64 * LDW256 + 256 + 64 + 32 + 256) * sizeof(float);
   static std::atomic<unsigned long long> attr{0}, attr_s{0};
   if (split_f16) {
@@ -2124,6 +2148,7 @@ extern "C" int pmce_vertex_ca_mlp_f32(const float* xq, const float* vt, const fl
                                       const float* ca_img, hipStream_t stream) {
   PMCE_REQUIRE((xq || (vt && Wv3 && Eq)) && bp && GB && W1 && b1 && W2 && b2 && yout, "vertex_ca_mlp: null pointer");
   PMCE_REQUIRE(J >= 1 && J <= 32 && B > 0, "vertex_ca_mlp: J must be in 1..32");
+  PMCE_REQUIRE(!ffn_img || (reinterpret_cast<uintptr_t>(ffn_img) & 15) == 0, "vertex_ca_mlp: unaligned FFN image");
   if (J > 23) {  // one clip's folded operands no longer fit beside the FFN weights: the two-launch form
     PMCE_REQUIRE(scratch && Kf && s0 && Vf, "vertex_ca_mlp: J > 23 needs Kf / s0 / Vf and a [B,431,64] scratch buffer");
     PMCE_TRY(pmce_vertex_ca_f32(xq, vt, Wv3, Eq, Kf, s0, Vf, bp, scratch, B, J, stream));
@@ -2213,6 +2238,7 @@ extern "C" int pmce_tokens_kv_f32(const float* xk, const float* xv, const float*
                                   const float* tkv_img, hipStream_t stream) {
   PMCE_REQUIRE(((xk && xv) || (vt && Wv3 && Ev && Ek && (Wv2j || tkv_img))) && GB && bk && bv && kv && ((Wk && Wv) || tkv_img),
                "tokens_kv: null pointer");
+  PMCE_REQUIRE(B > 0, "tokens_kv: B must be positive");
   if (tkv_img) {
     PMCE_REQUIRE((reinterpret_cast<uintptr_t>(tkv_img) & 15) == 0, "tokens_kv: unaligned image");
     hipLaunchKernelGGL(tokens_kv_kernel<true>, dim3(tl_grid(B, 2)), dim3(256), 0, stream, xk, xv, vt, Wv3, Ev, Wv2j, Ek, GB, gb_stride, ik, iv,
@@ -2230,6 +2256,8 @@ extern "C" int pmce_joint_stream_f32(const float* xq, const float* jQ, const flo
   PMCE_REQUIRE(xq && (kv || stage == 4) && GB && wptr && inst, "joint_stream: null pointer");
   PMCE_REQUIRE(J >= 1 && J <= 32 && B > 0, "joint_stream: J must be in 1..32");
   PMCE_REQUIRE(stage >= 1 && stage <= 4, "joint_stream: stage must be 1 (CA), 2 (CA+FFN), 3 (full) or 4 (SA block only)");
+  PMCE_REQUIRE(y_out || (stage >= 3 && pose_out), "joint_stream: no output (stages 1 and 2 write y_out)");
+  PMCE_REQUIRE(!pose_out || (stage >= 3 && jt), "joint_stream: pose_out needs stage 3 or 4 and jt");
   JointStreamW w;
   w.wq = wptr[0]; w.bq = wptr[1]; w.proj_w = wptr[2]; w.proj_b = wptr[3];
   w.fc1_w = wptr[4]; w.fc1_b = wptr[5]; w.fc2_w = wptr[6]; w.fc2_b = wptr[7];
@@ -2243,7 +2271,7 @@ extern "C" int pmce_joint_stream_f32(const float* xq, const float* jQ, const flo
 }
 
 extern "C" int pmce_build_final_operand_f32(const float* g, const float* vt, float* A, int B, int KP, int packed, hipStream_t stream) {
-  PMCE_REQUIRE(g && vt && A && KP >= 2048 + NV * 3 && (!packed || KP % 16 == 0), "build_final_operand: bad args");
+  PMCE_REQUIRE(g && vt && A && B > 0 && KP >= 2048 + NV * 3 && (!packed || KP % 16 == 0), "build_final_operand: bad args");
   const long long n = (long long)B * KP;
   if (packed) hipLaunchKernelGGL(build_final_operand_kernel<true>, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, stream, g, vt, A, B, KP);
   else hipLaunchKernelGGL(build_final_operand_kernel<false>, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, stream, g, vt, A, B, KP);

@@ -249,6 +249,24 @@ __device__ __forceinline__ void store4_split_f16(float* __restrict__ row, int c,
   *reinterpret_cast<f16x4*>(p + 16) = lo;
 }
 
+// The unbiased std of a slot-layout token whose squared deviations overflow fp32 (a finite |x - mean| beyond 2^63, e.g. one channel at
+// 1e30): the plain sum gives var = inf and 1 / (inf + eps) = 0, which normalises the token to its beta - a finite, wrong AdaLN where the
+// reference's std (accumulated in double) is finite.  The same sum on the deviations scaled by a power of two (exact), scaled back.
+// Reached only when var == inf: NaN and infinite inputs give var = NaN and keep propagating as they did; no other token's bits change.
+__device__ __forceinline__ float slots_std_scaled(const float* x, float mean) {
+  float m = 0.f;
+#pragma unroll
+  for (int i = 0; i < 32; ++i) m = fmaxf(m, fabsf(x[i] - mean));
+  int e = 0;
+  frexpf(pair_max(m), &e);
+  float ss = 0.f;
+#pragma unroll
+  for (int i = 0; i < 32; ++i) {
+    const float d = ldexpf(x[i] - mean, -e);
+    ss += d * d;
+  }
+  return ldexpf(sqrtf(pair_sum(ss) * (1.0f / 63.0f)), e);
+}
 // The statistics of AdaLayerNorm on a slot-layout token (reference CoevoDecoder.py:23-29): the mean over the lane pair's 64 channels and
 // 1 / (unbiased std + eps), eps on the std.
 __device__ __forceinline__ void slots_mean_inv_std(const float* x, float& mean_, float& inv_) {
@@ -264,7 +282,9 @@ __device__ __forceinline__ void slots_mean_inv_std(const float* x, float& mean_,
   }
   const float var = pair_sum(ss) * (1.0f / 63.0f);
   mean_ = mean;
-  inv_ = 1.0f / (sqrtf(var) + 1e-6f);
+  float sd = sqrtf(var);
+  if (var == INFINITY) sd = slots_std_scaled(x, mean);  // (the same for both lanes of the pair)
+  inv_ = 1.0f / (sd + 1e-6f);
 }
 // AdaLayerNorm on a slot-layout token.  gb points at this clip's [gamma(64) | beta(64)] for the instance.
 __device__ __forceinline__ void adaln_slots(const float* x, float* y, const float* __restrict__ gb, int hb) {

@@ -350,26 +350,108 @@ def adaln_params(g, sd, names):
     return gemm_nt(g, _c(Wt), _c(bt))
 
 
-def cross_attn_vertex(xq, xk, xv, g, sd, p):
-    """Fused AdaLN + vertex<-joint cross-attention + residual: xq + CA(AdaLN_q(xq), AdaLN_k(xk), AdaLN_v(xv))
-    (first line of CrossAttentionBlock.forward, CoevoDecoder.py:83) with p = '...vertx_CA_FFN'."""
+# ---- the decoder's operators ---------------------------------------------------------------------------------------------------------------
+# Every wrapper below takes, next to its operands, what a test needs to place a launch inside memory of its own making (nothing here is on the
+# product path, which calls pmce_forward):
+#   out= (and vt_out=, pose_out=, qkv=)  the caller's result tensor, written in place and returned, as seq_attention's `out`;
+#   bufs=  a dict of the caller's scratch and intermediate buffers, each optional: "Kf" [B,64,64], "s0" [B,64], "Vf" [B,64,64], "img"
+#          [B, pmce_ca_image_floats()], "scratch" [B,431,64] (the J > 23 form), "kv" [B,431,128], "jf" [B,J,64], "sab" (vertex_sab's scratch);
+#   gb=    (GB, insts): a caller-made [B, W] view of the [gamma | beta] blocks - rows may be strided (gb_stride = the view's row stride), the
+#          last dimension contiguous - and the instance index of each AdaLN of the wrapper, in the order its docstring names them;
+#   coords= / embed=  the operands of the from-coordinates forms (the token features are then None).
+def _vp(t):
+    """Device pointer of a tensor that need not be contiguous (a strided GB view), or None."""
+    return None if t is None else C.c_void_p(t.data_ptr())
+
+
+def _gb_of(gb, g, sd, names):
+    """-> (GB view, gb_stride, instance indices) of a wrapper's AdaLN instances `names`: the dense GB of adaln_params, or the caller's."""
+    if gb is None:
+        GB = adaln_params(g, sd, names)
+        return GB, GB.shape[1], list(range(len(names)))
+    GB, insts = gb
+    if not (GB.is_cuda and GB.dtype == torch.float32 and GB.dim() == 2 and GB.stride(1) == 1) or len(insts) != len(names):
+        raise ValueError(f"gb must be (an fp32 device view [B, W] with a contiguous last dimension, {len(names)} instance indices)")
+    return GB, (GB.stride(0) if GB.shape[0] > 1 else GB.shape[1]), [int(i) for i in insts]
+
+
+def _buf(t, shape, like, what):
+    """A fresh fp32 buffer of `shape`, or the caller's (checked: a wrong size would let a kernel write past it)."""
+    if t is None:
+        return torch.empty(shape, device=like.device, dtype=torch.float32)
+    if t.dtype != torch.float32 or tuple(t.shape) != tuple(shape) or t.device != like.device or not t.is_contiguous():
+        raise ValueError(f"{what} must be a contiguous float32 {tuple(shape)} tensor on {like.device}, got {t.dtype} {tuple(t.shape)} on {t.device}")
+    return t
+
+
+def _ca_w(sd, p):
+    return {k: _c(sd[f"{p}.attn.{k}"]) for k in ("wq.weight", "wq.bias", "wk.weight", "wk.bias", "wv.weight", "wv.bias",
+                                                 "proj.weight", "proj.bias")}
+
+
+def ca_image_floats(J=None):
+    """Floats per clip of ca_fold's f16 image: the row stride (J = None), or what a clip's row holds at J joints (the rest of the row is
+    never written)."""
     lib = _lib.load()
-    xq, xk, xv = _c(xq), _c(xk), _c(xv)
-    B, Nq, _ = xq.shape
-    J = xk.shape[1]
-    assert Nq == 431
-    GB = adaln_params(g, sd, [p + ".normq", p + ".normk", p + ".normv"])
-    dev = xq.device
-    Kf = torch.empty(B, 64, 64, device=dev)
-    s0 = torch.empty(B, 64, device=dev)
-    Vf = torch.empty(B, 64, 64, device=dev)
-    w = {k: _c(sd[f"{p}.attn.{k}"]) for k in ("wq.weight", "wq.bias", "wk.weight", "wk.bias", "wv.weight", "wv.bias",
-                                              "proj.weight", "proj.bias")}
-    _lib.check(lib.pmce_ca_fold_f32(P(xk), P(xv), P(GB), GB.shape[1], 0, 1, 2, P(w["wq.weight"]), P(w["wq.bias"]),
-                                    P(w["wk.weight"]), P(w["wk.bias"]), P(w["wv.weight"]), P(w["wv.bias"]),
-                                    P(w["proj.weight"]), P(Kf), P(s0), P(Vf), None, B, J, _st()), "ca_fold")
-    out = torch.empty_like(xq)
-    _lib.check(lib.pmce_vertex_ca_f32(P(xq), None, None, None, P(Kf), P(s0), P(Vf), P(w["proj.bias"]), P(out), B, J, _st()),
+    return lib.pmce_ca_image_floats() if J is None else lib.pmce_ca_image_floats_written(int(J))
+
+
+def ca_fold(xk, xv, GB, gb_stride, insts, w, B, J, Kf=None, s0=None, Vf=None, img=None, embed=None, jf=None):
+    """pmce_ca_fold_f32 on its own, on the caller's buffers (each of Kf / s0 / Vf / img may be None = not wanted): the vertex<-joint
+    cross-attention's key / value side of a clip, folded.  insts = the instances of (normq, normk, normv) in GB; w = the attention's
+    weights (`_ca_w`).  embed = (jt [B,J,3], joint_proj.weight, .bias, joint_pos_embed [J,64], proj_j2v_dim.weight, .bias, j2v_K_embed
+    [J,64]) with xk = xv = None: pmce_joint_prep_f32 (jf [B,J,64] or None receives the joint features)."""
+    lib = _lib.load()
+    tail = (_vp(GB), gb_stride, insts[0], insts[1], insts[2], P(w["wq.weight"]), P(w["wq.bias"]), P(w["wk.weight"]), P(w["wk.bias"]),
+            P(w["wv.weight"]), P(w["wv.bias"]), P(w["proj.weight"]), P(Kf), P(s0), P(Vf), P(img), B, J, _st())
+    if embed is None:
+        _lib.check(lib.pmce_ca_fold_f32(P(xk), P(xv), *tail), "ca_fold")
+    else:
+        _lib.check(lib.pmce_joint_prep_f32(*[P(e) for e in embed], P(jf), *tail), "joint_prep")
+
+
+def _fold(xk, xv, g, sd, p, names, gb, bufs, B, J, embed, want_img, like):
+    """The fold of a composite wrapper: -> (GB, gb_stride, insts, w, Kf, s0, Vf, img)."""
+    bufs = bufs or {}
+    GB, gbs, insts = _gb_of(gb, g, sd, names)
+    w = _ca_w(sd, p)
+    Kf = _buf(bufs.get("Kf"), (B, 64, 64), like, "Kf")
+    s0 = _buf(bufs.get("s0"), (B, 64), like, "s0")
+    Vf = _buf(bufs.get("Vf"), (B, 64, 64), like, "Vf")
+    img = _buf(bufs.get("img"), (B, ca_image_floats()), like, "img") if want_img else None
+    jf = bufs.get("jf")
+    if embed is not None:
+        embed = [_c(e) for e in embed]
+        if jf is not None:
+            jf = _buf(jf, (B, J, 64), like, "jf")
+    ca_fold(xk, xv, GB, gbs, insts, w, B, J, Kf, s0, Vf, img, embed, jf)
+    return GB, gbs, insts, w, Kf, s0, Vf, img
+
+
+def _query_side(xq, coords):
+    """-> (xq or None, vt, Wv3, Eq, B, a tensor on the device): explicit query tokens, or coords = (vt [B,431,3], vertx_proj.weight [64,3],
+    Eq [431,64] = vertx_proj.bias + vertx_pos_embed + v_Q_embed)."""
+    if coords is None:
+        xq = _c(xq)
+        assert xq.shape[1] == 431
+        return xq, None, None, None, xq.shape[0], xq
+    vt, Wv3, Eq = (_c(t) for t in coords)
+    assert xq is None and vt.shape[1] == 431
+    return None, vt, Wv3, Eq, vt.shape[0], vt
+
+
+def cross_attn_vertex(xq, xk, xv, g, sd, p, out=None, gb=None, bufs=None, coords=None, embed=None):
+    """Fused AdaLN + vertex<-joint cross-attention + residual: xq + CA(AdaLN_q(xq), AdaLN_k(xk), AdaLN_v(xv))
+    (first line of CrossAttentionBlock.forward, CoevoDecoder.py:83) with p = '...vertx_CA_FFN'.  AdaLN order of gb: normq, normk, normv.
+    coords: the query tokens from the vertex coordinates (`_query_side`); embed: the key side from the joints (`ca_fold`)."""
+    lib = _lib.load()
+    xq, vt, Wv3, Eq, B, like = _query_side(xq, coords)
+    if embed is None:
+        xk, xv = _c(xk), _c(xv)
+    J = xk.shape[1] if embed is None else embed[0].shape[1]
+    _, _, _, w, Kf, s0, Vf, _ = _fold(xk, xv, g, sd, p, [p + ".normq", p + ".normk", p + ".normv"], gb, bufs, B, J, embed, False, like)
+    out = _buf(out, (B, 431, 64), like, "out")
+    _lib.check(lib.pmce_vertex_ca_f32(P(xq), P(vt), P(Wv3), P(Eq), P(Kf), P(s0), P(Vf), P(w["proj.bias"]), P(out), B, J, _st()),
                "vertex_ca")
     return out
 
@@ -384,59 +466,52 @@ def ffn_image(fc1_w, fc2_w):
     return img
 
 
-def cross_attn_block_vertex(xq, xk, xv, g, sd, p, split_f16=False, packed=False):
+def cross_attn_block_vertex(xq, xk, xv, g, sd, p, split_f16=False, packed=False, out=None, gb=None, bufs=None, coords=None, embed=None):
     """The whole vertex-stream CrossAttentionBlock in one launch (CoevoDecoder.py:82-87), p = '...vertx_CA_FFN':
     xq + CA(...) then + Mlp(AdaLN_2(.)).  fp32 form: bit-identical to cross_attn_vertex followed by adaln_mlp.  split_f16: the FFN and
     (round 5, J <= 23) the attention's two contractions in the three-product f16 form - the folded key / value operands reach the kernel as
     the f16 image ca_fold writes.  packed (with split_f16): the FFN's planes from a pre-made image (ffn_image) instead of converted per
-    workgroup."""
+    workgroup.  AdaLN order of gb: normq, normk, normv, norm2.  coords / embed: see cross_attn_vertex."""
     lib = _lib.load()
-    xq, xk, xv = _c(xq), _c(xk), _c(xv)
-    B, Nq, _ = xq.shape
-    J = xk.shape[1]
-    assert Nq == 431
-    GB = adaln_params(g, sd, [p + ".normq", p + ".normk", p + ".normv", p + ".norm2"])
-    dev = xq.device
-    Kf = torch.empty(B, 64, 64, device=dev)
-    s0 = torch.empty(B, 64, device=dev)
-    Vf = torch.empty(B, 64, 64, device=dev)
-    img = torch.empty(B, lib.pmce_ca_image_floats(), device=dev) if (split_f16 and J <= 23) else None
-    w = {k: _c(sd[f"{p}.attn.{k}"]) for k in ("wq.weight", "wq.bias", "wk.weight", "wk.bias", "wv.weight", "wv.bias",
-                                              "proj.weight", "proj.bias")}
-    _lib.check(lib.pmce_ca_fold_f32(P(xk), P(xv), P(GB), GB.shape[1], 0, 1, 2, P(w["wq.weight"]), P(w["wq.bias"]),
-                                    P(w["wk.weight"]), P(w["wk.bias"]), P(w["wv.weight"]), P(w["wv.bias"]),
-                                    P(w["proj.weight"]), P(Kf), P(s0), P(Vf), P(img), B, J, _st()), "ca_fold")
+    xq, vt, Wv3, Eq, B, like = _query_side(xq, coords)
+    if embed is None:
+        xk, xv = _c(xk), _c(xv)
+    J = xk.shape[1] if embed is None else embed[0].shape[1]
+    names = [p + ".normq", p + ".normk", p + ".normv", p + ".norm2"]
+    GB, gbs, insts, w, Kf, s0, Vf, img = _fold(xk, xv, g, sd, p, names, gb, bufs, B, J, embed, split_f16 and J <= 23, like)
     m = [_c(sd[p + k]) for k in (".mlp.fc1.weight", ".mlp.fc1.bias", ".mlp.fc2.weight", ".mlp.fc2.bias")]
-    out = torch.empty_like(xq)
-    scratch = torch.empty_like(xq) if J > 23 else None
+    out = _buf(out, (B, 431, 64), like, "out")
+    scratch = _buf((bufs or {}).get("scratch"), (B, 431, 64), like, "scratch") if J > 23 else None
     fimg = ffn_image(m[0], m[2]) if packed else None
-    _lib.check(lib.pmce_vertex_ca_mlp_f32(P(xq), None, None, None, P(Kf), P(s0), P(Vf), P(w["proj.bias"]), P(GB), GB.shape[1],
-                                          3, P(m[0]), P(m[1]), P(m[2]), P(m[3]), P(out), P(scratch), B, J,
+    _lib.check(lib.pmce_vertex_ca_mlp_f32(P(xq), P(vt), P(Wv3), P(Eq), P(Kf), P(s0), P(Vf), P(w["proj.bias"]), _vp(GB), gbs,
+                                          insts[3], P(m[0]), P(m[1]), P(m[2]), P(m[3]), P(out), P(scratch), B, J,
                                           1 if split_f16 else 0, P(fimg), P(img), _st()), "vertex_ca_mlp")
     return out
 
 
-def adaln_mlp(x, g, sd, p_norm, p_mlp, coor=None, vt_in=None, want_features=True, split_f16=False, packed=False):
+def adaln_mlp(x, g, sd, p_norm, p_mlp, coor=None, vt_in=None, want_features=True, split_f16=False, packed=False, out=None, vt_out=None,
+              gb=None):
     """x + Mlp(AdaLN(x)) on [B,431,64]; optional coordinate head (Wc[3,64], bc[3]) + vt_in residual.  packed: see cross_attn_block_vertex."""
     lib = _lib.load()
     x = _c(x)
     B = x.shape[0]
-    GB = adaln_params(g, sd, [p_norm])
+    GB, gbs, insts = _gb_of(gb, g, sd, [p_norm])
     w = [_c(sd[p_mlp + k]) for k in (".fc1.weight", ".fc1.bias", ".fc2.weight", ".fc2.bias")]
-    y = torch.empty_like(x) if want_features else None
-    vt_out = None
+    y = _buf(out, tuple(x.shape), x, "out") if want_features else None
     Wc = bc = None
+    if coor is None and vt_out is not None:
+        raise ValueError("adaln_mlp: vt_out needs the coordinate head (coor, vt_in)")
     if coor is not None:
         Wc, bc = _c(coor[0]), _c(coor[1])
         vt_in = _c(vt_in)
-        vt_out = torch.empty_like(vt_in)
+        vt_out = _buf(vt_out, tuple(vt_in.shape), x, "vt_out")
     img = ffn_image(w[0], w[2]) if packed else None
-    _lib.check(lib.pmce_adaln_mlp_f32(P(x), P(GB), GB.shape[1], 0, P(w[0]), P(w[1]), P(w[2]), P(w[3]), P(y), P(Wc), P(bc),
+    _lib.check(lib.pmce_adaln_mlp_f32(P(x), _vp(GB), gbs, insts[0], P(w[0]), P(w[1]), P(w[2]), P(w[3]), P(y), P(Wc), P(bc),
                                       P(vt_in), P(vt_out), B, 1 if split_f16 else 0, P(img), _st()), "adaln_mlp")
     return y, vt_out
 
 
-def vertex_self_attn(x, g, sd, p, split_f16=False):
+def vertex_self_attn(x, g, sd, p, split_f16=False, out=None, qkv=None, gb=None, bufs=None):
     """x + SA(AdaLN(x)) on [B,431,64], 2 heads (first line of Block.forward, CoevoDecoder.py:103); p = '...vertx_SA_FFN'.
     fp32 pipe: two launches (adaln_qkv, vertex_sa), returns (y, qkv).  split_f16: ONE launch (pmce_vertex_sab_split_f32: AdaLN + qkv
     product + attention + proj + residual, every contraction but the projection as three f16 matrix products; what a model in split_f16
@@ -444,42 +519,65 @@ def vertex_self_attn(x, g, sd, p, split_f16=False):
     lib = _lib.load()
     x = _c(x)
     B = x.shape[0]
-    GB = adaln_params(g, sd, [p + ".norm1"])
+    GB, gbs, insts = _gb_of(gb, g, sd, [p + ".norm1"])
     Wqkv = _c(sd[p + ".attn.qkv.weight"])
-    y = torch.empty_like(x)
+    y = _buf(out, tuple(x.shape), x, "out")
     if split_f16:
         img = torch.empty(lib.pmce_qkv_image_floats(), device=x.device)
         _lib.check(lib.pmce_qkv_pack_f16(P(Wqkv), P(img), _st()), "qkv_pack_f16")
-        scratch = torch.empty(lib.pmce_vertex_sab_scratch_floats(B), device=x.device)
-        _lib.check(lib.pmce_vertex_sab_split_f32(P(x), P(GB), GB.shape[1], 0, P(img), P(_c(sd[p + ".attn.qkv.bias"])),
+        scratch = _buf((bufs or {}).get("sab"), (lib.pmce_vertex_sab_scratch_floats(B),), x, "sab")
+        _lib.check(lib.pmce_vertex_sab_split_f32(P(x), _vp(GB), gbs, insts[0], P(img), P(_c(sd[p + ".attn.qkv.bias"])),
                                                  P(_c(sd[p + ".attn.proj.weight"])), P(_c(sd[p + ".attn.proj.bias"])), P(scratch), P(y), B,
                                                  _st()), "vertex_sab")
         return y, None
-    qkv = torch.empty(B, 431, 192, device=x.device)
-    _lib.check(lib.pmce_adaln_qkv_f32(P(x), P(GB), GB.shape[1], 0, P(Wqkv), P(_c(sd[p + ".attn.qkv.bias"])), P(qkv), B, _st()), "adaln_qkv")
+    qkv = _buf(qkv, (B, 431, 192), x, "qkv")
+    _lib.check(lib.pmce_adaln_qkv_f32(P(x), _vp(GB), gbs, insts[0], P(Wqkv), P(_c(sd[p + ".attn.qkv.bias"])), P(qkv), B, _st()), "adaln_qkv")
     _lib.check(lib.pmce_vertex_sa_f32(P(x), P(qkv), P(_c(sd[p + ".attn.proj.weight"])), P(_c(sd[p + ".attn.proj.bias"])), P(y), B, _st()),
                "vertex_sa")
     return y, qkv
 
 
-def joint_stream(xq, xk, xv, g, sd, blk, stage, jt=None, split_f16=False):
-    """Joint stream of a CoevoBlock given explicit q/k/v token sets (xq[B,J,64], xk/xv[B,431,64]):
-    stage 1 = xq + CA (CoevoDecoder.py:83), 2 = + FFN (:85-86), 3 = + joint_SA_FFN (:187) (+ coords if jt).
-    split_f16: the k / v products over the 431 vertex tokens (tokens_kv) in the three-product f16 form from the weights' image."""
+def tokens_kv(xk, xv, g, sd, ca, split_f16=False, kv=None, gb=None, coords=None):
+    """pmce_tokens_kv_f32 on its own: kv [B,431,128] = Wk AdaLN_k(xk) + bk | Wv AdaLN_v(xv) + bv of the joint<-vertex cross-attention
+    (ca = '...joint_CA_FFN').  AdaLN order of gb: normk, normv.  coords = (vt [B,431,3], vertx_proj.weight [64,3], Ev [431,64] =
+    vertx_proj.bias + vertx_pos_embed, proj_v2j_dim.weight [64,64], Ek [431,64] = proj_v2j_dim.bias + v2j_K_embed) with xk = xv = None:
+    xv = Wv3 vt + Ev, xk = Wv2j xv + Ek formed in the kernel.  split_f16: the 64 x 64 products in the three-product f16 form from the
+    weights' image, proj_v2j_dim.weight in its first slot when coords are given."""
     lib = _lib.load()
-    xq, xk, xv = _c(xq), _c(xk), _c(xv)
-    B, J, _ = xq.shape
-    ca, sa = blk + ".joint_CA_FFN", blk + ".joint_SA_FFN"
-    GB = adaln_params(g, sd, [ca + ".normq", ca + ".normk", ca + ".normv", ca + ".norm2", sa + ".norm1", sa + ".norm2"])
-    kv = torch.empty(B, 431, 128, device=xq.device)
+    vt = Wv3 = Ev = Wv2j = Ek = None
+    if coords is None:
+        xk, xv = _c(xk), _c(xv)
+        B, like = xk.shape[0], xk
+    else:
+        assert xk is None and xv is None
+        vt, Wv3, Ev, Wv2j, Ek = (_c(t) for t in coords)
+        B, like = vt.shape[0], vt
+    GB, gbs, insts = _gb_of(gb, g, sd, [ca + ".normk", ca + ".normv"])
+    kv = _buf(kv, (B, 431, 128), like, "kv")
     Wk, Wv = _c(sd[ca + ".attn.wk.weight"]), _c(sd[ca + ".attn.wv.weight"])
     img = None
     if split_f16:   # (the generic form does not use proj_v2j_dim: any 64 x 64 weight fills the image's first slot)
-        img = torch.empty(lib.pmce_tkv_image_floats(), device=xq.device)
-        _lib.check(lib.pmce_tkv_pack_f16(P(Wk), P(Wk), P(Wv), P(img), _st()), "tkv_pack_f16")
-    _lib.check(lib.pmce_tokens_kv_f32(P(xk), P(xv), None, None, None, None, None, P(GB), GB.shape[1], 1, 2,
+        img = torch.empty(lib.pmce_tkv_image_floats(), device=like.device)
+        _lib.check(lib.pmce_tkv_pack_f16(P(Wk if Wv2j is None else Wv2j), P(Wk), P(Wv), P(img), _st()), "tkv_pack_f16")
+    _lib.check(lib.pmce_tokens_kv_f32(P(xk), P(xv), P(vt), P(Wv3), P(Ev), P(Wv2j), P(Ek), _vp(GB), gbs, insts[0], insts[1],
                                       P(Wk), P(_c(sd[ca + ".attn.wk.bias"])), P(Wv), P(_c(sd[ca + ".attn.wv.bias"])), P(kv), B,
                                       P(img), _st()), "tokens_kv")
+    return kv
+
+
+def joint_stream(xq, xk, xv, g, sd, blk, stage, jt=None, split_f16=False, out=None, pose_out=None, gb=None, bufs=None, coords=None,
+                 jQ=None):
+    """Joint stream of a CoevoBlock given explicit q/k/v token sets (xq[B,J,64], xk/xv[B,431,64]):
+    stage 1 = xq + CA (CoevoDecoder.py:83), 2 = + FFN (:85-86), 3 = + joint_SA_FFN (:187) (+ coords if jt).
+    split_f16: the k / v products over the 431 vertex tokens (tokens_kv) in the three-product f16 form from the weights' image.
+    AdaLN order of gb: joint_CA_FFN's normq, normk, normv, norm2, joint_SA_FFN's norm1, norm2.  coords: see tokens_kv; jQ [J,64]: added
+    to xq in the kernel (j_Q_embed)."""
+    lib = _lib.load()
+    xq = _c(xq)
+    B, J, _ = xq.shape
+    ca, sa = blk + ".joint_CA_FFN", blk + ".joint_SA_FFN"
+    GB, gbs, insts = _gb_of(gb, g, sd, [ca + ".normq", ca + ".normk", ca + ".normv", ca + ".norm2", sa + ".norm1", sa + ".norm2"])
+    kv = tokens_kv(xk, xv, g, sd, ca, split_f16, (bufs or {}).get("kv"), (GB, insts[1:3]), coords)
     names = [ca + ".attn.wq.weight", ca + ".attn.wq.bias", ca + ".attn.proj.weight", ca + ".attn.proj.bias",
              ca + ".mlp.fc1.weight", ca + ".mlp.fc1.bias", ca + ".mlp.fc2.weight", ca + ".mlp.fc2.bias",
              sa + ".attn.qkv.weight", sa + ".attn.qkv.bias", sa + ".attn.proj.weight", sa + ".attn.proj.bias",
@@ -487,33 +585,33 @@ def joint_stream(xq, xk, xv, g, sd, blk, stage, jt=None, split_f16=False):
              blk + ".proj_joint_feat2coor.weight", blk + ".proj_joint_feat2coor.bias"]
     ws = [_c(sd[n]) for n in names]
     wptr = (C.c_void_p * 18)(*[w.data_ptr() for w in ws])
-    inst = (C.c_int * 4)(0, 3, 4, 5)
-    y = torch.empty_like(xq)
+    inst = (C.c_int * 4)(insts[0], insts[3], insts[4], insts[5])
+    y = _buf(out, (B, J, 64), xq, "out")
     pose = None
     if jt is not None:
         jt = _c(jt)
-        pose = torch.empty_like(jt)
-    _lib.check(lib.pmce_joint_stream_f32(P(xq), None, P(kv), P(GB), GB.shape[1], wptr, inst, P(jt), P(y), P(pose), B, J,
-                                         stage, _st()), "joint_stream")
+        pose = _buf(pose_out, (B, J, 3), xq, "pose_out")
+    _lib.check(lib.pmce_joint_stream_f32(P(xq), P(None if jQ is None else _c(jQ)), P(kv), _vp(GB), gbs, wptr, inst, P(jt), P(y), P(pose),
+                                         B, J, stage, _st()), "joint_stream")
     return y, pose, kv
 
 
-def joint_self_attn_block(x, g, sd, blk):
+def joint_self_attn_block(x, g, sd, blk, out=None, gb=None):
     """joint_SA_FFN alone: x + SA(AdaLN(x)); x + Mlp(AdaLN(x)) on [B,J,64], 8 heads (the reference's Block module,
-    CoevoDecoder.py:102-105) - joint_stream's stage 4."""
+    CoevoDecoder.py:102-105) - joint_stream's stage 4.  AdaLN order of gb: norm1, norm2."""
     lib = _lib.load()
     x = _c(x)
     B, J, _ = x.shape
     sa = blk + ".joint_SA_FFN"
-    GB = adaln_params(g, sd, [sa + ".norm1", sa + ".norm2"])
+    GB, gbs, insts = _gb_of(gb, g, sd, [sa + ".norm1", sa + ".norm2"])
     names = [sa + ".attn.qkv.weight"] * 8 + [sa + ".attn.qkv.weight", sa + ".attn.qkv.bias", sa + ".attn.proj.weight",
                                              sa + ".attn.proj.bias", sa + ".mlp.fc1.weight", sa + ".mlp.fc1.bias",
                                              sa + ".mlp.fc2.weight", sa + ".mlp.fc2.bias"] + [sa + ".attn.qkv.weight"] * 2
     ws = [_c(sd[n]) for n in names]            # slots 0-7 (cross-attention block) and 16-17 (coordinate head) are unused
     wptr = (C.c_void_p * 18)(*[w.data_ptr() for w in ws])
-    inst = (C.c_int * 4)(0, 0, 0, 1)
-    y = torch.empty_like(x)
-    _lib.check(lib.pmce_joint_stream_f32(P(x), None, None, P(GB), GB.shape[1], wptr, inst, None, P(y), None, B, J, 4, _st()),
+    inst = (C.c_int * 4)(insts[0], insts[0], insts[0], insts[1])
+    y = _buf(out, (B, J, 64), x, "out")
+    _lib.check(lib.pmce_joint_stream_f32(P(x), None, None, _vp(GB), gbs, wptr, inst, None, P(y), None, B, J, 4, _st()),
                "joint_stream(stage 4)")
     return y
 
