@@ -791,6 +791,46 @@ int pmce_vitpose_forward(const pmce_vitpose* v, const float* patches, long long 
                          float* heat, float* feat, void* workspace, size_t workspace_bytes, pmce_stream_t stream);
 
 /* ---------------------------------------------------------------------------------------------------------
+ * ViTPose's opt-in single-product f16 mode (csrc/gemm_f16.hip, csrc/vit_attention_f16.hip, csrc/layernorm_rows.hip): the four products
+ * and the attention of every block as ONE f16 matrix product with fp32 accumulation, the operands between them stored as single f16.
+ * r16(x) is round-to-nearest-even to f16 with every |x| < 2^-14 set to zero: every operand is rounded by it, none relies on f16
+ * sub-normals.  The default mode's entries above keep their bits.
+ *
+ * pmce_gemm_pack_f16: W[N][ldw] fp32 -> W16 = r16(W[n] * 2^s(n)) as f16 in the blocked layout [ceil(N/64)][K/32][64][32]
+ *   (pmce_gemm_packed_f16_halves(N, K) f16 of storage; rows past N are not written) and wscale[N] = 2^-s(n), the per-row power of two
+ *   that pmce_gemm_pack_split_f16 chooses (the row's max |w| lifted into [2^14, 2^15)).  K % 32 == 0, ldw >= K.
+ * pmce_gemm_nt_f16: C[M][N] = epi(A16[M][K] . W16[N][K]^T): A16 f16 [M][lda] (lda % 8 == 0), W16 / wscale from pmce_gemm_pack_f16,
+ *   bias fp32 [N] or NULL, act 0 or 1 (exact GELU), R an optional fp32 residual [M][ldc] that MAY BE C itself, C fp32 [M][ldc] or
+ *   (c_f16 = 1, no residual then) f16 [M][ldc] = r16 of the fp32 result.  K % 32 == 0, N % 32 == 0, any M >= 1; rows past M and columns
+ *   past N are never read past the tensors and never stored.  v_mfma_f32_32x32x16_f16 with fp32 accumulators, k ascending; the epilogue
+ *   (scale by 2^-s, bias, GELU, residual) in fp32.  A row of C has the same bits whatever M is and wherever the row sits.  A non-finite
+ *   result, or an f16 result beyond 65504, sets *overflow_word (NULL: the calling thread's overflow sink) to 1.  Buffers 16-byte
+ *   aligned; PMCE_ERR_ARG names the offending value.
+ * pmce_gemm_f16_set_tuning (a process-wide TUNING AID like pmce_gemm_split_set_tuning): tile 0 = 128x256, 1 = 128x128, 2 = 64x128,
+ *   anything else automatic; max_workgroups > 0 caps the persistent grid.  Results do not depend on either.
+ * pmce_layernorm_rows_f16: pmce_layernorm_rows_f32's arithmetic, the result stored as r16(y), f16 [rows][C].  It does not touch the
+ *   overflow word: a y beyond 65504 is stored as infinity and reported by the product that reads it.
+ * pmce_vit_attention_f16: pmce_vit_attention_split_f16's input, work split, bounds and shapes (pmce_vit_attention_supported answers
+ *   for both); q, k, v rounded by r16, s = q.k hd^-0.5 in one accumulator, p~ = exp(s - max), out = (r16(p~) . r16(v)) / sum(p~) with
+ *   the sum over the unrounded fp32 p~, stored as r16, f16 [n N][C].
+ * pmce_vitpose_create_precision: pmce_vitpose_create with `precision` 0 (split, what pmce_vitpose_create passes) or 1 (f16; anything
+ *   else PMCE_ERR_ARG naming the value).  The tensor table is the same in both.  In f16 mode the 4 x depth block weights are packed by
+ *   pmce_gemm_pack_f16 (2 bytes per weight instead of 4) and pmce_vitpose_forward runs the same seven launches per block through the
+ *   f16 entries; the patch embedding, the LayerNorm statistics, the fp32 residual stream, qkv's fp32 result, last_norm and the whole
+ *   head are the default mode's.  pmce_vitpose_workspace_bytes is the same bound in both.  pmce_vitpose_precision reads the mode back
+ *   (-1 for NULL). */
+long long pmce_gemm_packed_f16_halves(int N, int K);
+int pmce_gemm_pack_f16(const float* W, int N, int K, int ldw, void* W16, float* wscale, pmce_stream_t stream);
+int pmce_gemm_nt_f16(const void* A16, const void* W16, const float* wscale, const float* bias, const float* R, void* C, int M, int N, int K,
+                     long long lda, long long ldc, int act, int c_f16, unsigned* overflow_word, pmce_stream_t stream);
+int pmce_gemm_f16_set_tuning(int tile, int max_workgroups);
+int pmce_layernorm_rows_f16(const float* x, long long rows, int C, const float* add, int add_mod, float* out1, const float* w,
+                            const float* b, float eps, void* out16, pmce_stream_t stream);
+int pmce_vit_attention_f16(const float* qkv, void* out16, int n, int N, int C, int heads, pmce_stream_t stream);
+int pmce_vitpose_create_precision(int H, int W, int C, int depth, int heads, int F1, int F2, int K, int precision, pmce_vitpose** out);
+int pmce_vitpose_precision(const pmce_vitpose* v);
+
+/* ---------------------------------------------------------------------------------------------------------
  * The tracker's detector: YOLOv3 as the reference calls it (main/run_demo.py:199-215: MPT(detector_type='yolo', yolo_img_size=416)),
  * video frames -> box predictions (csrc/conv.hip, csrc/yolo.hip, csrc/yolo.cpp).  The structure is the published yolov3.cfg's and that of
  * the PyTorch-YOLOv3 lineage; no tensor was recorded from the yolov3 or multi_person_tracker packages.  Non-maximum suppression and SORT follow below

@@ -160,6 +160,14 @@ PROTOTYPES = {
     "pmce_vitpose_finalize_on": [C.c_void_p, _s],
     "pmce_vitpose_workspace_bytes": [C.c_void_p, _i],
     "pmce_vitpose_forward": [C.c_void_p, _f, _l, _l, _l, _l, _i, _f, _f, C.c_void_p, C.c_size_t, _s],
+    "pmce_gemm_packed_f16_halves": [_i, _i],
+    "pmce_gemm_pack_f16": [_f, _i, _i, _i, _f, _f, _s],
+    "pmce_gemm_nt_f16": [_f, _f, _f, _f, _f, _f, _i, _i, _i, _l, _l, _i, _i, _f, _s],
+    "pmce_gemm_f16_set_tuning": [_i, _i],
+    "pmce_layernorm_rows_f16": [_f, _l, _i, _f, _i, _f, _f, _f, _fl, _f, _s],
+    "pmce_vit_attention_f16": [_f, _f, _i, _i, _i, _i, _s],
+    "pmce_vitpose_create_precision": [_i, _i, _i, _i, _i, _i, _i, _i, _i, C.POINTER(C.c_void_p)],
+    "pmce_vitpose_precision": [C.c_void_p],
     "pmce_conv2d_act_split_f16": [_f, _l, _l, _l, _l, _i, _i, _i, _i, _f, _f, _f, _f, _l, _f, _l, _i, _i, _i, _i, _i, _i, _fl, _i, _s],
     "pmce_upsample2x_nhwc_f32": [_f, _l, _f, _l, _i, _i, _i, _i, _s],
     "pmce_yolo_decode_f32": [_f, _f, _f, C.POINTER(C.c_longlong), C.POINTER(C.c_int), C.POINTER(C.c_float), _i, _i, _i, _f, _s],
@@ -201,6 +209,7 @@ _RESTYPES = {
     "pmce_render_workspace_bytes": C.c_size_t,
     "pmce_smpl_workspace_bytes": C.c_size_t,
     "pmce_conv_packed_floats": C.c_longlong,
+    "pmce_gemm_packed_f16_halves": C.c_longlong,
     "pmce_extractor_destroy": None,
     "pmce_extractor_conv_name": C.c_char_p,
     "pmce_extractor_workspace_bytes": C.c_size_t,

@@ -234,6 +234,14 @@ __device__ __forceinline__ float pinned(float v) {
   asm volatile("" : "+v"(v));
   return v;
 }
+// The ONE rounding of the single-product f16 mode (gemm_f16.hip, vit_attention_f16.hip, layernorm_rows.hip): round to nearest even, and
+// every |x| < 2^-14 becomes zero by a select - no operand relies on what the matrix pipe does with f16 sub-normals.  Inf / NaN stay.
+// A COMPUTED x goes through pinned() first, as for the planes.
+__device__ __forceinline__ _Float16 r16(float x) {
+  const _Float16 h = (_Float16)x;
+  return fabsf(x) < 6.103515625e-05f ? (_Float16)0.0f : h;
+}
+
 // Four consecutive channels c..c+3 (c % 4 == 0) of a row, written in the pre-split operand layout of the three-product f16 GEMM
 // (gemm_split_f16.hip): per 16-wide k-tile 16 f16 "hi" then 16 f16 "lo * 2^11".  `row` is the row's start (the packed row takes
 // the bytes of the fp32 row).

@@ -1,7 +1,8 @@
 // nn.LayerNorm over rows of any width C with C % 16 == 0 and C <= 2048 (pmce_ln_chain_f32 serves the lifter's 256 and 512 only), with the
 // optional broadcast addend of a ViT's position embedding in front:
 //     y = x + add[row % add_mod]      (add == null: y = x);      out1 = y (optional: the new residual stream; may be x itself);
-//     out  = LN(y; w, b, eps)         fp32, or pre-split [row][C/16][16 hi | 16 lo*2^11] f16 - the A operand of a three-product f16 GEMM.
+//     out  = LN(y; w, b, eps)         fp32, or pre-split [row][C/16][16 hi | 16 lo*2^11] f16 - the A operand of a three-product f16 GEMM,
+//                                     or (pmce_layernorm_rows_f16) plain f16 [row][C], each value rounded once by r16 - gemm_f16.hip's.
 // One wave per row, the row in registers (up to eight 16-byte pieces per lane); two-pass fp32 statistics: the mean, then the mean of
 // the squared deviations (biased, as nn.LayerNorm), each summed in-lane in piece order and then across the wave - a row's result
 // depends on nothing but the row.
@@ -67,16 +68,20 @@ __global__ __launch_bounds__(256) void layernorm_rows_kernel(const float* x, lon
       f32x4 y;
 #pragma unroll
       for (int e = 0; e < 4; ++e) y[e] = (v[i][e] - mean) * inv * g[e] + be[e];
-      if (out_split) store4_split_f16(out + row * C, 4 * p, y);
+      if (out_split == 2) {  // plain f16 [rows][C], each value rounded once by r16: the A operand of gemm_f16.hip
+        f16x4 h;
+#pragma unroll
+        for (int e = 0; e < 4; ++e) h[e] = r16(pinned(y[e]));
+        *reinterpret_cast<f16x4*>(reinterpret_cast<_Float16*>(out) + row * C + 4 * p) = h;
+      } else if (out_split) store4_split_f16(out + row * C, 4 * p, y);
       else *reinterpret_cast<f32x4*>(out + row * C + 4 * p) = y;
     }
   }
 }
 
-}  // namespace
-
-extern "C" int pmce_layernorm_rows_f32(const float* x, long long rows, int C, const float* add, int add_mod, float* out1, const float* w,
-                                       const float* b, float eps, float* out, int out_split, hipStream_t stream) {
+// out_form: 0 fp32, 1 planes, 2 plain f16
+int layernorm_rows_any(const float* x, long long rows, int C, const float* add, int add_mod, float* out1, const float* w, const float* b, float eps,
+                       float* out, int out_split, hipStream_t stream) {
   PMCE_REQUIRE(x && w && b && out, "layernorm_rows: null pointer");
   PMCE_REQUIRE(C >= 16 && C % 16 == 0 && C <= 64 * 4 * LN_MAX_PIECES, "layernorm_rows: C must be a multiple of 16 in 16..2048 (got C=%d)", C);
   PMCE_REQUIRE(rows >= 1 && (rows + 3) / 4 < (1ll << 31), "layernorm_rows: rows must be in 1..2^33 (got %lld)", rows);
@@ -99,4 +104,17 @@ extern "C" int pmce_layernorm_rows_f32(const float* x, long long rows, int C, co
   PMCE_LN_CASE(8)
 #undef PMCE_LN_CASE
   return PMCE_OK;
+}
+
+}  // namespace
+
+extern "C" int pmce_layernorm_rows_f32(const float* x, long long rows, int C, const float* add, int add_mod, float* out1, const float* w,
+                                       const float* b, float eps, float* out, int out_split, hipStream_t stream) {
+  return layernorm_rows_any(x, rows, C, add, add_mod, out1, w, b, eps, out, out_split ? 1 : 0, stream);
+}
+
+// The same statistics and the same fp32 result, stored as r16(y) in plain f16 [rows][C] (the single-product f16 mode's operand).
+extern "C" int pmce_layernorm_rows_f16(const float* x, long long rows, int C, const float* add, int add_mod, float* out1, const float* w,
+                                       const float* b, float eps, void* out16, hipStream_t stream) {
+  return layernorm_rows_any(x, rows, C, add, add_mod, out1, w, b, eps, static_cast<float*>(out16), 2, stream);
 }

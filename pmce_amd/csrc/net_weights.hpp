@@ -10,7 +10,9 @@
 
 namespace pmce_net {
 
-enum Kind { PLAIN, LINEAR, CONV };  // PLAIN: copied as it is; LINEAR: [N][K] packed for the product; CONV: OIHW packed for the convolution
+// PLAIN: copied as it is; LINEAR: [N][K] packed for the three-product GEMM; CONV: OIHW packed for the convolution;
+// LINEAR_F16: [N][K] packed for pmce_gemm_nt_f16 (one f16 per weight - half of LINEAR's planes), wscale as for LINEAR
+enum Kind { PLAIN, LINEAR, CONV, LINEAR_F16 };
 
 struct Param {
   Kind kind = PLAIN;

@@ -20,6 +20,7 @@ namespace {
 using pmce_net::CONV;
 using pmce_net::Kind;
 using pmce_net::LINEAR;
+using pmce_net::LINEAR_F16;
 using pmce_net::PLAIN;
 
 struct Tensor : pmce_net::Param {
@@ -35,6 +36,7 @@ constexpr float LN_EPS = 1e-6f;
 struct pmce_vitpose {
   int H, W, C, depth, heads, F1, F2, K;
   int Hp, Wp, N;
+  int precision;  // 0: every product in the three-product split form; 1: the blocks' products and attention as ONE f16 product (gemm_f16.hip)
   std::vector<Tensor> t;
   pmce_net::Arena arena;
 
@@ -45,7 +47,14 @@ struct pmce_vitpose {
 };
 
 extern "C" int pmce_vitpose_create(int H, int W, int C, int depth, int heads, int F1, int F2, int K, pmce_vitpose** out) {
+  return pmce_vitpose_create_precision(H, W, C, depth, heads, F1, F2, K, 0, out);
+}
+
+extern "C" int pmce_vitpose_precision(const pmce_vitpose* v) { return v ? v->precision : -1; }
+
+extern "C" int pmce_vitpose_create_precision(int H, int W, int C, int depth, int heads, int F1, int F2, int K, int precision, pmce_vitpose** out) {
   PMCE_REQUIRE(out, "vitpose_create: null pointer");
+  PMCE_REQUIRE(precision == 0 || precision == 1, "vitpose_create: precision must be 0 (split_f16) or 1 (f16) (got %d)", precision);
   PMCE_REQUIRE(H >= PATCH && W >= PATCH && H % PATCH == 0 && W % PATCH == 0, "vitpose_create: the image (%d x %d) must be whole 16 x 16 patches", H, W);
   const int Hp = H / PATCH, Wp = W / PATCH, N = Hp * Wp;
   PMCE_REQUIRE(N <= 192, "vitpose_create: the image (%d x %d) has %d tokens, at most 192 are supported", H, W, N);
@@ -59,11 +68,13 @@ extern "C" int pmce_vitpose_create(int H, int W, int C, int depth, int heads, in
   pmce_vitpose* v = new pmce_vitpose();
   v->H = H; v->W = W; v->C = C; v->depth = depth; v->heads = heads; v->F1 = F1; v->F2 = F2; v->K = K;
   v->Hp = Hp; v->Wp = Wp; v->N = N;
+  v->precision = precision;
+  const Kind block_linear = precision == 1 ? LINEAR_F16 : LINEAR;
   auto add = [&](const std::string& name, Kind kind, int rank, int s0, int s1 = 0, int s2 = 0, int s3 = 0) {
     v->t.push_back({pmce_net::Param(kind, rank, s0, s1, s2, s3), name});
   };
   auto lin = [&](const std::string& p, int nout, int nin) {
-    add(p + ".weight", LINEAR, 2, nout, nin);
+    add(p + ".weight", block_linear, 2, nout, nin);
     add(p + ".bias", PLAIN, 1, nout);
   };
   auto norm = [&](const std::string& p) {
@@ -173,20 +184,41 @@ extern "C" int pmce_vitpose_forward(const pmce_vitpose* v, const float* patches,
   // the patch embedding reads the patches through the caller's strides; its NHWC result is the token matrix
   PMCE_TRY(pmce_conv2d_split_f16(patches, sn, sc, sy, sx, n, 3, v->H, v->W, tab[1].dev, tab[1].wscale, tab[2].dev, nullptr, X, C, PATCH, PATCH, PATCH,
                                  PATCH_PAD, 0, stream));
-  for (int i = 0; i < v->depth; ++i) {
-    const Tensor* b = tab + 3 + PER_BLOCK * i;
-    // block 0's norm1 also adds the position table and writes the sum back as the residual stream
-    if (i == 0) {
-      PMCE_TRY(ln(b + NORM1, tab[0].dev, X, XN, 1));
-    } else {
-      PMCE_TRY(ln(b + NORM1, nullptr, nullptr, XN, 1));
+  if (v->precision == 1) {
+    // The same seven launches per block through the f16 entries: XN, AO and HID hold plain f16 rows in (half of) their fp32-sized slots.
+    auto product16 = [&](const Tensor* w, const Tensor* b, const float* A16, const float* R, float* out, int act, int c_f16) {
+      return pmce_gemm_nt_f16(A16, w->dev, w->wscale, b->dev, R, out, M, w->shape[0], w->shape[1], w->shape[1], w->shape[0], act, c_f16, nullptr,
+                              stream);
+    };
+    auto ln16 = [&](const Tensor* wb, const float* add, float* out1) {
+      return pmce_layernorm_rows_f16(X, M, C, add, N, out1, wb[0].dev, wb[1].dev, LN_EPS, XN, stream);
+    };
+    for (int i = 0; i < v->depth; ++i) {
+      const Tensor* b = tab + 3 + PER_BLOCK * i;
+      PMCE_TRY(i == 0 ? ln16(b + NORM1, tab[0].dev, X) : ln16(b + NORM1, nullptr, nullptr));
+      PMCE_TRY(product16(b + QKV_W, b + QKV_B, XN, nullptr, QKV, 0, 0));
+      PMCE_TRY(pmce_vit_attention_f16(QKV, AO, n, N, C, v->heads, stream));
+      PMCE_TRY(product16(b + PROJ_W, b + PROJ_B, AO, X, X, 0, 0));
+      PMCE_TRY(ln16(b + NORM2, nullptr, nullptr));
+      PMCE_TRY(product16(b + FC1_W, b + FC1_B, XN, nullptr, HID, 1, 1));
+      PMCE_TRY(product16(b + FC2_W, b + FC2_B, HID, X, X, 0, 0));
     }
-    PMCE_TRY(product(b + QKV_W, b + QKV_B, XN, nullptr, QKV, M, 0, 0));
-    PMCE_TRY(pmce_vit_attention_split_f16(QKV, AO, n, N, C, v->heads, stream));
-    PMCE_TRY(product(b + PROJ_W, b + PROJ_B, AO, X, X, M, 0, 0));
-    PMCE_TRY(ln(b + NORM2, nullptr, nullptr, XN, 1));
-    PMCE_TRY(product(b + FC1_W, b + FC1_B, XN, nullptr, HID, M, 1, 1));
-    PMCE_TRY(product(b + FC2_W, b + FC2_B, HID, X, X, M, 0, 0));
+  } else {
+    for (int i = 0; i < v->depth; ++i) {
+      const Tensor* b = tab + 3 + PER_BLOCK * i;
+      // block 0's norm1 also adds the position table and writes the sum back as the residual stream
+      if (i == 0) {
+        PMCE_TRY(ln(b + NORM1, tab[0].dev, X, XN, 1));
+      } else {
+        PMCE_TRY(ln(b + NORM1, nullptr, nullptr, XN, 1));
+      }
+      PMCE_TRY(product(b + QKV_W, b + QKV_B, XN, nullptr, QKV, M, 0, 0));
+      PMCE_TRY(pmce_vit_attention_split_f16(QKV, AO, n, N, C, v->heads, stream));
+      PMCE_TRY(product(b + PROJ_W, b + PROJ_B, AO, X, X, M, 0, 0));
+      PMCE_TRY(ln(b + NORM2, nullptr, nullptr, XN, 1));
+      PMCE_TRY(product(b + FC1_W, b + FC1_B, XN, nullptr, HID, M, 1, 1));
+      PMCE_TRY(product(b + FC2_W, b + FC2_B, HID, X, X, M, 0, 0));
+    }
   }
   PMCE_TRY(ln(tail, nullptr, nullptr, XN, 1));
   if (feat) {  // the same rows once more, as fp32 NHWC [n][Hp][Wp][C]

@@ -12,6 +12,14 @@ them, and ``pose2d.TopDownPose(net)`` is the stage from tracker boxes to keypoin
 folded into each deconvolution on the host in fp64 (``fold_bn_deconv``), a deconvolution is one product and a gather
 (``deconv_weight_as_product``, ``deconv_gather``).  The operators are also bound one by one (``vit_attention``, ``layernorm_rows``,
 ``deconv_gather``).  There is no fallback: without the library's kernels a call raises.
+
+    net = ViTPose.from_state_dict(sd, device, precision="f16")              # opt-in: the blocks' products and attention as ONE f16 product
+
+``precision="split_f16"`` (the default) runs every product as three f16 products of an exact two-term split, at fp32 accuracy;
+``precision="f16"`` runs the four products and the attention of every block as one f16 product with fp32 accumulation, the operands
+between them stored as single f16 and the block weights in 2 bytes each (csrc/gemm_f16.hip, vit_attention_f16.hip).  The LayerNorm
+statistics, the fp32 residual stream, the patch embedding, last_norm and the whole head are the same in both.  The f16 mode's operators
+are bound one by one as well (``pack_f16``, ``gemm_f16``, ``layernorm_rows(out="f16")``, ``vit_attention(precision="f16")``).
 """
 from __future__ import annotations
 
@@ -31,6 +39,14 @@ IMG_SIZE = (256, 192)
 MAX_TOKENS = 192
 MAX_BATCH = 256
 PREFIXES = ("backbone.", "keypoint_head.")
+PRECISIONS = ("split_f16", "f16")       # the library's precision 0 and 1 (include/pmce_hip.h: pmce_vitpose_create_precision)
+
+
+def check_precision(precision):
+    """-> the library's number of a precision name; any other value raises a ValueError that lists the two choices."""
+    if precision not in PRECISIONS:
+        raise ValueError(f'precision must be "split_f16" or "f16" (got {precision!r})')
+    return PRECISIONS.index(precision)
 
 
 # ----------------------------------------------------------------------------------------------
@@ -178,9 +194,67 @@ def decode_planes(planes):
     return (h[..., 0, :] + h[..., 1, :] * 2.0 ** -11).reshape(*planes.shape[:-1], c)
 
 
-def vit_attention(qkv, n, n_tok, heads):
+def decode_f16(buf):
+    """An f16 tensor the f16 mode's operators wrote -> its fp64 values."""
+    if buf.dtype != torch.float16:
+        raise ValueError(f"decode_f16: an f16 tensor is expected (got {buf.dtype})")
+    return buf.double()
+
+
+class PackedF16:
+    """A weight [N, K] packed by ``pack_f16``: ``data`` f16 in the blocked layout [ceil(N/64)][K/32][64][32], ``wscale`` fp32 [N] = 2^-s."""
+
+    def __init__(self, data, wscale, n, k):
+        self.data, self.wscale, self.n, self.k = data, wscale, n, k
+
+    def decode(self):
+        """-> fp64 [N, K]: r16(w[n] 2^s(n)) 2^-s(n), the weight the product multiplies by."""
+        nb = (self.n + 63) // 64
+        w = self.data.reshape(nb, self.k // 32, 64, 32).permute(0, 2, 1, 3).reshape(nb * 64, self.k)[:self.n]
+        return w.double() * self.wscale.double()[:, None]
+
+
+def pack_f16(w):
+    """w fp32 [N, K] on the device, K % 32 == 0 -> ``PackedF16`` (pmce_gemm_pack_f16)."""
+    if w.dim() != 2 or w.dtype != torch.float32 or w.shape[1] % 32 or w.shape[1] < 32 or w.shape[0] < 1:
+        raise ValueError(f"pack_f16: w must be float32 [N, K] with K a positive multiple of 32 (got {w.dtype} {tuple(w.shape)})")
+    n, k = w.shape
+    lib = _lib.load()
+    data = torch.zeros(lib.pmce_gemm_packed_f16_halves(n, k), device=w.device, dtype=torch.float16)
+    wscale = torch.empty(n, device=w.device, dtype=torch.float32)
+    with torch.cuda.device(w.device):
+        _lib.check(lib.pmce_gemm_pack_f16(_lib.ptr(w), n, k, k, _lib.ptr(data), _lib.ptr(wscale), _lib.current_stream()), "gemm_pack_f16")
+    return PackedF16(data, wscale, n, k)
+
+
+def gemm_f16(a16, packed, bias=None, act=0, residual=None, out=None, out_f16=False, overflow=None):
+    """a16 f16 [M, K] (contiguous) times a ``PackedF16`` [N, K] -> act(a16 W16^T + bias) (+ residual), fp32 [M, N] or (``out_f16``) its
+    r16 as f16.  ``out`` may be the residual itself (in place).  ``overflow``: an int32 device word that a non-finite result sets."""
+    m, k = a16.shape
+    if a16.dim() != 2 or a16.dtype != torch.float16 or k != packed.k or not a16.is_contiguous():
+        raise ValueError(f"gemm_f16: a16 must be a contiguous float16 [M, {packed.k}] (got {a16.dtype} {tuple(a16.shape)}, strides {a16.stride()})")
+    want = torch.float16 if out_f16 else torch.float32
+    if out is None:
+        out = torch.empty(m, packed.n, device=a16.device, dtype=want)
+    if out.dtype != want or tuple(out.shape) != (m, packed.n) or not out.is_contiguous() or out.device != a16.device:
+        raise ValueError(f"gemm_f16: out must be a contiguous {want} [{m}, {packed.n}] on {a16.device} (got {out.dtype} {tuple(out.shape)} on {out.device})")
+    if bias is not None and (bias.dtype != torch.float32 or tuple(bias.shape) != (packed.n,) or bias.device != a16.device):
+        raise ValueError(f"gemm_f16: bias must be float32 [{packed.n}] on {a16.device} (got {bias.dtype} {tuple(bias.shape)} on {bias.device})")
+    if residual is not None and (out_f16 or residual.dtype != torch.float32 or tuple(residual.shape) != (m, packed.n) or not residual.is_contiguous()
+                                 or residual.device != a16.device):
+        raise ValueError(f"gemm_f16: residual must be a contiguous float32 [{m}, {packed.n}] on {a16.device}, and only with an fp32 result "
+                         f"(got {residual.dtype} {tuple(residual.shape)} on {residual.device}, out_f16={out_f16})")
+    with torch.cuda.device(a16.device):
+        _lib.check(_lib.load().pmce_gemm_nt_f16(_lib.ptr(a16), _lib.ptr(packed.data), _lib.ptr(packed.wscale), _lib.ptr(bias), _lib.ptr(residual),
+                                                _lib.ptr(out), m, packed.n, k, a16.stride(0), out.stride(0), act, 1 if out_f16 else 0,
+                                                _lib.ptr(overflow), _lib.current_stream()), "gemm_nt_f16")
+    return out
+
+
+def vit_attention(qkv, n, n_tok, heads, precision="split_f16"):
     """qkv fp32 [n * n_tok, 3C] (contiguous; may be a view into a larger buffer) -> the attention result as planes, fp32 storage
-    [n * n_tok, C] (``decode_planes`` reads it)."""
+    [n * n_tok, C] (``decode_planes`` reads it), or with ``precision="f16"`` as f16 [n * n_tok, C] (``decode_f16``)."""
+    f16 = check_precision(precision) == 1
     rows, c3 = qkv.shape
     c = c3 // 3
     if rows != n * n_tok or c3 != 3 * c or qkv.dtype != torch.float32:
@@ -188,21 +262,35 @@ def vit_attention(qkv, n, n_tok, heads):
     lib = _lib.load()
     if not lib.pmce_vit_attention_supported(n_tok, c, heads):
         raise ValueError(f"vit_attention: N must be in 1..{MAX_TOKENS} and C / heads 64 or 80 (got N={n_tok}, C={c}, heads={heads})")
-    out = torch.empty(rows, c, device=qkv.device, dtype=torch.float32)
-    if rows:
+    out = torch.empty(rows, c, device=qkv.device, dtype=torch.float16 if f16 else torch.float32)
+    if rows and f16:
+        with torch.cuda.device(qkv.device):
+            _lib.check(lib.pmce_vit_attention_f16(_lib.ptr(qkv), _lib.ptr(out), n, n_tok, c, heads, _lib.current_stream()), "vit_attention_f16")
+    elif rows:
         with torch.cuda.device(qkv.device):
             _lib.check(lib.pmce_vit_attention_split_f16(_lib.ptr(qkv), _lib.ptr(out), n, n_tok, c, heads, _lib.current_stream()), "vit_attention_split_f16")
     return out
 
 
-def layernorm_rows(x, weight, bias, eps=LN_EPS, add=None, return_sum=False, split=False):
-    """x fp32 [rows, C]; y = x + add[row % len(add)] (add [m, C] or None); -> LayerNorm(y) as fp32 or (``split``) planes[, y]."""
+def layernorm_rows(x, weight, bias, eps=LN_EPS, add=None, return_sum=False, split=False, out=None):
+    """x fp32 [rows, C]; y = x + add[row % len(add)] (add [m, C] or None); -> LayerNorm(y)[, y] in the form ``out``: "f32", "planes"
+    (fp32 storage) or "f16" (an f16 tensor, each value rounded once; the f16 mode's operand).  ``split=True`` is ``out="planes"``."""
+    if out is None:
+        out = "planes" if split else "f32"
+    if out not in ("f32", "planes", "f16"):
+        raise ValueError(f'layernorm_rows: out must be "f32", "planes" or "f16" (got {out!r})')
+    split = out == "planes"
     rows, c = x.shape
     if c % 16 or c > 2048 or x.dtype != torch.float32:
         raise ValueError(f"layernorm_rows: C must be a multiple of 16, at most 2048, of float32 (got {x.dtype} C={c})")
-    out = torch.empty_like(x)
+    form, out = out, torch.empty_like(x, dtype=torch.float16 if out == "f16" else torch.float32)
     y = torch.empty_like(x) if return_sum else None
-    if rows:
+    if rows and form == "f16":
+        with torch.cuda.device(x.device):
+            _lib.check(_lib.load().pmce_layernorm_rows_f16(_lib.ptr(x), rows, c, _lib.ptr(add), 0 if add is None else add.shape[0], _lib.ptr(y),
+                                                           _lib.ptr(weight), _lib.ptr(bias), eps, _lib.ptr(out), _lib.current_stream()),
+                       "layernorm_rows_f16")
+    elif rows:
         with torch.cuda.device(x.device):
             _lib.check(_lib.load().pmce_layernorm_rows_f32(_lib.ptr(x), rows, c, _lib.ptr(add), 0 if add is None else add.shape[0], _lib.ptr(y),
                                                            _lib.ptr(weight), _lib.ptr(bias), eps, _lib.ptr(out), 1 if split else 0,
@@ -247,19 +335,22 @@ def prepare_tensors(cfg, t):
 
 class ViTPose(DeviceNetwork):
     """ViTPose as HIP kernels.  ``max_batch``: patches per launch sequence (the workspace is allocated once for it and reused; 22.6 MB
-    per patch for ViTPose-H); ``check_finite``: raise when a heatmap is not finite, naming the first such patch."""
+    per patch for ViTPose-H); ``check_finite``: raise when a heatmap is not finite, naming the first such patch; ``precision``:
+    "split_f16" (the default: every product at fp32 accuracy) or "f16" (the blocks' products and attention as one f16 product each;
+    the module's docstring), read back as ``net.precision``."""
     NAME = "vitpose"
     MAX_BATCH = MAX_BATCH
 
-    def __init__(self, cfg, tensors, device, max_batch: int = 64, check_finite: bool = True):
+    def __init__(self, cfg, tensors, device, max_batch: int = 64, check_finite: bool = True, precision: str = "split_f16"):
+        mode = check_precision(precision)            # before any device work
         super().__init__(device, max_batch, check_finite)
         check_config(cfg)
         self.cfg = dict(cfg)
         self.Hp, self.Wp = cfg["H"] // PATCH, cfg["W"] // PATCH
         lib = _lib.load()
         h = C.c_void_p()
-        _lib.check(lib.pmce_vitpose_create(cfg["H"], cfg["W"], cfg["C"], cfg["depth"], cfg["heads"], cfg["F1"], cfg["F2"], cfg["K"], C.byref(h)),
-                   "vitpose_create")
+        _lib.check(lib.pmce_vitpose_create_precision(cfg["H"], cfg["W"], cfg["C"], cfg["depth"], cfg["heads"], cfg["F1"], cfg["F2"], cfg["K"], mode,
+                                                     C.byref(h)), "vitpose_create")
         self._h = h
         prepared = prepare_tensors(cfg, tensors)
 
@@ -276,14 +367,21 @@ class ViTPose(DeviceNetwork):
 
         self._finalize(uploads())
 
+    @property
+    def precision(self):
+        """The mode the handle runs in: "split_f16" or "f16"."""
+        return PRECISIONS[_lib.load().pmce_vitpose_precision(self._h)]
+
     @classmethod
     def from_state_dict(cls, sd, device="cuda", img_size=IMG_SIZE, num_heads=None, **kw):
+        check_precision(kw.get("precision", "split_f16"))
         cfg, t = select_state_dict(sd, img_size, num_heads)
         return cls(cfg, t, device, **kw)
 
     @classmethod
     def from_checkpoint(cls, path, device="cuda", **kw):
         """``torch.load(path)['state_dict']``, as mmpose writes its checkpoints."""
+        check_precision(kw.get("precision", "split_f16"))
         ckpt = torch.load(path, map_location="cpu", weights_only=False)
         if not hasattr(ckpt, "keys") or "state_dict" not in ckpt:
             raise ValueError(f"{path}: the checkpoint has no 'state_dict' entry")

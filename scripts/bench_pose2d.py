@@ -15,6 +15,7 @@ this file.  The GPU work runs in a child
 process under its own timeout.  Runs on an MI355X only.  Writes one JSON (default profiles/pose2d_bench.json).
 
     python scripts/bench_pose2d.py [--out profiles/pose2d_bench.json] [--persons 8] [--frames 300] [--reps 5] [--max-batch 64]
+                                   [--precision split_f16|f16]
 """
 import argparse
 import json
@@ -86,7 +87,7 @@ def step_run(args):
     from pmce_amd import pose2d, vitpose
     dev = torch.device("cuda:0")
     sd = BV.device_state_dict(BV.CFG, dev)
-    net = vitpose.ViTPose(BV.CFG, sd, dev, max_batch=args.max_batch, check_finite=False)
+    net = vitpose.ViTPose(BV.CFG, sd, dev, max_batch=args.max_batch, check_finite=False, precision=args.precision)
     del sd
     frames, fi, boxes = workload(args, dev)
     N = len(fi)
@@ -158,6 +159,7 @@ def main():
     ap.add_argument("--frames", type=int, default=300)
     ap.add_argument("--reps", type=int, default=5)
     ap.add_argument("--max-batch", type=int, default=64)
+    ap.add_argument("--precision", choices=["split_f16", "f16"], default="split_f16", help="the network's mode (vitpose.ViTPose(precision=))")
     ap.add_argument("--step", choices=["run"], help="(internal) run the GPU work in this process and print its JSON")
     args = ap.parse_args()
     if args.reps < 5:
@@ -166,7 +168,7 @@ def main():
         print("RESULT " + json.dumps(step_run(args)))
         return 0
     cmd = [sys.executable, os.path.abspath(__file__), "--step", "run", "--reps", str(args.reps), "--persons", str(args.persons),
-           "--frames", str(args.frames), "--max-batch", str(args.max_batch)]
+           "--frames", str(args.frames), "--max-batch", str(args.max_batch), "--precision", args.precision]
     try:
         r = subprocess.run(cmd, capture_output=True, text=True, timeout=LIMIT)
     except subprocess.TimeoutExpired:
@@ -178,7 +180,7 @@ def main():
         return 2
     from pmce_amd import _lib
     res = {"results": json.loads(line[-1][7:]), "build_id": _lib.build_id(), "persons": args.persons, "frames_per_person": args.frames,
-           "image": list(WH), "network": "ViTPose-H, drawn weights", "patch": [256, 192], "heatmap": [64, 48]}
+           "image": list(WH), "network": "ViTPose-H, drawn weights", "precision": args.precision, "patch": [256, 192], "heatmap": [64, 48]}
     r_ = res["results"]
     res["held_against"] = {"host_route_over_device_decode_time": round(r_["host_route"]["ms_median"] / r_["decode_flip"]["ms_median"], 1)}
     os.makedirs(os.path.dirname(args.out), exist_ok=True)

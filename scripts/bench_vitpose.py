@@ -12,7 +12,17 @@ skips it.  No ratio is fixed in advance: the measured ratio goes into the JSON w
 reads this file.  Every GPU step runs in a child process under its own timeout; the first step that fails ends the run (the baseline
 is last).  Runs on an MI355X only.  Writes one JSON (default profiles/vitpose_bench.json).
 
+``--precision f16`` or ``both`` adds an ``f16`` block: the network built with ``precision="f16"`` (pmce_amd/vitpose.py) on the same
+weights and patches - with ``both`` in the SAME process as a default-mode network, the two timed one after the other, median of
+``--reps`` passes each - its ms, patches / s, the ratio to the split mode of that run, the spread of the passes, the shader clock right
+after each loop, the per-class times and shares on one chunk through the f16 operators, and, as information, the heatmaps of the two
+modes compared through ``pose2d.decode_heatmaps``: the share of keypoints with the same maximum cell and the largest shift of a refined
+keypoint in patch pixels.  The weights are synthetic: that comparison says nothing about accuracy on real images.
+The output file is always written WHOLE, from the steps of this run alone (one library build): a run without ``--precision both`` writes
+no ``f16`` block, so the committed record is regenerated with ``--precision both``.
+
     python scripts/bench_vitpose.py [--out profiles/vitpose_bench.json] [--patches 2400] [--reps 5] [--max-batch 64] [--no-torch-baseline]
+                                    [--precision split_f16|f16|both]
 """
 import argparse
 import json
@@ -24,7 +34,7 @@ REPO = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, REPO)
 sys.path.insert(0, os.path.join(REPO, "tests"))
 
-STEPS = (("network", 420), ("classes", 300), ("torch", 600))           # (name, timeout in seconds)
+STEPS = (("network", 420), ("classes", 300), ("f16", 600), ("torch", 600))           # (name, timeout in seconds)
 CFG = dict(H=256, W=192, C=1280, depth=32, heads=16, F1=256, F2=256, K=17)
 MIN_SECONDS = 5.0
 
@@ -35,6 +45,32 @@ def macs_per_patch(cfg):
     hd = c // cfg["heads"]
     return {"patch_embed": n * c * 3 * 256, "products": d * n * 12 * c * c, "attention": d * cfg["heads"] * 2 * n * n * hd,
             "head": n * 16 * cfg["F1"] * c + 4 * n * 16 * cfg["F2"] * cfg["F1"] + 16 * n * cfg["K"] * cfg["F2"]}
+
+
+def clock_now():
+    """rocm-smi's sclk line(s): the shader clock right after a timed loop (a read; nothing is set)."""
+    try:
+        r = subprocess.run(["rocm-smi", "--showclocks"], capture_output=True, text=True, timeout=20).stdout
+        s = " ; ".join(" ".join(l.split()) for l in r.splitlines() if "sclk" in l)[:400]
+        return s or "rocm-smi --showclocks printed no sclk line"
+    except Exception as e:  # noqa: BLE001
+        return f"rocm-smi unavailable: {e}"
+
+
+def timed_passes(fn, reps):
+    """-> the ms of exactly ``reps`` passes after a warm-up pass."""
+    import torch
+    fn()
+    torch.cuda.synchronize()
+    ts = []
+    for _ in range(reps):
+        a, b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+        a.record()
+        fn()
+        b.record()
+        b.synchronize()
+        ts.append(a.elapsed_time(b))
+    return ts
 
 
 def timed(fn, reps, min_seconds=0.0):
@@ -161,6 +197,118 @@ def step_classes(args):
                         "operators_ms_per_launch": {k2: round(v, 4) for k2, v in res.items()}}}
 
 
+def classes_f16(args):
+    """The f16 mode's operators alone, on one chunk, with the forward's shapes: the four products, the attention, the LayerNorm."""
+    import torch
+    from pmce_amd import vitpose
+    dev = torch.device("cuda:0")
+    n, c, depth, heads = args.max_batch, CFG["C"], CFG["depth"], CFG["heads"]
+    ntok = 192
+    m = n * ntok
+    g = torch.Generator(device=dev)
+    g.manual_seed(9)
+
+    def rnd(*shape, scale=1.0):
+        return torch.randn(*shape, device=dev, generator=g) * scale
+
+    def t(fn):
+        return timed(fn, args.reps)[0]
+
+    def linear(nout, nin):
+        return vitpose.pack_f16(rnd(nout, nin, scale=nin ** -0.5)), rnd(nout, scale=0.1)
+
+    x = rnd(m, c)
+    x16 = x.half()
+    res = {}
+    wq, bq = linear(3 * c, c)
+    qkv = torch.empty(m, 3 * c, device=dev)
+    res["qkv"] = t(lambda: vitpose.gemm_f16(x16, wq, bq, out=qkv))
+    qkv[:, :2 * c] *= 2.0 ** 0.5
+    res["attention"] = t(lambda: vitpose.vit_attention(qkv, n, ntok, heads, precision="f16"))
+    wp, bp = linear(c, c)
+    out = torch.empty(m, c, device=dev)
+    res["proj"] = t(lambda: vitpose.gemm_f16(x16, wp, bp, residual=x, out=out))
+    w1, b1 = linear(4 * c, c)
+    hid = torch.empty(m, 4 * c, device=dev, dtype=torch.float16)
+    res["fc1"] = t(lambda: vitpose.gemm_f16(x16, w1, b1, act=1, out=hid, out_f16=True))
+    w2, b2 = linear(c, 4 * c)
+    res["fc2"] = t(lambda: vitpose.gemm_f16(hid, w2, b2, residual=x, out=out))
+    lw, lb = 1.0 + rnd(c, scale=0.1), rnd(c, scale=0.1)
+    res["layernorm"] = t(lambda: vitpose.layernorm_rows(x, lw, lb, out="f16"))
+    # what was tried for the tile: every product with each of the kernel's three tile shapes forced (the launches above chose automatically)
+    from pmce_amd import _lib
+    products = {"qkv": lambda: vitpose.gemm_f16(x16, wq, bq, out=qkv), "proj": lambda: vitpose.gemm_f16(x16, wp, bp, residual=x, out=out),
+                "fc1": lambda: vitpose.gemm_f16(x16, w1, b1, act=1, out=hid, out_f16=True),
+                "fc2": lambda: vitpose.gemm_f16(hid, w2, b2, residual=x, out=out)}
+    tiles = {}
+    try:
+        for tile, shape in enumerate(("128x256", "128x128", "64x128")):
+            _lib.load().pmce_gemm_f16_set_tuning(tile, 0)
+            tiles[shape] = {k: round(t(fn), 4) for k, fn in products.items()}
+    finally:
+        _lib.load().pmce_gemm_f16_set_tuning(-1, 0)
+    classes = {"products": depth * (res["qkv"] + res["proj"] + res["fc1"] + res["fc2"]), "attention": depth * res["attention"],
+               "layernorm": 2 * depth * res["layernorm"]}
+    total = sum(classes.values())
+    macs = macs_per_patch(CFG)
+    return {"batch": n, "what": "the blocks' launches only (patch embedding, last_norm and the head are the default mode's)",
+            "ms_per_batch": {k: round(v, 3) for k, v in classes.items()}, "sum_ms_per_batch": round(total, 3),
+            "share_of_the_blocks": {k: round(v / total, 4) for k, v in classes.items()},
+            "tflops_algorithmic": {k: round(2 * macs[k] * n / (classes[k] * 1e-3) / 1e12, 2) for k in ("products", "attention")},
+            "operators_ms_per_launch": {k: round(v, 4) for k, v in res.items()}, "products_ms_per_launch_by_forced_tile": tiles}
+
+
+def step_f16(args):
+    """The f16 mode (and with ``both`` the default mode, in this same process) on the same weights and patches."""
+    import numpy as np
+    import torch
+    from pmce_amd import pose2d, vitpose
+    dev = torch.device("cuda:0")
+    sd = device_state_dict(CFG, dev)
+    modes = ("split_f16", "f16") if args.precision == "both" else ("f16",)
+    nets = {m: vitpose.ViTPose(CFG, sd, dev, max_batch=args.max_batch, check_finite=False, precision=m) for m in modes}
+    del sd
+    x = make_patches(args.patches, dev)
+    out, heat = {}, {}
+    for m in modes:
+        assert nets[m].precision == m
+        heat[m] = nets[m](x)
+        assert heat[m].shape == (args.patches, 17, 64, 48) and bool(torch.isfinite(heat[m]).all()), f"a bench heatmap of mode {m} is not finite"
+        ts = timed_passes(lambda: nets[m](x), args.reps)
+        clock = clock_now()                                                           # right after the loop
+        med = float(np.median(ts))
+        out[m] = {"passes": len(ts), "ms_median": round(med, 3), "ms_min": round(min(ts), 3), "ms_max": round(max(ts), 3),
+                  "ms_per_patch": round(med / args.patches, 5), "patches_per_s": round(args.patches / (med * 1e-3), 1), "sclk_after": clock}
+    block = dict(out["f16"], patches=args.patches, max_batch=args.max_batch, heatmap_max=round(float(heat["f16"].abs().max()), 3))
+    if "split_f16" in out:
+        s, f = out["split_f16"], out["f16"]
+        block["split_f16_same_run"] = s
+        block["split_over_f16_time"] = round(s["ms_median"] / f["ms_median"], 3)
+        block["faster_by_more_than_the_spread"] = bool(f["ms_max"] < s["ms_min"])
+        cs = torch.tensor([[CFG["W"] / 2, CFG["H"] / 2, CFG["W"], CFG["H"]]], device=dev).repeat(args.patches, 1)      # keypoints in patch pixels
+        same, total, shifts = 0, 0, []
+        for k in range(0, args.patches, 256):
+            ka, _, aa = pose2d.decode_heatmaps(heat["split_f16"][k:k + 256], cs[k:k + 256], return_heatmap_coords=True)
+            kb, _, ab = pose2d.decode_heatmaps(heat["f16"][k:k + 256], cs[k:k + 256], return_heatmap_coords=True)
+            eq = (aa == ab).all(dim=-1)
+            same, total = same + int(eq.sum()), total + eq.numel()
+            shifts.append((ka[..., :2] - kb[..., :2]).norm(dim=-1)[eq])
+        shifts = torch.cat(shifts).double().cpu()
+        block["heatmaps_against_split_f16"] = {
+            "what": "information only: SYNTHETIC weights (there is no checkpoint where this ran), so this says nothing about accuracy on real "
+                    "images; both modes' heatmaps of the bench's patches through pose2d.decode_heatmaps",
+            "keypoints": total, "same_maximum_cell_share": round(same / total, 5),
+            "refined_shift_px_where_the_cell_agrees": {
+                "median": round(float(shifts.median()), 5), "p99": round(float(shifts.quantile(0.99)), 5), "largest": round(float(shifts.max()), 4),
+                "note": "on these noise-like heatmaps the sub-pixel Taylor step divides by a Hessian that can be close to singular: the "
+                        "largest shift is such a keypoint, where both modes' refinements are far outside the patch"},
+            "largest_heatmap_difference": round(float((heat["split_f16"] - heat["f16"]).abs().max()), 5)}
+    del nets, heat
+    torch.cuda.empty_cache()
+    block["classes"] = classes_f16(args)
+    return {"f16": block}
+
+
 def step_torch(args):
     import torch
     import vitpose_ref as VR
@@ -192,6 +340,8 @@ def main():
     ap.add_argument("--reps", type=int, default=5)
     ap.add_argument("--max-batch", type=int, default=64)
     ap.add_argument("--no-torch-baseline", action="store_true")
+    ap.add_argument("--precision", choices=["split_f16", "f16", "both"], default="split_f16",
+                    help="f16 / both: also measure the single-product f16 mode (both: against the default mode in the same process)")
     ap.add_argument("--step", choices=[s for s, _ in STEPS], help="(internal) run one GPU step in this process and print its JSON")
     args = ap.parse_args()
     if args.reps < 5:
@@ -203,8 +353,10 @@ def main():
     for name, limit in STEPS:
         if name == "torch" and args.no_torch_baseline:
             continue
+        if name == "f16" and args.precision == "split_f16":
+            continue
         cmd = [sys.executable, os.path.abspath(__file__), "--step", name, "--reps", str(args.reps), "--patches", str(args.patches),
-               "--max-batch", str(args.max_batch)]
+               "--max-batch", str(args.max_batch), "--precision", args.precision]
         try:
             r = subprocess.run(cmd, capture_output=True, text=True, timeout=limit)
         except subprocess.TimeoutExpired:
