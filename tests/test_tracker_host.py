@@ -206,6 +206,184 @@ def test_guard_scenes(seed):
     assert t[1, :2, 4].tolist() == [2.0, 1.0] and t[1, 0, 0] > t[1, 1, 0]    # tracker 1 took detection 0 (the right one), tracker 0 detection 1
 
 
+# ----------------------------------------------------------------------------------------------
+# guards of the inputs at the kernels' documented sizes (tests/test_gpu_tracker_crowd.py)
+# ----------------------------------------------------------------------------------------------
+
+def guarded_sort(p, c, **kw):
+    """The restatement in both precisions on a drawn input: every assignment unique at the run's threshold, every discrete result the
+    same in float64 and longdouble, the float tolerance not empty -> (tracks, counts, status, IoU matrices, live ids per frame)."""
+    ious, live = [], []
+    t, n, s = TR.sort_tracks(p, c, ious=ious, live=live, **kw)
+    tl, nl, sl = TR.sort_tracks(p, c, dtype=np.longdouble, **kw)
+    assert ious and all(TR.assignment_is_unique(m, kw.get("iou_threshold", 0.3)) for m in ious)
+    assert np.array_equal(n, nl) and np.array_equal(s, sl) and np.array_equal(t[..., 4], tl[..., 4].astype(np.float64))
+    assert float(np.abs(t[..., :4] - tl[..., :4]).max()) > 0
+    return t, n, s, ious, live
+
+
+def test_row_ordered_solver_agrees_with_scipy():
+    g = np.random.default_rng(TR.SEED + 1)
+    for _ in range(40):
+        nd, nt = g.integers(1, 7, 2)
+        m = g.uniform(0, 1, (nd, nt)) * (g.uniform(0, 1, (nd, nt)) > 0.3)
+        pairs, longest, used = TR.assign_paths(m)
+        assert abs(sum(m[d, t] for d, t in pairs) - sum(m[d, t] for d, t in TR.assign_scipy(m))) < 1e-12 and 1 <= longest <= used + 1
+    assert TR.assign_paths(np.array([[0.6, 0.5], [0.55, 0.0]])) == ([(0, 1), (1, 0)], 2, 1)
+
+
+@pytest.mark.parametrize("n,reverse,shuffle", TR.CHAIN_CASES + [(2, False, None), (2, True, None)],
+                         ids=lambda v: {None: "inorder", True: "rev", False: "fwd", TR.CHAIN_SHUFFLE: "shuffled"}.get(v, str(v)))
+def test_guard_chain_scenes(n, reverse, shuffle):
+    p, c = TR.chain_scene(n, reverse, shuffle)
+    t, cnt, s, ious, _ = guarded_sort(p, c)
+    order = np.array(TR.chain_order(n, reverse, shuffle))
+    m = ious[0]
+    assert m.shape == (n, n) and not s.any() and cnt.tolist() == [n] * 5
+    own, nxt = m[np.arange(n), order], m[np.arange(n), np.clip(order + (-1 if reverse else 1), 0, n - 1)]
+    assert np.abs(own - TR.CHAIN_A).max() < 1e-12 and np.abs(np.sort(nxt)[1:] - TR.CHAIN_B).max() < 1e-12 and TR.CHAIN_B > TR.CHAIN_A
+    assert n * TR.CHAIN_A - (n - 1) * TR.CHAIN_B > 0.08                               # the margin of the identity: 0.089 at n = 64
+    assert TR.assign_scipy(m) == sorted((d, int(b)) for d, b in enumerate(order))     # the optimum: every box on its own tracker
+    assert int((m.argmax(1) != order).sum()) == n - 1                                 # every row but one prefers another tracker
+    pairs, longest, used = TR.assign_paths(m)
+    assert pairs == TR.assign_scipy(m) and used == n - 1                              # some row's search goes through every column
+    if shuffle is None:
+        assert longest == n                                                           # in order: the last row re-routes all the others
+    else:
+        assert longest >= n // 2 and not np.array_equal(order, np.arange(n)) and not np.array_equal(order, np.arange(n)[::-1])
+    assert t[1, :n, 4].tolist() == list(range(n, 0, -1))                              # every id kept, reported in descending order
+
+
+@pytest.mark.parametrize("reverse", [False, True], ids=["fwd", "rev"])
+@pytest.mark.parametrize("shuffle", [None, TR.CHAIN_SHUFFLE], ids=["inorder", "shuffled"])
+def test_guard_chain_variants(reverse, shuffle):
+    n = 33
+    p, c = TR.chain_scene(n, reverse, shuffle, extra=True)                            # more detections than trackers: the extra box LOSES
+    t, cnt, s, ious, _ = guarded_sort(p, c)
+    order = TR.chain_order(n, reverse, shuffle, extra=True)
+    k, end = order.index(n), 0 if reverse else n - 1
+    assert ious[0].shape == (n + 1, n) and 0.3 < ious[0][k, end] < TR.CHAIN_A and np.count_nonzero(ious[0][k]) == 1
+    assert (k, end) not in TR.assign_scipy(ious[0]) and len(TR.assign_scipy(ious[0])) == n
+    assert t[1, :n + 1, 4].tolist() == list(range(n + 1, 0, -1)) and cnt[1] == n + 1 and not s.any()
+    p, c = TR.chain_scene(n, reverse, shuffle, drop=16)                               # fewer: the chain is cut in two
+    t, cnt, s, ious, _ = guarded_sort(p, c)
+    order = np.array(TR.chain_order(n, reverse, shuffle, drop=16))
+    moved = order > 16 if reverse else order < 16                                     # before the gap: on to the neighbour's tracker
+    want = sorted((d, int(b) + int(moved[d]) * (-1 if reverse else 1)) for d, b in enumerate(order))
+    assert ious[0].shape == (n - 1, n) and TR.assign_scipy(ious[0]) == want and int(moved.sum()) == 16
+    assert sorted(t[1, :n - 1, 4].tolist()) == [i + 1 for i in range(n) if i != (n - 1 if reverse else 0)]
+    assert TR.assign_paths(ious[0])[1] >= (16 if shuffle is None else 4)
+
+
+def test_guard_chain_holes():
+    p, c = TR.chain_holes()
+    t, cnt, s, ious, live = guarded_sort(p, c, **TR.HOLES_KW)
+    dead, n = TR.HOLES_DEAD, TR.HOLES_N
+    assert live[1][1] == [i for i in range(n) if i not in dead] and live[2][1] == live[1][1] + [n, n + 1, n + 2]
+    m = ious[1]                                                                       # frame 2: 38 detections, 35 trackers in 40 slots
+    assert m.shape == (n - len(dead) + TR.HOLES_NEW, n - len(dead)) and cnt.tolist() == [40, 35, 35, 38, 38] and not s.any()
+    pairs = [(d, k) for d, k in TR.assign_scipy(m) if m[d, k] >= 0.3]
+    assert len(pairs) == 35 and all(abs(m[d, k] - TR.CHAIN_A) < 1e-9 for d, k in pairs)
+    assert int((m.argmax(1)[[d for d, _ in pairs]] != [k for _, k in pairs]).sum()) == 35 - 5       # five chains of 7: 6 rows each prefer another
+    mixed, below, seen = TR.replay_slots(live, {f: t[f, :cnt[f], 4].astype(int).tolist() for f in range(5)})
+    assert below == TR.HOLES_NEW and mixed == 2 and seen == 5                         # born into slots 7, 15, 23; reported out of slot order
+
+
+@pytest.mark.parametrize("seed", TR.CROWD_SEEDS)
+def test_guard_crowds(seed):
+    p, c = TR.draw_crowd(seed)
+    assert int(c.max()) >= 36
+    for kw in TR.CROWD_PARAMS:
+        t, cnt, s, ious, live = guarded_sort(p, c, **kw)
+        assert len(ious) == 23 and max(m.shape[0] for m in ious) >= 36 and max(m.shape[1] for m in ious) >= 36 and not s.any()
+        assert any(m.shape[0] > m.shape[1] for m in ious) and any(m.shape[0] < m.shape[1] for m in ious)
+        mixed, below, seen = TR.replay_slots(live, {f: t[f, :cnt[f], 4].astype(int).tolist() for f in range(24)})
+        if kw in (dict(), dict(max_age=0, min_hits=0)):
+            assert seen == 24 and mixed >= 6                                          # slot order is not id order in a quarter of the frames
+        if kw == dict(max_age=0, min_hits=0):
+            assert below >= 10 and t[..., 4].max() >= 70                              # births below live trackers; ids far beyond 40 persons
+    q, d = TR.draw_crowd(TR.CROWD_SEEDS[1], frames=16)                                # the shorter crowd of the launch with three sequences
+    guarded_sort(q, d)
+    assert all(c[f] > 0 for f in TR.CROWD_EMPTY)
+    p, c = TR.draw_crowd(seed, empty=TR.CROWD_EMPTY)
+    t1, n1, _, _, _ = guarded_sort(p, c, update_on_empty=1)
+    t0, n0, _, _, _ = guarded_sort(p, c)
+    assert not c[list(TR.CROWD_EMPTY)].any() and not np.array_equal(t1[..., 4], t0[..., 4])        # seeing the empty frames changes ids
+
+
+def test_guard_wide_crowd():
+    seed, persons, frames = TR.WIDE_CROWD
+    p, c = TR.draw_crowd(seed, frames=frames, persons=persons)
+    for kw in TR.WIDE_PARAMS:
+        t, cnt, s, ious, live = guarded_sort(p, c, **kw)
+        assert max(m.shape[0] for m in ious) >= 56 and max(m.shape[1] for m in ious) >= 56 and not s.any()
+        if kw["max_age"] == 3:
+            assert max(len(ids) for _, ids in live) == 64                             # every slot holds a tracker, none is refused
+        else:
+            assert t[..., 4].max() >= 90 and TR.replay_slots(live, {f: t[f, :cnt[f], 4].astype(int).tolist() for f in range(frames)})[1] >= 10
+
+
+def test_guard_full_house_and_clamps():
+    p, c = TR.full_house()
+    t, cnt, s, ious, live = guarded_sort(p, c, min_hits=0)
+    assert [m.shape for m in ious] == [(64, 64)] * 3 and not ious[0].any() and not ious[1].any()   # 64 detections, none overlaps a tracker
+    assert int((ious[2] >= 0.3).sum()) == 64                                          # frame 4: the new 64, each met again
+    # the list is full while the first 64 coast (two frames at max_age = 1: sort.py founds before it buries), then 64 new ids
+    assert s.tolist() == [0, 1, 1, 0, 0] and cnt.tolist() == [64, 0, 0, 64, 64]
+    assert t[0, :, 4].tolist() == list(range(64, 0, -1)) and t[3, :, 4].tolist() == list(range(128, 64, -1)) == t[4, :, 4].tolist()
+    t, cnt, s, ious, live = guarded_sort(p, c, min_hits=0, max_tracks=63)
+    assert s.tolist() == [1] * 5 and cnt.tolist() == [63, 0, 0, 63, 63] and t[3, :, 4].tolist() == list(range(126, 63, -1))
+    assert all(m.shape == (64, 63) for m in ious)
+    p, c = TR.shrink_scene()
+    t, cnt, s, ious, _ = guarded_sort(p, c, **TR.SHRINK_KW)
+    for dt in (np.float64, np.longdouble):                                            # which path: the area's velocity is set to zero, once,
+        trk, fired = TR.Sort(dtype=dt, **TR.SHRINK_KW), []                            # while the tracker coasts; no box is ever NaN
+        for f in range(len(c)):
+            fired += [(f, k.id, k.time_since_update) for k in trk.trackers if k.x[6] + k.x[2] <= 0]
+            before = len(trk.trackers)
+            trk.update(p[f, :c[f]])
+            assert len(trk.trackers) >= before - 1 and all(np.isfinite(k.box().astype(np.float64)).all() for k in trk.trackers)
+        assert fired == [(4, 1, 1)]
+    assert [t[f, :cnt[f], 4].tolist() for f in (2, 4, 5)] == [[2.0, 1.0], [1.0], [2.0, 1.0]]       # ... and the tracker it saved is met again
+
+
+def test_guard_nms_limits():
+    rows = TR.draw_full_rows()
+    assert TR.nms_margin(rows) > MARGIN and int((rows[..., 4] >= 0.5).sum()) == 2048 == rows.shape[1]
+    tr = {}
+    TR.nms_image(rows[0], dtype=torch.float64, trace=tr)
+    last = [h for h in tr["heads"] if h >= 1984]
+    assert len(tr["heads"]) == 9 and len(last) == 1 and last[0] % 64 > 0             # a head in chunk 31, not on its first lane ...
+    d, c, s, src = TR.nms(rows, max_candidates=2048, dtype=torch.float64)
+    d32 = TR.nms(rows, max_candidates=2048)[0]
+    merged = torch.tensor([330.0 - 30, 330.0 - 40, 330.0 + 30, 330.0 + 40], dtype=torch.float64)
+    assert c.tolist() == [9] and s.tolist() == [0] and torch.equal(d[0, 8, :4], merged)            # ... that merged rows of that chunk
+    assert int((rows[0, :, 0] == 330.0).sum()) >= 2 and float((d32.double() - d)[..., :4].abs().max()) > 0
+    more = torch.cat([rows, rows[:, :1]], 1)
+    assert TR.nms(more, max_candidates=2048)[2].tolist() == [1] and more.shape[1] == 2049
+    caps = TR.draw_caps_rows(TR.CAPS_SEED)[:1]
+    assert int((caps[..., 4] >= 0.5).sum()) == 20
+    assert TR.nms(caps, max_candidates=20)[2].tolist() == [0] and TR.nms(caps, max_candidates=19)[2].tolist() == [1]
+    rows = TR.draw_keep_rows()
+    d, c, s, src = TR.nms(rows, dtype=torch.float64)
+    d32, c32, _, _ = TR.nms(rows)
+    assert TR.nms_margin(rows) > MARGIN and c.tolist() == [64] and s.tolist() == [0] and int((rows[..., 4] >= 0.5).sum()) > 100
+    assert float((d32.double() - d)[..., :4].abs().max()) > 0
+    ppl, pc = TR.people(d32, c32, (0, 420, 1920 / 416))
+    assert 8 <= int(pc[0]) < 64 and ppl[0, pc[0] - 1, 4] == float(d32[0, 63, 4]) and d32[0, 63, 6] == 0     # the 64th kept row is a person
+    rows = TR.draw_keep_rows(extra=True)
+    d, c, s, src = TR.nms(rows, dtype=torch.float64)
+    assert TR.nms_margin(rows) > MARGIN and c.tolist() == [0] and s.tolist() == [2] and not d.any()
+    assert TR.nms(rows, max_keep=65, dtype=torch.float64)[1].tolist() == [65]
+    rows = TR.draw_seam_rows()
+    d, c, s, src = TR.nms(rows, dtype=torch.float64)
+    cand = (rows[0, :, 4] >= 0.5)
+    assert rows.shape[1] == 1025 and all(bool(cand[r]) for r in TR.SEAM_ROWS) and int(cand.sum()) >= 100
+    assert TR.nms_margin(rows) > MARGIN and not s.any() and 0 < int(c[0]) < int(cand.sum())
+    assert float((TR.nms(rows)[0].double() - d)[..., :4].abs().max()) > 0
+    assert set(TR.SEAM_ROWS) & set(src[0].tolist())                                   # a seam row is itself a kept head
+
+
 @pytest.fixture(scope="module")
 def lib():
     from pmce_amd import _lib, build

@@ -39,14 +39,15 @@ def nms_image(x, conf_thres=0.5, nms_thres=0.4, dtype=torch.float32, trace=None)
     Candidates ``conf >= conf_thres``; score = conf * max class; sorted by score descending, ties by the lower row (the project's rule);
     a head takes every remaining candidate of its class with IoU > nms_thres, the kept box is their conf-weighted mean summed in
     sorted order; the head itself always leaves (the lineage loops forever on a head whose self-IoU is not > nms_thres).
-    ``trace``: a dict that receives 'ious' (the same-class IoUs examined) and 'scores' (the sorted keys)."""
+    ``trace``: a dict that receives 'ious' (the same-class IoUs examined), 'scores' (the sorted keys) and 'heads' (the heads' sorted
+    positions)."""
     x = x.to(dtype)
     thr_c, thr_n = torch.tensor(conf_thres, dtype=dtype), torch.tensor(nms_thres, dtype=dtype)
     idx = torch.nonzero(x[:, 4] >= thr_c)[:, 0]
     c = x[idx]
     if c.shape[0] == 0:
         if trace is not None:
-            trace.update(ious=np.zeros(0), scores=np.zeros(0))
+            trace.update(ious=np.zeros(0), scores=np.zeros(0), heads=[])
         return torch.zeros(0, 7, dtype=dtype), torch.zeros(0, dtype=torch.int64)
     cls_conf = c[:, 5:].max(1).values
     cls = torch.from_numpy((c[:, 5:] == cls_conf[:, None]).numpy().argmax(1))       # numpy: the FIRST maximum
@@ -56,10 +57,11 @@ def nms_image(x, conf_thres=0.5, nms_thres=0.4, dtype=torch.float32, trace=None)
     order = torch.from_numpy(np.lexsort((idx.numpy(), -score.numpy())))
     box, conf, cls_conf, cls, src, score = box[order], c[order, 4], cls_conf[order], cls[order], idx[order], score[order]
     alive = np.ones(len(order), bool)
-    keep, rows, ious = [], [], []
+    keep, rows, ious, heads = [], [], [], []
     for h in range(len(order)):
         if not alive[h]:
             continue
+        heads.append(h)
         rem = np.nonzero(alive)[0]
         iou = _iou_plus1(box[h], box[rem])
         same = (cls[rem] == cls[h]).numpy()
@@ -74,7 +76,7 @@ def nms_image(x, conf_thres=0.5, nms_thres=0.4, dtype=torch.float32, trace=None)
         alive[inv] = False
         alive[h] = False
     if trace is not None:
-        trace.update(ious=np.concatenate(ious) if ious else np.zeros(0), scores=score.numpy().astype(np.float64))
+        trace.update(ious=np.concatenate(ious) if ious else np.zeros(0), scores=score.numpy().astype(np.float64), heads=heads)
     return torch.stack(keep), torch.tensor(rows, dtype=torch.int64)
 
 
@@ -202,6 +204,49 @@ def assignment_is_unique(iou, thr):
             if sum(alt[a, b] for a, b in assign_scipy(alt)) - 1e3 + iou[d, c] >= best - 1e-6:
                 return False
     return True
+
+
+def assign_paths(iou, columns=64):
+    """The textbook row-by-row solver (shortest augmenting paths with potentials over cost = -IoU, the detections as rows in their
+    order, the trackers as the first columns of ``columns``, the others dummy columns of cost 0) -> (pairs (detection, tracker), the
+    longest augmenting path in columns, the most columns any one row's search marked used).  It tells the guards how far a row-ordered
+    solver has to re-route on a drawn input; no device result is compared with it."""
+    iou = np.asarray(iou, dtype=np.float64)
+    nd, nt = iou.shape
+    m = max(columns, nt)
+    assert nd <= m
+    cost = np.zeros((nd + 1, m + 1))
+    cost[1:, 1:nt + 1] = -iou
+    u, v = np.zeros(nd + 1), np.zeros(m + 1)
+    p, way = np.zeros(m + 1, int), np.zeros(m + 1, int)
+    longest = most_used = 0
+    for i in range(1, nd + 1):
+        p[0] = i
+        j0 = 0
+        minv, used = np.full(m + 1, np.inf), np.zeros(m + 1, bool)
+        while True:
+            used[j0] = True
+            i0 = p[j0]
+            cur = cost[i0] - u[i0] - v
+            better = ~used & (cur < minv)
+            minv[better], way[better] = cur[better], j0
+            free = np.nonzero(~used)[0]
+            j1 = free[np.argmin(minv[free])]
+            delta = minv[j1]
+            u[p[used]] += delta
+            v[used] -= delta
+            minv[~used] -= delta
+            j0 = j1
+            if p[j0] == 0:
+                break
+        most_used = max(most_used, int(used.sum()) - 1)
+        steps = 0
+        while j0:
+            p[j0] = p[way[j0]]
+            j0 = way[j0]
+            steps += 1
+        longest = max(longest, steps)
+    return sorted((int(p[j]) - 1, j - 1) for j in range(1, nt + 1) if p[j]), longest, most_used
 
 
 # ----------------------------------------------------------------------------------------------
@@ -362,10 +407,11 @@ class Sort:
 
 
 def sort_tracks(people_rows, people_count, seq_offsets=None, max_age=1, min_hits=3, iou_threshold=0.3, max_tracks=64, update_on_empty=0,
-                dtype=np.float64, assign=assign_scipy, ious=None):
+                dtype=np.float64, assign=assign_scipy, ious=None, live=None):
     """multi_person_tracker's run_tracker over frames: people [F, K, 5], counts [F] -> (tracks [F, max_tracks, 5] in ``dtype``,
     track_count int32 [F], status int32 [F]); a frame without detections leaves the tracker untouched unless ``update_on_empty``.
-    ``ious``: a list that receives every IoU matrix handed to the assignment (for the guard)."""
+    ``ious``: a list that receives every IoU matrix handed to the assignment (for the guard); ``live``: a list that receives
+    (frame, ids of the tracker list after the frame) of every frame the tracker saw."""
     F = len(people_count)
     seq = [0, F] if seq_offsets is None else [int(v) for v in seq_offsets]
     tracks, cnt, status = np.zeros((F, max_tracks, 5), dtype), np.zeros(F, np.int32), np.zeros(F, np.int32)
@@ -378,6 +424,8 @@ def sort_tracks(people_rows, people_count, seq_offsets=None, max_age=1, min_hits
             rows, status[f] = s.update(np.asarray(people_rows[f, :nd], dtype).reshape(nd, 5))
             if ious is not None and s.last_iou is not None:
                 ious.append(s.last_iou)
+            if live is not None:
+                live.append((f, [t.id for t in s.trackers]))
             tracks[f, :len(rows)], cnt[f] = rows, len(rows)
     return tracks, cnt, status
 
@@ -522,4 +570,252 @@ def draw_many_rows(seed=MANY_SEED, R=1500):
                            [140, 300, 60, 80]], dtype=torch.float32)
     k = torch.from_numpy(np.random.default_rng(seed).integers(0, 6, R))
     rows[0, :, 0:4] = protos[k]
+    return rows
+
+
+# ----------------------------------------------------------------------------------------------
+# drawn inputs at the kernels' documented sizes (tests/test_gpu_tracker_crowd.py; guards in tests/test_tracker_host.py)
+# ----------------------------------------------------------------------------------------------
+
+CHAIN_W, CHAIN_D, CHAIN_E = 100.0, 30.0, 29.4
+CHAIN_SHUFFLE = 61
+CHAIN_A = (CHAIN_W - CHAIN_D) / (CHAIN_W + CHAIN_D)                                    # a detection with its own tracker: 70 / 130
+CHAIN_B = (CHAIN_W - CHAIN_E) / (CHAIN_W + CHAIN_E)                                    # ... with the next one: 70.6 / 129.4 > a
+# (n, reverse, shuffle seed or None) of the device's chain cases
+CHAIN_CASES = [(n, rev, sh) for n in (8, 33, 64) for rev in (False, True) for sh in (None, CHAIN_SHUFFLE)]
+
+
+def chain_order(n, reverse=False, shuffle_seed=None, extra=False, drop=None):
+    """The box behind every detection of the chain's frames >= 1 (n = the extra box).  Unshuffled, the boxes come in the order in which a
+    row-ordered solver meets its worst case: ascending, or descending with ``reverse`` - then every row but the last asks for the
+    tracker that the next row's box owns, and the last row, which overlaps its own tracker only, re-routes all the earlier ones."""
+    order = [i for i in range(n) if i != drop] + ([n] if extra else [])
+    if reverse:
+        order = order[::-1]
+    if shuffle_seed is not None:
+        order = [order[i] for i in np.random.default_rng(shuffle_seed).permutation(len(order))]
+    return order
+
+
+def chain_scene(n, reverse=False, shuffle_seed=None, frames=5, extra=False, drop=None, K=64):
+    """people [frames, K, 5], counts: frame 0 has n boxes 100 x 100 with left edges S i, S = d + e = 59.4, in slot order; from frame 1
+    on the same boxes stand moved by d = 30 towards box i + 1 (``reverse``: i - 1), listed in ``chain_order``.  At frame 1 the trackers
+    have no velocity, so detection i has the IoU a = 70 / 130 with its own tracker and b = 70.6 / 129.4 > a with the next one, the last
+    box with its own only: the optimum keeps every box on its own tracker (n a > (n - 1) b) although every row but one prefers another.
+    ``extra``: one more box, moved by 45 from the last tracker, which it alone overlaps (IoU 55 / 145 = 0.379 < a: it loses the tracker
+    and founds a new one; more detections than trackers).  ``drop``: that box is missing from frame 1 on (fewer detections than
+    trackers, the chain cut in two): the boxes before the gap each take the next tracker, which is free now and better, the boxes
+    behind it keep their own, and the first tracker (``reverse``: the last) goes without."""
+    S, sign = CHAIN_D + CHAIN_E, -1.0 if reverse else 1.0
+    out, cnt = np.zeros((frames, K, 5)), np.zeros(frames, np.int32)
+    left = [S * i for i in range(n)] + [S * (0 if reverse else n - 1) + sign * (45.0 - CHAIN_D)]
+    for i in range(n):
+        out[0, i] = [left[i], 0.0, left[i] + CHAIN_W, 100.0, 0.9]
+    cnt[0] = n
+    order = chain_order(n, reverse, shuffle_seed, extra, drop)
+    for f in range(1, frames):
+        for k, i in enumerate(order):
+            x = left[i] + sign * CHAIN_D
+            out[f, k] = [x, 0.0, x + CHAIN_W, 100.0, 0.9]
+        cnt[f] = len(order)
+    return out, cnt
+
+
+HOLES_N, HOLES_DEAD, HOLES_NEW, HOLES_SHUFFLE = 40, tuple(range(7, 40, 8)), 3, 62
+HOLES_KW = dict(max_age=0, min_hits=1)
+
+
+def chain_holes(frames=5, K=64):
+    """The chain over 40 slots of which every 8th is dead, for ``max_age = 0``: frame 0 founds 40 trackers, frame 1 shows all but
+    boxes 7, 15, 23, 31, 39 where they stood (those five die, the others keep zero velocity), from frame 2 on the 35 survivors stand
+    moved by d - five chains of 7, free slots between them inside the assignment - and three new boxes far below are born into slots
+    7, 15 and 23, below live trackers.  Detection order: one fixed permutation per kind of frame."""
+    S = CHAIN_D + CHAIN_E
+    out, cnt = np.zeros((frames, K, 5)), np.zeros(frames, np.int32)
+    g = np.random.default_rng(HOLES_SHUFFLE)
+    live = [i for i in range(HOLES_N) if i not in HOLES_DEAD]
+    for i in range(HOLES_N):
+        out[0, i] = [S * i, 0.0, S * i + CHAIN_W, 100.0, 0.9]
+    cnt[0] = HOLES_N
+    for k, i in enumerate([live[j] for j in g.permutation(len(live))]):
+        out[1, k] = [S * i, 0.0, S * i + CHAIN_W, 100.0, 0.9]
+    cnt[1] = len(live)
+    boxes = [[S * i + CHAIN_D, 0.0, S * i + CHAIN_D + CHAIN_W, 100.0, 0.9] for i in live]
+    boxes += [[300.0 * j, 400.0, 300.0 * j + 80.0, 560.0, 0.9] for j in range(HOLES_NEW)]
+    perm = g.permutation(len(boxes))
+    for f in range(2, frames):
+        for k, j in enumerate(perm):
+            out[f, k] = boxes[j]
+        cnt[f] = len(boxes)
+    return out, cnt
+
+
+CROWD_SEEDS = (73, 74)
+# the parameter sets of the crowd runs: the defaults, a multi-frame coast, no coast and no probation, a higher threshold
+CROWD_PARAMS = [dict(), dict(max_age=3, min_hits=1), dict(max_age=0, min_hits=0), dict(iou_threshold=0.5)]
+CROWD_EMPTY = (9, 15)
+# (seed, persons, frames) and the parameter sets of the widest crowd: matrices near 60 x 60, every one of the 64 slots in use
+WIDE_CROWD, WIDE_PARAMS = (75, 64, 16), [dict(max_age=3, min_hits=1), dict(max_age=0, min_hits=0)]
+
+
+def draw_crowd(seed, frames=24, persons=40, empty=(), K=64):
+    """people [frames, K, 5], counts: ``persons`` on a jittered grid of 10 columns, 120 px apart and 260 px between the rows, boxes about
+    85 x 175; alternate persons walk left and right at 6 to 14 px per frame with 1.5 px of jitter; a quarter are born late, a quarter
+    leave early, every detection is missing with probability 0.06, the order of a frame's detections is drawn afresh; the frames in
+    ``empty`` have no detection."""
+    g = np.random.default_rng(seed)
+    i = np.arange(persons)
+    x0 = 150.0 + 120.0 * (i % 10) + g.normal(0, 8.0, persons)
+    y0 = 150.0 + 260.0 * (i // 10) + g.normal(0, 8.0, persons)
+    w, h = 85.0 + g.normal(0, 4.0, persons), 175.0 + g.normal(0, 6.0, persons)
+    speed = g.uniform(6.0, 14.0, persons) * np.where(i % 2 == 0, 1.0, -1.0)
+    who = g.permutation(persons)
+    born, gone = np.zeros(persons, int), np.full(persons, frames)
+    q = persons // 4
+    born[who[:q]] = g.integers(2, max(3, frames // 2), q)
+    gone[who[q:2 * q]] = g.integers(frames // 2, max(frames // 2 + 1, frames - 2), q)
+    out, cnt = np.zeros((frames, K, 5)), np.zeros(frames, np.int32)
+    for f in range(frames):
+        boxes = []
+        for p in range(persons):
+            j, miss = g.normal(0, 1.5, 4), g.uniform() < 0.06
+            if born[p] <= f < gone[p] and not miss and f not in empty:
+                cx, cy = x0[p] + speed[p] * f + j[0], y0[p] + j[1]
+                boxes.append([cx - (w[p] + j[2]) / 2, cy - (h[p] + j[3]) / 2, cx + (w[p] + j[2]) / 2, cy + (h[p] + j[3]) / 2, 0.9])
+        for k, b in enumerate(g.permutation(len(boxes))):
+            out[f, k] = boxes[b]
+        cnt[f] = len(boxes)
+    return out, cnt
+
+
+def replay_slots(live, reported):
+    """The lowest-free-slot rule over the restatement's births and deaths.  ``live``: what ``sort_tracks(live=...)`` recorded;
+    ``reported``: {frame: ids in report order} -> (frames whose reported trackers, read in slot order, are not in id order, births
+    into a slot below a live tracker, frames seen)."""
+    slot, known, mixed, below = {}, -1, 0, 0
+    for f, ids in live:
+        for t in sorted(t for t in ids if t > known):                                 # births, in id order, before this frame's deaths
+            s = min(set(range(len(slot) + 1)) - set(slot.values()))
+            below += bool(slot) and s < max(slot.values())
+            slot[t] = s
+        known = max([known] + ids)
+        by_slot = sorted((t - 1 for t in reported[f]), key=lambda t: slot[t])
+        mixed += by_slot != sorted(by_slot)
+        slot = {t: s for t, s in slot.items() if t in ids}
+    return mixed, below, len(live)
+
+
+HOUSE_SEED = 81
+
+
+def full_house(frames=5, K=64):
+    """64 jittered boxes on an 8 x 8 grid in frame 0, the same 64 moved 5000 px away from frame 1 on (no overlap with any tracker), the
+    order of a frame's detections drawn afresh: with 64 slots nothing is free until the first 64 have died."""
+    g = np.random.default_rng(HOUSE_SEED)
+    out, cnt = np.zeros((frames, K, 5)), np.full(frames, 64, np.int32)
+    i = np.arange(64)
+    cx, cy = 100.0 + 200.0 * (i % 8) + g.normal(0, 5.0, 64), 120.0 + 260.0 * (i // 8) + g.normal(0, 5.0, 64)
+    w, h = 80.0 + g.normal(0, 3.0, 64), 165.0 + g.normal(0, 5.0, 64)
+    for f in range(frames):
+        j = g.normal(0, 1.0, (64, 4)) if f else np.zeros((64, 4))
+        x = cx + (5000.0 if f else 0.0) + j[:, 0]
+        for k, b in enumerate(g.permutation(64) if f else i):
+            out[f, k] = [x[b] - (w[b] + j[b, 2]) / 2, cy[b] + j[b, 1] - (h[b] + j[b, 3]) / 2, x[b] + (w[b] + j[b, 2]) / 2,
+                         cy[b] + j[b, 1] + (h[b] + j[b, 3]) / 2, 0.9]
+    return out, cnt
+
+
+SHRINK_KW = dict(max_age=3, min_hits=1)
+
+
+def shrink_scene(frames=9):
+    """people [frames, 4, 5]: one person walking steadily (so that no frame is empty) and one whose box shrinks fast - 100, 80, 62, 46 px
+    square in frames 0 to 3, matched every time - and is gone from frame 4 on: its area's velocity is far below zero when it starts to
+    coast, and the coasting area would pass zero.  From frame 5 on a 24 px box stands where it was: it fits the tracker whose area's
+    velocity was set to zero (area 601), and no other."""
+    out, cnt = np.zeros((frames, 4, 5)), np.zeros(frames, np.int32)
+    for f in range(frames):
+        out[f, 0] = [400.0 + 3.1 * f, 50.3, 470.0 + 3.1 * f, 210.7, 0.9]
+        cnt[f] = 1
+        if f < 4:
+            s = (100.0, 80.0, 62.0, 46.0)[f]
+            out[f, 1] = [100.2 - s / 2, 100.1 - s / 2, 100.2 + s / 2, 100.1 + s / 2, 0.9]
+            cnt[f] = 2
+        if f >= 5:
+            out[f, 1] = [100.2 - 12.0, 100.1 - 12.0, 100.2 + 12.0, 100.1 + 12.0, 0.9]
+            cnt[f] = 2
+    return out, cnt
+
+
+FULL_SEED, KEEP_SEED, SEAM_SEED = MANY_SEED, 91, 92
+SEAM_ROWS = (0, 63, 64, 1023, 1024)
+
+
+def sorted_candidates(rows_i, conf_thres=0.5):
+    """One image's candidate rows in the suppression's order (fp32 score descending, ties by the lower row) and their classes."""
+    x = rows_i.to(torch.float32)
+    idx = torch.nonzero(x[:, 4] >= conf_thres)[:, 0]
+    cmax, cls = x[idx, 5:].max(1)
+    order = np.lexsort((idx.numpy(), -(x[idx, 4] * cmax).numpy()))
+    return idx[order], cls[order]
+
+
+def draw_full_rows(seed=FULL_SEED):
+    """``draw_many_rows`` at 2048 rows, the documented maximum of candidates (32 chunks of 64, the last one bit 31 of the kernel's
+    word), with the boxes of one class among the sorted positions 2000 .. 2047 moved to a place of their own: the first of them is a
+    head in the last chunk and takes the others with it."""
+    rows = draw_many_rows(seed, 2048)
+    idx, cls = sorted_candidates(rows[0])
+    sel = [int(idx[p]) for p in range(2000, 2048) if cls[p] == cls[2000]]
+    rows[0, sel, 0:4] = torch.tensor([330.0, 330.0, 60.0, 80.0])
+    return rows
+
+
+def draw_keep_rows(seed=KEEP_SEED, extra=False):
+    """One image whose suppression keeps exactly 64 boxes: 20 x 20 boxes in 48 cells of a 7 x 7 grid 56 px apart, one class per cell and
+    both classes in the first 16 - 64 groups -, every group a box plus 0 to 2 copies of its class moved by at most 2 px (+1-form IoU
+    with each other >= 0.48: one is kept), scores on a shuffled grid; the group with the lowest score is of class 0, alone, and its
+    conf is above 0.7 (the 64th kept row is a person).  30 more rows stay below conf_thres.  ``extra``: one more box alone in the
+    49th cell - 65 kept."""
+    g = np.random.default_rng(seed)
+    groups = [(c, c % 2) for c in range(48)] + [(c, 1 - c % 2) for c in range(16)]
+    low = groups.index((46, 0))
+    cand = []                                                                          # (cell, class, dx, dy, group)
+    for k, (c, cl) in enumerate(groups):
+        cand.append((c, cl, 0.0, 0.0, k))
+        for _ in range(0 if k == low else int(g.integers(0, 3))):
+            dx, dy = g.uniform(-2.0, 2.0, 2)
+            cand.append((c, cl, dx, dy, k))
+    n = len(cand)
+    rank = g.permutation(n)
+    first = next(i for i, t in enumerate(cand) if t[4] == low)
+    j = int(np.nonzero(rank == 0)[0][0])
+    rank[j], rank[first] = rank[first], 0                                              # the lowest score goes to the lone group
+    rows = np.zeros((n + 30 + (1 if extra else 0), 7), np.float32)
+    cmax = g.uniform(0.75, 0.98, n)
+    cmax[first] = 0.68
+    score = 0.5 + 0.22 * (rank + 0.5) / n
+    for i, (c, cl, dx, dy, _) in enumerate(cand):
+        rows[i, :5] = [30.0 + 56.0 * (c % 7) + dx, 30.0 + 56.0 * (c // 7) + dy, 20.0, 20.0, score[i] / cmax[i]]
+        rows[i, 5 + cl], rows[i, 6 - cl] = cmax[i], cmax[i] * g.uniform(0.0, 0.7)
+    rows[n:n + 30, 0:2] = g.uniform(20.0, 400.0, (30, 2))
+    rows[n:n + 30, 2:4] = 20.0
+    rows[n:n + 30, 4] = g.uniform(0.02, 0.45, 30)
+    rows[n:n + 30, 5:] = g.uniform(0.1, 0.9, (30, 2))
+    rows[:n + 30] = rows[g.permutation(n + 30)]
+    if extra:
+        rows[-1] = [30.0 + 56.0 * 6, 30.0 + 56.0 * 6, 20.0, 20.0, 0.9, 0.1, 0.85]
+    return torch.from_numpy(rows)[None]
+
+
+def draw_seam_rows(seed=SEAM_SEED):
+    """One image of 1025 rows (two tiles of the compaction, the second of one row) with candidates at rows 0, 63, 64, 1023 and 1024,
+    the ends of the first wave, of the first tile and the lone row of the second, among about a hundred others."""
+    rows = draw_rows(1, 1025, 2, seed, 0.1)
+    is_cand = (rows[0, :, 4] >= 0.5).numpy()
+    spare = [r for r in np.nonzero(is_cand)[0] if r not in SEAM_ROWS]
+    for r in SEAM_ROWS:
+        if not is_cand[r]:
+            s = spare.pop()
+            rows[0, [r, s]] = rows[0, [s, r]]
     return rows
