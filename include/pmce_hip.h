@@ -20,7 +20,7 @@
  *     pmce_model_profile_read (waits for the recorded events);
  *   - mutable state outside the handles: the thread-local error string and, while a model entry point runs, the thread-local
  *     pointer to that model's overflow word - one process per GPU or several host threads with their own streams are both fine -
- *     and the process-wide TUNING AIDS pmce_gemm_set_tuning, pmce_gemm_split_set_tuning (relaxed atomics
+ *     and the process-wide TUNING AIDS pmce_gemm_set_tuning, pmce_gemm_split_set_tuning, pmce_gemm_set_max_workgroups (relaxed atomics
  *     read at launch time: meant for benchmarks and tests, not to be flipped while forwards are being enqueued elsewhere).
  * Fixed structural constants of the path: T = 16 frames, F = 2048 image-feature channels, V = 431 coarse
  * vertices, 6890 mesh vertices, D = 64 decoder channels, GRU hidden 1024, 8 lifter heads.  J <= 32,
@@ -223,6 +223,11 @@ int pmce_gemm_nt_f32(const float* A, const float* W, const float* bias, const fl
 /* Tuning aid only: force the tile configuration (0..3, -1 = automatic) and the persistent workgroups per CU (1..8, 0 =
  * automatic) of pmce_gemm_nt_f32 for the whole process (initially automatic; no environment variable sets it, see pmce_model_create). */
 int pmce_gemm_set_tuning(int tile, int grid_per_cu);
+/* Tuning aid only, process-wide like the one above: at most n workgroups (rounded up to a multiple of 8; 0 = automatic, the initial state) per
+ * launch of the persistent kernels of pmce_gemm_nt_f32, pmce_gemm_nt_split_f16 and pmce_gemm_nt_split_f16_ln, so that a product of a few dozen
+ * tiles makes every workgroup walk several (tests/test_gpu_gemm_split_exact.py, tests/test_gpu_gemm_f32_exact.py).  The split product's
+ * small-grid kernel takes one tile per workgroup by design and ignores it.  Results do not depend on it. */
+int pmce_gemm_set_max_workgroups(int n);
 /* The same nn.Linear product on the f16 matrix pipe with fp32 operands, result and accuracy: W is split ONCE into f16
  * (hi, lo) planes of W[n] * 2^s(n) by pmce_gemm_pack_split_f16 (Wp: N*K floats of storage; wscale: N floats, 2^-s(n) - one power
  * of two per OUTPUT ROW n of W, chosen so that the row's largest |w| 2^s lies in [2^14, 2^15): an outlier row does not cost the
@@ -267,6 +272,11 @@ int pmce_gemm_nt_split_f16_ln(const float* Ap, const float* Wp, int w_blocked, c
                               const float* ln2_b, float ln2_eps, float* out2, pmce_stream_t stream);
 /* Tuning aid only: force the tile configuration of pmce_gemm_nt_split_f16 (0: 128x256, 1: 128x128, 2: 64x128; -1 automatic). */
 int pmce_gemm_split_set_tuning(int tile);
+/* Which kernel pmce_gemm_nt_split_f16 launches for this product under the current tuning (a query: nothing is launched; the launch decides
+ * through the same function).  0 / 1 / 2: the persistent kernel with the 128x256 / 128x128 / 64x128 tile; 3: 64x128 with two k-tiles per
+ * stage; 4 / 5: the small-grid kernel (one tile per workgroup) with the 64x64 / 64x128 tile.  row_scaled implies a packed A.  Sizes the
+ * product refuses (K < 32, K % 16 != 0, a row-scaled A with K < 128) return PMCE_ERR_ARG. */
+int pmce_gemm_split_path(int M, int N, int K, int act, int a_packed, int c_packed, int has_residual, int row_scaled);
 /* PoseEstimation.py:78-81 — x[tok] = joint_embed(pose2d) + imgfeat_embed(img_feat)[b,t] + spatial_pos[j]. */
 int pmce_embed_tokens_f32(const float* pose2d, const float* E, const float* Wje, const float* bje, const float* spos,
                           float* x, long long ntok, int J, int C, pmce_stream_t stream);

@@ -66,6 +66,7 @@ PROTOTYPES = {
     "pmce_model_profile_read": [C.c_void_p, _i, C.POINTER(C.c_char_p), C.POINTER(C.c_double), C.POINTER(C.c_longlong)],
     "pmce_gemm_nt_f32": [_f, _f, _f, _f, _f, _i, _i, _i, _l, _i, _l, _i, _i, _l, _l, _i, _l, _l, _i, _l, _l, _l, _l, _s],
     "pmce_gemm_set_tuning": [_i, _i],
+    "pmce_gemm_set_max_workgroups": [_i],
     "pmce_gemm_pack_split_f16": [_f, _i, _i, _i, _f, _f, _i, _s],
     "pmce_gemm_nt_split_f16": [_f, _f, _f, _i, _f, _f, _f, _f, _i, _i, _i, _l, _l, _i, _i, _i, _i, _l, _l, _s],
     "pmce_split_rows_f16": [_f, _l, _i, _l, _f, _s],
@@ -80,6 +81,7 @@ PROTOTYPES = {
     "pmce_lifter_attention_split_f16": [_f, _f, _i, _i, _i, _i, _l, _l, _l, _s],
     "pmce_qkv_attention_fused_split_f16": [_f, _f, _f, _f, _f, _i, _i, _i, _f, _s],
     "pmce_gemm_split_set_tuning": [_i],
+    "pmce_gemm_split_path": [_i, _i, _i, _i, _i, _i, _i, _i],
     "pmce_embed_tokens_f32": [_f, _f, _f, _f, _f, _f, _l, _i, _i, _s],
     "pmce_embed_ln_f32": [_f, _f, _f, _f, _f, _f, _l, _i, _i, _f, _f, _fl, _f, _i, _s],
     "pmce_lifter_head_f32": [_f, _f, _f, _fl, _f, _f, _f, _f, _f, _f, _f, _i, _i, _i, _i, _s],

@@ -44,6 +44,8 @@ static inline int pmce_opt_in_lds(const void* fn, int bytes, std::atomic<unsigne
 }
 // integer environment knob, read once per process by its (function-local static) caller
 int pmce_env_int(const char* name, int dflt);
+// pmce_gemm_set_max_workgroups (gemm_f32.hip): 0 = automatic, else the most workgroups a persistent GEMM launch may start (a multiple of 8)
+int pmce_gemm_workgroup_cap(void);
 #endif
 
 #define PMCE_REQUIRE(cond, ...)                \

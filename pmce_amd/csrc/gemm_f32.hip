@@ -22,6 +22,8 @@
 //    VGPR for the whole kernel), so a slice is one VMEM instruction (+ packed GELU) per element and no address arithmetic
 //    on the vector unit, which shares its FMA lanes with the fp32 matrix pipe.  Stores are streaming (nt); residuals are
 //    fetched two slices ahead (the residual stream is cold when a launch starts).
+// Tests: tests/test_gpu_ops.py (fp64 parity at the model's shapes) and tests/test_gpu_gemm_f32_exact.py (integer operands, every tile, bit for
+// bit: ragged edges, row maps, batch, pitches, fences, and workgroups that walk tiles with the whole-tile and the riding epilogue).
 #include <stdlib.h>
 
 #include <type_traits>
@@ -382,6 +384,8 @@ template <int BM, int BN, int WGM>
 static void launch_gemm(const GemmParams& p, int batch, bool cmap, hipStream_t stream) {
   int g = p.ntm * p.ntn;
   if (g > p.grid_cap) g = p.grid_cap;
+  const int cap = pmce_gemm_workgroup_cap();  // test aid: a few workgroups walk many tiles each
+  if (cap > 0 && g > cap) g = cap;
   g = (g + 7) & ~7;  // the XCD chunking wants a multiple of 8 workgroups
   const dim3 grid(g, 1, batch), block(256);
   const bool res = p.R != nullptr;
@@ -409,6 +413,16 @@ extern "C" int pmce_gemm_set_tuning(int tile, int grid_per_cu) {
   g_force_grid.store(grid_per_cu, std::memory_order_relaxed);
   return PMCE_OK;
 }
+
+// Test aid (tests/test_gpu_gemm_f32_exact.py, test_gpu_gemm_split_exact.py): at most n workgroups per persistent launch of this kernel and of
+// gemm_split_kernel, so that a product of a few dozen tiles makes every workgroup walk several.  0 = automatic.
+static std::atomic<int> g_max_workgroups{0};
+extern "C" int pmce_gemm_set_max_workgroups(int n) {
+  PMCE_REQUIRE(n >= 0 && n <= (1 << 20), "gemm_set_max_workgroups: n=%d (0 = automatic, else 1 .. 2^20)", n);
+  g_max_workgroups.store(n > 0 ? (n + 7) & ~7 : 0, std::memory_order_relaxed);
+  return PMCE_OK;
+}
+int pmce_gemm_workgroup_cap(void) { return g_max_workgroups.load(std::memory_order_relaxed); }
 
 struct TileCfg { int bm, bn, bpc; double ovh; };
 static const TileCfg kTiles[] = {{128, 128, 2, 1.0}, {96, 128, 2, 1.015}, {64, 128, 3, 1.03}, {64, 64, 4, 1.03}};

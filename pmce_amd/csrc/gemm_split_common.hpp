@@ -54,5 +54,7 @@ __device__ __forceinline__ unsigned split_pack_exchange(float x, unsigned perm_s
 }
 
 // gemm_split_small.hip: the small-grid form (one 64 x 128 tile per workgroup, eight waves, at most one round of workgroups)
-bool pmce_gemm_split_small_applies(int M, int N, int K, int act, bool apack, bool opack, bool res, bool rs);
-int pmce_gemm_split_small_launch(SplitParams& p, int act, bool apack, bool opack, hipStream_t stream);
+// pmce_gemm_split_small_nwn: 2 (the 64 x 64 tile), 4 (64 x 128) or 0 (no small-grid form for this product) - the ONE decision both the
+// launch and pmce_gemm_split_path take.
+int pmce_gemm_split_small_nwn(int M, int N, int K, int act, bool apack, bool opack, bool res, bool rs);
+int pmce_gemm_split_small_launch(SplitParams& p, int nwn, bool apack, bool opack, hipStream_t stream);

@@ -7,7 +7,9 @@
 //     a = ahi + alo * 2^-11,  w * 2^s = whi + wlo            (hi = rne16(x), lo = rne16(x - hi); 22 mantissa bits each)
 //     a * w * 2^s  =  ahi whi + ahi wlo + alo (whi 2^-11)  +  O(2^-22)
 // (the dropped lo*lo term and the planes' own rounding sit below the fp32 product's accumulation error: measured against an
-// fp64 product the result is CLOSER than the fp32 pipe's, tests/test_gpu_ops.py).  2^s - a power of two per OUTPUT ROW of W
+// fp64 product the result is CLOSER than the fp32 pipe's, tests/test_gpu_ops.py; on operands whose planes are known integers the three
+// products have ONE fp32 value and every tile shape, path and epilogue form is held to it bit for bit, tests/test_gpu_gemm_split_exact.py
+// with tests/gemm_split_ref.py).  2^s - a power of two per OUTPUT ROW of W
 // (round 3; per tensor before), chosen by pmce_gemm_pack_split_f16 - lifts the row's max|w| to [2^14, 2^15) so that wlo and
 // whi 2^-11 are normal f16 numbers for every weight within 2^-17 of the row's largest: an outlier row cannot starve the other
 // rows' lo planes.  alo carries 2^11 so that it is normal wherever ahi is.  No operand relies on f16 sub-normals.
@@ -551,6 +553,12 @@ static int launch_one(const SplitParams& p, int grid, hipStream_t stream) {
   hipLaunchKernelGGL((gemm_split_kernel<TM, TN, ACT, RES, APACK, OPACK, RS, KSUB, LNEP>), dim3(grid), dim3(256), LDS, stream, p);
   return PMCE_OK;
 }
+// the persistent grid: pmce_gemm_set_max_workgroups' cap (a test aid; 0 = none), then a multiple of 8 (the XCD chunking)
+static int capped_grid(int g) {
+  const int cap = pmce_gemm_workgroup_cap();
+  if (cap > 0 && g > cap) g = cap;
+  return (g + 7) & ~7;
+}
 // the 64x128 tile with two k-tiles per stage (small grids): the operand / epilogue combinations the model's products use
 template <int KSUB>
 static int launch_small_k32(SplitParams& p, int act, bool apack, bool opack, hipStream_t stream) {
@@ -559,7 +567,7 @@ static int launch_small_k32(SplitParams& p, int act, bool apack, bool opack, hip
   p.ntn = (p.N + Cfg::BN - 1) / Cfg::BN;
   int g = p.ntm * p.ntn;
   if (g > 512) g = 512;
-  g = (g + 7) & ~7;
+  g = capped_grid(g);
   const bool res = p.R != nullptr;
   if (p.rscale) return launch_one<1, 2, 0, false, true, false, true, KSUB>(p, g, stream);
   if (opack) return launch_one<1, 2, 1, false, true, true, false, KSUB>(p, g, stream);
@@ -580,7 +588,7 @@ static int launch_cfg(SplitParams& p, int act, bool apack, bool opack, hipStream
   const int per_cu = (160 * 1024) / Cfg::LDS_BYTES >= 3 ? 3 : 2;
   int g = p.ntm * p.ntn;
   if (g > 256 * per_cu) g = 256 * per_cu;
-  g = (g + 7) & ~7;
+  g = capped_grid(g);
   const bool res = p.R != nullptr;
   if (p.rscale) return launch_one<TM, TN, 0, false, true, false, true>(p, g, stream);  // raw-input products: packed, row-scaled A
   if (opack) return launch_one<TM, TN, 1, false, true, true>(p, g, stream);  // fc1 of the lifter: GELU, packed in, packed out
@@ -630,6 +638,29 @@ static int pick_split_tile(int M, int N) {
   return best;
 }
 
+// Which kernel takes the product under the current tuning - the ONE decision, read by gemm_split_any's launch and by pmce_gemm_split_path.
+enum SplitPath { kPathTile0 = 0, kPathTile1 = 1, kPathTile2 = 2, kPathTwoKTiles = 3, kPathSmall64 = 4, kPathSmall128 = 5 };
+static int split_path(int M, int N, int K, int act, bool apack, bool opack, bool res, bool rs) {
+  const int tile = pick_split_tile(M, N);
+  const bool automatic = g_split_tile.load(std::memory_order_relaxed) < 0;
+  if (tile == 2 && automatic) {
+    // at most one round of 64 x 128 tiles: the small-grid kernel (gemm_split_small.hip: eight waves per tile, a deep ring, no tile stream)
+    const int nwn = pmce_gemm_split_small_nwn(M, N, K, act, apack, opack, res, rs);
+    if (nwn != 0) return nwn == 2 ? kPathSmall64 : kPathSmall128;
+    if (K % 32 == 0 && K >= 128 && (long long)((M + 63) / 64) * ((N + 127) / 128) <= 512 && small_k32_form_exists(act, apack, opack, res, rs))
+      return kPathTwoKTiles;  // small grid: two k-tiles per trip
+  }
+  return tile;
+}
+// 0 / 1 / 2: the persistent kernel's 128x256 / 128x128 / 64x128 tile; 3: 64x128 with two k-tiles per stage; 4 / 5: the small-grid kernel's
+// 64x64 / 64x128 tile; PMCE_ERR_ARG: a product pmce_gemm_nt_split_f16 refuses for its sizes.  A query: it launches nothing.
+extern "C" int pmce_gemm_split_path(int M, int N, int K, int act, int a_packed, int c_packed, int has_residual, int row_scaled) {
+  PMCE_REQUIRE(M > 0 && N > 0 && K >= 32 && K % 16 == 0, "gemm_split_path: need M,N>0, K>=32 and K%%16==0 (got M=%d N=%d K=%d)", M, N, K);
+  PMCE_REQUIRE(act == 0 || act == 1, "gemm_split_path: act must be 0 or 1");
+  PMCE_REQUIRE(!row_scaled || K >= 128, "gemm_split_path: a row-scaled A needs K >= 128");
+  return split_path(M, N, K, act, (a_packed || row_scaled) != 0, c_packed != 0, has_residual != 0, row_scaled != 0);
+}
+
 static int gemm_split_any(const float* A, const float* Wp, const float* wscale, const float* bias, const float* R, float* C, int M,
                           int N, int K, long long lda, long long ldc, int act, int a_packed, int c_packed, int c_div,
                           long long c_lo, long long c_hi, hipStream_t stream, const float* rscale = nullptr, int w_blocked = 0) {
@@ -656,22 +687,18 @@ static int gemm_split_any(const float* A, const float* Wp, const float* wscale, 
   p.ln1_w = p.ln1_b = p.ln2_w = p.ln2_b = nullptr; p.ln1_eps = p.ln2_eps = 0.f; p.out1 = p.out2 = nullptr;
   p.oflow = pmce_overflow_sink();
   p.clk = pmce_clock_sink();  // (thread-local: set while an entry point of a model with a clock probe runs)
-  const int tile = pick_split_tile(M, N);
-  // at most one round of 64 x 128 tiles: the small-grid kernel (gemm_split_small.hip: eight waves per tile, a deep ring, no tile stream)
-  if (tile == 2 && g_split_tile.load(std::memory_order_relaxed) < 0 &&
-      pmce_gemm_split_small_applies(M, N, K, act, a_packed != 0, c_packed != 0, R != nullptr, rscale != nullptr)) {
-    PMCE_TRY(pmce_gemm_split_small_launch(p, act, a_packed != 0, c_packed != 0, stream));
-    return pmce_check_launch("gemm_nt_split_f16 (small grid)");
-  }
-  if (tile == 2 && g_split_tile.load(std::memory_order_relaxed) < 0 && K % 32 == 0 && K >= 128 &&
-      (long long)((M + 63) / 64) * ((N + 127) / 128) <= 512 &&
-      small_k32_form_exists(act, a_packed != 0, c_packed != 0, R != nullptr, rscale != nullptr)) {
-    PMCE_TRY(launch_small_k32<2>(p, act, a_packed != 0, c_packed != 0, stream));  // small grid: two k-tiles per trip
-    return pmce_check_launch("gemm_nt_split_f16 (64x128, two k-tiles per stage)");
-  }
-  switch (tile) {
-    case 0: PMCE_TRY((launch_cfg<2, 4>(p, act, a_packed != 0, c_packed != 0, stream))); break;
-    case 1: PMCE_TRY((launch_cfg<2, 2>(p, act, a_packed != 0, c_packed != 0, stream))); break;
+  switch (split_path(M, N, K, act, a_packed != 0, c_packed != 0, R != nullptr, rscale != nullptr)) {
+    case kPathSmall64:
+      PMCE_TRY(pmce_gemm_split_small_launch(p, 2, a_packed != 0, c_packed != 0, stream));
+      return pmce_check_launch("gemm_nt_split_f16 (small grid)");
+    case kPathSmall128:
+      PMCE_TRY(pmce_gemm_split_small_launch(p, 4, a_packed != 0, c_packed != 0, stream));
+      return pmce_check_launch("gemm_nt_split_f16 (small grid)");
+    case kPathTwoKTiles:
+      PMCE_TRY(launch_small_k32<2>(p, act, a_packed != 0, c_packed != 0, stream));
+      return pmce_check_launch("gemm_nt_split_f16 (64x128, two k-tiles per stage)");
+    case kPathTile0: PMCE_TRY((launch_cfg<2, 4>(p, act, a_packed != 0, c_packed != 0, stream))); break;
+    case kPathTile1: PMCE_TRY((launch_cfg<2, 2>(p, act, a_packed != 0, c_packed != 0, stream))); break;
     default: PMCE_TRY((launch_cfg<1, 2>(p, act, a_packed != 0, c_packed != 0, stream))); break;
   }
   return pmce_check_launch("gemm_nt_split_f16");
@@ -712,8 +739,7 @@ extern "C" int pmce_gemm_nt_split_f16_ln(const float* Ap, const float* Wp, int w
   p.ln2_w = ln2_w; p.ln2_b = ln2_b; p.ln2_eps = ln2_eps; p.out2 = out2;
   p.ntm = (M + 63) / 64;
   p.ntn = 1;
-  int g = p.ntm > 512 ? 512 : p.ntm;
-  g = (g + 7) & ~7;
+  const int g = capped_grid(p.ntm > 512 ? 512 : p.ntm);
   // (two k-tiles per stage on small grids, as the plain 64 x 128 tile has them, were measured and change nothing here: at M = 272 the
   // launch is its prologue and the epilogue's dependent chain, not the 16 trips of its k-loop)
   PMCE_TRY((launch_one<1, 4, 0, true, true, false, false, 1, true>(p, g, stream)));

@@ -14,7 +14,8 @@
 // issue - multiply), bias / scales / residual requested before the first k-tile instead of after the last, a ring of six 24 KB or four 16 KB
 // stages of two k-tiles each.
 // Arithmetic: the same k-tiles in the same order into one fp32 accumulator per element, the same epilogue expressions - results are
-// bit-identical to the persistent kernel's (tests: batch invariance B = 4 against B = 64; test_gemm_split_small_grid_equals_persistent).
+// bit-identical to the persistent kernel's (tests: batch invariance B = 4 against B = 64; test_gemm_split_small_grid_equals_persistent; and both
+// tiles against the exact value of plane-exact operands, tests/test_gpu_gemm_split_exact.py).
 #include <atomic>
 
 #include "gemm_split_common.hpp"
@@ -229,13 +230,16 @@ static int small_nwn_for(int M, int N) {
 
 // Is there a small-grid form for this product?  (K in whole pairs of k-tiles; one round of workgroups; the operand / epilogue combinations
 // the model's small products use.)
-bool pmce_gemm_split_small_applies(int M, int N, int K, int act, bool apack, bool opack, bool res, bool rs) {
+static bool small_form_exists(int K, int act, bool apack, bool opack, bool res, bool rs) {
   if (K % 32 != 0 || K < 64) return false;
-  if (small_nwn_for(M, N) == 0) return false;
   if (rs) return K >= 128;  // (the row-scaled form's documented limit, enforced by gemm_split_any before either kernel is chosen)
   if (opack) return act == 1;
   if (apack) return act == 0;
   return act == 0 && !res;
+}
+// -> 2: the 64 x 64 tile, 4: the 64 x 128 tile, 0: no small-grid form (the persistent kernel takes the product)
+int pmce_gemm_split_small_nwn(int M, int N, int K, int act, bool apack, bool opack, bool res, bool rs) {
+  return small_form_exists(K, act, apack, opack, res, rs) ? small_nwn_for(M, N) : 0;
 }
 
 template <int NWN>
@@ -249,7 +253,7 @@ static int launch_small_cfg(SplitParams& p, bool apack, bool opack, hipStream_t 
   return launch_small<NWN, 0, false, false, false, false>(p, stream);
 }
 
-int pmce_gemm_split_small_launch(SplitParams& p, int act, bool apack, bool opack, hipStream_t stream) {
-  (void)act;
-  return small_nwn_for(p.M, p.N) == 2 ? launch_small_cfg<2>(p, apack, opack, stream) : launch_small_cfg<4>(p, apack, opack, stream);
+int pmce_gemm_split_small_launch(SplitParams& p, int nwn, bool apack, bool opack, hipStream_t stream) {
+  PMCE_REQUIRE(nwn == 2 || nwn == 4, "gemm_split (small grid): tile width %d", nwn);
+  return nwn == 2 ? launch_small_cfg<2>(p, apack, opack, stream) : launch_small_cfg<4>(p, apack, opack, stream);
 }
