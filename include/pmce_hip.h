@@ -801,7 +801,7 @@ int pmce_vitpose_forward(const pmce_vitpose* v, const float* patches, long long 
                          float* heat, float* feat, void* workspace, size_t workspace_bytes, pmce_stream_t stream);
 
 /* ---------------------------------------------------------------------------------------------------------
- * ViTPose's opt-in single-product f16 mode (csrc/gemm_f16.hip, csrc/vit_attention_f16.hip, csrc/layernorm_rows.hip): the four products
+ * ViTPose's opt-in single-product f16 mode (csrc/gemm_f16.hip, csrc/vit_attention.hip, csrc/layernorm_rows.hip): the four products
  * and the attention of every block as ONE f16 matrix product with fp32 accumulation, the operands between them stored as single f16.
  * r16(x) is round-to-nearest-even to f16 with every |x| < 2^-14 set to zero: every operand is rounded by it, none relies on f16
  * sub-normals.  The default mode's entries above keep their bits.
@@ -820,8 +820,8 @@ int pmce_vitpose_forward(const pmce_vitpose* v, const float* patches, long long 
  *   anything else automatic; max_workgroups > 0 caps the persistent grid.  Results do not depend on either.
  * pmce_layernorm_rows_f16: pmce_layernorm_rows_f32's arithmetic, the result stored as r16(y), f16 [rows][C].  It does not touch the
  *   overflow word: a y beyond 65504 is stored as infinity and reported by the product that reads it.
- * pmce_vit_attention_f16: pmce_vit_attention_split_f16's input, work split, bounds and shapes (pmce_vit_attention_supported answers
- *   for both); q, k, v rounded by r16, s = q.k hd^-0.5 in one accumulator, p~ = exp(s - max), out = (r16(p~) . r16(v)) / sum(p~) with
+ * pmce_vit_attention_f16: pmce_vit_attention_split_f16's kernel without the lo planes - its input, work split, bounds and shapes
+ *   (pmce_vit_attention_supported answers for both); q, k, v rounded by r16, s = q.k hd^-0.5 in one accumulator, p~ = exp(s - max), out = (r16(p~) . r16(v)) / sum(p~) with
  *   the sum over the unrounded fp32 p~, stored as r16, f16 [n N][C].
  * pmce_vitpose_create_precision: pmce_vitpose_create with `precision` 0 (split, what pmce_vitpose_create passes) or 1 (f16; anything
  *   else PMCE_ERR_ARG naming the value).  The tensor table is the same in both.  In f16 mode the 4 x depth block weights are packed by

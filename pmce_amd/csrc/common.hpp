@@ -204,6 +204,31 @@ __device__ __forceinline__ void lds_dma_copy(float* lds_dst, const float* src, i
   for (int c = w0; c < kib; c += nwaves) lds_dma16(rsrc, (unsigned)(c * 1024 + lane * 16), 0, base + (unsigned)c * 1024u);
 }
 
+// The tile walk of the persistent GEMMs, in two pieces.
+// The XCD chunk.  The hardware places workgroup b on XCD b % 8; XCD x owns a contiguous chunk [start, start + len) of the nblk units of the
+// launch's order (8 chunks whose lengths differ by at most one and add up to nblk) and its gx resident workgroups - this one is number bx
+// of them - walk that chunk round-robin (bx, bx + gx, ...; a workgroup with bx >= len has nothing to do), so the tiles in flight on one
+// XCD share A / W panels in its L2.  Correctness never depends on the placement.  The grid is a multiple of 8 workgroups.
+struct XcdChunk {
+  int start, len, bx, gx;
+};
+__device__ __forceinline__ XcdChunk xcd_chunk(int nblk) {
+  const int xcd = blockIdx.x & 7, cq = nblk >> 3, cr = nblk & 7;
+  const int start = xcd < cr ? xcd * (cq + 1) : cr * (cq + 1) + (xcd - cr) * cq;  // the first cr chunks are one longer
+  return {start, cq + (int)(xcd < cr), (int)(blockIdx.x >> 3), (int)(gridDim.x >> 3)};
+}
+// The grouped tile order.  Position bid of an ntm x ntn tile grid -> the tile's first row and column: groups of GROUP_M tile rows (the last
+// group takes what is left), inside a group the rows fastest, so that neighbours in the order share a W panel and a group its A panels.
+template <int GROUP_M, int BM, int BN>
+__device__ __forceinline__ void grouped_tile_coords(int bid, int ntm, int ntn, int& mb, int& nb) {
+  const int per_group = GROUP_M * ntn;
+  const int group = bid / per_group;
+  const int first_m = group * GROUP_M;
+  const int gsz = min(ntm - first_m, GROUP_M);
+  mb = (first_m + (bid % per_group) % gsz) * BM;
+  nb = ((bid % per_group) / gsz) * BN;
+}
+
 typedef _Float16 f16x4 __attribute__((ext_vector_type(4)));
 typedef _Float16 f16x8 __attribute__((ext_vector_type(8)));
 
@@ -236,7 +261,7 @@ __device__ __forceinline__ float pinned(float v) {
   asm volatile("" : "+v"(v));
   return v;
 }
-// The ONE rounding of the single-product f16 mode (gemm_f16.hip, vit_attention_f16.hip, layernorm_rows.hip): round to nearest even, and
+// The ONE rounding of the single-product f16 mode (gemm_f16.hip, the single-product form of vit_attention.hip, layernorm_rows.hip): round to nearest even, and
 // every |x| < 2^-14 becomes zero by a select - no operand relies on what the matrix pipe does with f16 sub-normals.  Inf / NaN stay.
 // A COMPUTED x goes through pinned() first, as for the planes.
 __device__ __forceinline__ _Float16 r16(float x) {

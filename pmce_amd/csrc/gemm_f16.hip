@@ -62,22 +62,12 @@ __global__ __launch_bounds__(256, 2) void gemm_f16_kernel(F16Params p) {
   const int n0 = lane & 31, hb = lane >> 5;
   const int wm = wave & 1, wn = wave >> 1;
 
-  // ---- persistent workgroups on an XCD-local chunk of the grouped tile order (gemm_split_f16.hip) ----
-  const int nblk = p.ntm * p.ntn;
-  const int xcd = blockIdx.x & 7, bx = blockIdx.x >> 3, gx = gridDim.x >> 3;
-  const int cq = nblk >> 3, cr = nblk & 7;
-  const int chunk_start = xcd < cr ? xcd * (cq + 1) : cr * (cq + 1) + (xcd - cr) * cq;
-  const int chunk_len = cq + (xcd < cr ? 1 : 0);
+  // ---- persistent workgroups on an XCD-local chunk of the grouped tile order (common.hpp: xcd_chunk, grouped_tile_coords; GROUP_M as the
+  // split kernel's) ----
+  const XcdChunk chunk = xcd_chunk(p.ntm * p.ntn);
+  const int chunk_start = chunk.start, chunk_len = chunk.len, bx = chunk.bx, gx = chunk.gx;
   if (bx >= chunk_len) return;
-  constexpr int GROUP_M = 4;
-  const int per_group = GROUP_M * p.ntn;
-  auto tile_coords = [&](int bid, int& mb, int& nb) {
-    const int group = bid / per_group;
-    const int first_m = group * GROUP_M;
-    const int gsz = min(p.ntm - first_m, GROUP_M);
-    mb = (first_m + (bid % per_group) % gsz) * BM;
-    nb = ((bid % per_group) / gsz) * BN;
-  };
+  auto tile_coords = [&](int bid, int& mb, int& nb) { grouped_tile_coords<4, BM, BN>(bid, p.ntm, p.ntn, mb, nb); };
   const int my_tiles = (chunk_len - bx + gx - 1) / gx;
   const int nk = p.K / 32;  // stages per tile
   const int total = my_tiles * nk;

@@ -79,23 +79,10 @@ __global__ __launch_bounds__(256, 2) void gemm_nt_kernel(GemmParams p) {
   const int n0 = lane & 31, hb = lane >> 5;
   const int wm = wave % WGM, wn = wave / WGM;
 
-  // ---- persistent workgroups.  The hardware places workgroup b on XCD b % 8; XCD x owns a contiguous chunk of
-  // the (grouped) tile order and its resident workgroups walk that chunk round-robin, so the tiles in flight on
-  // one XCD share A / W panels in its L2.  Correctness never depends on the placement. ----
-  const int nblk = p.ntm * p.ntn;
-  const int xcd = blockIdx.x & 7, bx = blockIdx.x >> 3, gx = gridDim.x >> 3;
-  const int cq = nblk >> 3, cr = nblk & 7;
-  const int chunk_start = xcd < cr ? xcd * (cq + 1) : cr * (cq + 1) + (xcd - cr) * cq;
-  const int chunk_len = cq + (xcd < cr ? 1 : 0);
-  constexpr int GROUP_M = 8;
-  const int per_group = GROUP_M * p.ntn;
-  auto tile_coords = [&](int bid, int& mb, int& nb) {
-    const int group = bid / per_group;
-    const int first_m = group * GROUP_M;
-    const int gsz = min(p.ntm - first_m, GROUP_M);
-    mb = (first_m + (bid % per_group) % gsz) * BM;
-    nb = ((bid % per_group) / gsz) * BN;
-  };
+  // ---- persistent workgroups on an XCD-local chunk of the grouped tile order (common.hpp: xcd_chunk, grouped_tile_coords) ----
+  const XcdChunk chunk = xcd_chunk(p.ntm * p.ntn);
+  const int chunk_start = chunk.start, chunk_len = chunk.len, bx = chunk.bx, gx = chunk.gx;
+  auto tile_coords = [&](int bid, int& mb, int& nb) { grouped_tile_coords<8, BM, BN>(bid, p.ntm, p.ntn, mb, nb); };
 
   const float* __restrict__ A = p.A + (long long)blockIdx.z * p.bsA;
   const float* __restrict__ W = p.W + (long long)blockIdx.z * p.bsW;

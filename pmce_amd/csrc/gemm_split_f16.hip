@@ -84,24 +84,13 @@ __global__ __launch_bounds__(256, 2) void gemm_split_kernel(SplitParams p) {
   const int n0 = lane & 31, hb = lane >> 5;
   const int wm = wave & 1, wn = wave >> 1;
 
-  // ---- persistent workgroups on an XCD-local chunk of the grouped tile order (gemm_f32.hip) ----
-  const int nblk = p.ntm * p.ntn;
-  const int xcd = blockIdx.x & 7, bx = blockIdx.x >> 3, gx = gridDim.x >> 3;
-  const int cq = nblk >> 3, cr = nblk & 7;
-  const int chunk_start = xcd < cr ? xcd * (cq + 1) : cr * (cq + 1) + (xcd - cr) * cq;
-  const int chunk_len = cq + (xcd < cr ? 1 : 0);
+  // ---- persistent workgroups on an XCD-local chunk of the grouped tile order (common.hpp: xcd_chunk, grouped_tile_coords) ----
+  const XcdChunk chunk = xcd_chunk(p.ntm * p.ntn);
+  const int chunk_start = chunk.start, chunk_len = chunk.len, bx = chunk.bx, gx = chunk.gx;
   if (bx >= chunk_len) return;
-  // (8 until round 6, as gemm_f32.hip has it; 4 measures 0.2-0.9 % faster on the lifter's products at C = 512 and, through what they leave in the
-  // caches, 2.5 % on the ln_chain launches between them - equal at C = 256; 16 slower, 2 / 1 mixed: profiles/r06_p_*, r06_q_*)
-  constexpr int GROUP_M = 4;
-  const int per_group = GROUP_M * p.ntn;
-  auto tile_coords = [&](int bid, int& mb, int& nb) {
-    const int group = bid / per_group;
-    const int first_m = group * GROUP_M;
-    const int gsz = min(p.ntm - first_m, GROUP_M);
-    mb = (first_m + (bid % per_group) % gsz) * BM;
-    nb = ((bid % per_group) / gsz) * BN;
-  };
+  // GROUP_M = 4 (8 until round 6, as gemm_f32.hip has it; 4 measures 0.2-0.9 % faster on the lifter's products at C = 512 and, through what they
+  // leave in the caches, 2.5 % on the ln_chain launches between them - equal at C = 256; 16 slower, 2 / 1 mixed: profiles/r06_p_*, r06_q_*)
+  auto tile_coords = [&](int bid, int& mb, int& nb) { grouped_tile_coords<4, BM, BN>(bid, p.ntm, p.ntn, mb, nb); };
   // clock probe (bench.py: the shader clock the chip sustains under this kernel; MI355X runs it power-limited far below 2.4 GHz)
   const bool probe = p.clk != nullptr && tid == 0;
   const long long pc0 = probe ? (long long)__builtin_readcyclecounter() : 0, pw0 = probe ? (long long)wall_clock64() : 0;

@@ -45,12 +45,9 @@ __global__ __launch_bounds__(128 * NWN) void gemm_split_small_kernel(SplitParams
   const int wm = wave & 1, wn = wave >> 1;
 
   // tile of this workgroup: XCD-local chunks of the tile order, row tiles fastest (the row tiles of one W panel share an L2)
-  const int nblk = p.ntm * p.ntn;
-  const int xcd = blockIdx.x & 7, bx = blockIdx.x >> 3;
-  const int cq = nblk >> 3, cr = nblk & 7;
-  const int chunk_start = xcd < cr ? xcd * (cq + 1) : cr * (cq + 1) + (xcd - cr) * cq;
-  if (bx >= cq + (xcd < cr ? 1 : 0)) return;
-  const int t = chunk_start + bx;
+  const XcdChunk chunk = xcd_chunk(p.ntm * p.ntn);
+  if (chunk.bx >= chunk.len) return;
+  const int t = chunk.start + chunk.bx;
   const int m_base = (t % p.ntm) * S_BM, n_base = (t / p.ntm) * S_BN;
 
   // ---- everything the epilogue needs from memory is requested now (in-order completion: it lands before the first k-tile) ----

@@ -74,10 +74,8 @@ __global__ __launch_bounds__(256, 2) void qkv_attention_fused_kernel(QkvAttnPara
   const int n0 = lane & 31, hb = lane >> 5;
 
   // ---- persistent workgroups; XCD x owns a contiguous chunk of tiles, unit v of the chunk = (tile v / 8, head v % 8) ----
-  const int xcd = blockIdx.x & 7, bx = blockIdx.x >> 3, gx = gridDim.x >> 3;
-  const int cq = p.ntiles >> 3, cr = p.ntiles & 7;
-  const int chunk_start = xcd < cr ? xcd * (cq + 1) : cr * (cq + 1) + (xcd - cr) * cq;
-  const int chunk_units = (cq + (xcd < cr ? 1 : 0)) * 8;
+  const XcdChunk chunk = xcd_chunk(p.ntiles);
+  const int chunk_start = chunk.start, chunk_units = chunk.len * 8, bx = chunk.bx, gx = chunk.gx;
   if (bx >= chunk_units) return;
   const int my_units = (chunk_units - bx + gx - 1) / gx;
   const int total = my_units * NK;

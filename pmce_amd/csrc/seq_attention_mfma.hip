@@ -368,12 +368,12 @@ extern "C" int pmce_seq_attention_split_f16(const float* qkv, float* out, int ns
 // well: the library's f16 matrix code stays in the translation units it was in.
 #include "conv.hip"
 
-// ViTPose's attention (sequences of up to 192 tokens, heads of 64 or 80 channels; the same split arithmetic and plane layout) likewise.
+// ViTPose's attention (sequences of up to 192 tokens, heads of 64 or 80 channels; the same split arithmetic and plane layout, and the
+// single-product form of the opt-in f16 mode) likewise.
 #include "vit_attention.hip"
 
-// ViTPose's opt-in single-product f16 mode (one f16 product where the kernels above spend three): its GEMM and its attention.
+// The GEMM of ViTPose's opt-in single-product f16 mode (one f16 product where the kernels above spend three).
 #include "gemm_f16.hip"
-#include "vit_attention_f16.hip"
 
 // The detector's letterbox, upsample and decode kernels (no matrix code; they ride along with the convolution they surround).
 #include "yolo.hip"

@@ -184,41 +184,28 @@ extern "C" int pmce_vitpose_forward(const pmce_vitpose* v, const float* patches,
   // the patch embedding reads the patches through the caller's strides; its NHWC result is the token matrix
   PMCE_TRY(pmce_conv2d_split_f16(patches, sn, sc, sy, sx, n, 3, v->H, v->W, tab[1].dev, tab[1].wscale, tab[2].dev, nullptr, X, C, PATCH, PATCH, PATCH,
                                  PATCH_PAD, 0, stream));
-  if (v->precision == 1) {
-    // The same seven launches per block through the f16 entries: XN, AO and HID hold plain f16 rows in (half of) their fp32-sized slots.
-    auto product16 = [&](const Tensor* w, const Tensor* b, const float* A16, const float* R, float* out, int act, int c_f16) {
-      return pmce_gemm_nt_f16(A16, w->dev, w->wscale, b->dev, R, out, M, w->shape[0], w->shape[1], w->shape[1], w->shape[0], act, c_f16, nullptr,
-                              stream);
-    };
-    auto ln16 = [&](const Tensor* wb, const float* add, float* out1) {
-      return pmce_layernorm_rows_f16(X, M, C, add, N, out1, wb[0].dev, wb[1].dev, LN_EPS, XN, stream);
-    };
-    for (int i = 0; i < v->depth; ++i) {
-      const Tensor* b = tab + 3 + PER_BLOCK * i;
-      PMCE_TRY(i == 0 ? ln16(b + NORM1, tab[0].dev, X) : ln16(b + NORM1, nullptr, nullptr));
-      PMCE_TRY(product16(b + QKV_W, b + QKV_B, XN, nullptr, QKV, 0, 0));
-      PMCE_TRY(pmce_vit_attention_f16(QKV, AO, n, N, C, v->heads, stream));
-      PMCE_TRY(product16(b + PROJ_W, b + PROJ_B, AO, X, X, 0, 0));
-      PMCE_TRY(ln16(b + NORM2, nullptr, nullptr));
-      PMCE_TRY(product16(b + FC1_W, b + FC1_B, XN, nullptr, HID, 1, 1));
-      PMCE_TRY(product16(b + FC2_W, b + FC2_B, HID, X, X, 0, 0));
-    }
-  } else {
-    for (int i = 0; i < v->depth; ++i) {
-      const Tensor* b = tab + 3 + PER_BLOCK * i;
-      // block 0's norm1 also adds the position table and writes the sum back as the residual stream
-      if (i == 0) {
-        PMCE_TRY(ln(b + NORM1, tab[0].dev, X, XN, 1));
-      } else {
-        PMCE_TRY(ln(b + NORM1, nullptr, nullptr, XN, 1));
-      }
-      PMCE_TRY(product(b + QKV_W, b + QKV_B, XN, nullptr, QKV, M, 0, 0));
-      PMCE_TRY(pmce_vit_attention_split_f16(QKV, AO, n, N, C, v->heads, stream));
-      PMCE_TRY(product(b + PROJ_W, b + PROJ_B, AO, X, X, M, 0, 0));
-      PMCE_TRY(ln(b + NORM2, nullptr, nullptr, XN, 1));
-      PMCE_TRY(product(b + FC1_W, b + FC1_B, XN, nullptr, HID, M, 1, 1));
-      PMCE_TRY(product(b + FC2_W, b + FC2_B, HID, X, X, M, 0, 0));
-    }
+  // The blocks' steps through the entries of the network's precision.  XN, AO and HID hold the products' operand form: the planes, or in the
+  // f16 mode plain f16 rows in (half of) their fp32-sized slots.
+  const bool f16 = v->precision == 1;
+  auto block_ln = [&](const Tensor* wb, const float* add, float* out1) {  // LayerNorm of X -> XN in operand form
+    return f16 ? pmce_layernorm_rows_f16(X, M, C, add, N, out1, wb[0].dev, wb[1].dev, LN_EPS, XN, stream) : ln(wb, add, out1, XN, 1);
+  };
+  // out[M][nout] = act(A W^T + bias) (+ R); A in operand form; out fp32, or in operand form (out_operand)
+  auto block_product = [&](const Tensor* w, const Tensor* b, const float* A, const float* R, float* out, int act, int out_operand) {
+    return f16 ? pmce_gemm_nt_f16(A, w->dev, w->wscale, b->dev, R, out, M, w->shape[0], w->shape[1], w->shape[1], w->shape[0], act, out_operand, nullptr,
+                                  stream)
+               : product(w, b, A, R, out, M, act, out_operand);
+  };
+  for (int i = 0; i < v->depth; ++i) {
+    const Tensor* b = tab + 3 + PER_BLOCK * i;
+    // block 0's norm1 also adds the position table and writes the sum back as the residual stream
+    PMCE_TRY(i == 0 ? block_ln(b + NORM1, tab[0].dev, X) : block_ln(b + NORM1, nullptr, nullptr));
+    PMCE_TRY(block_product(b + QKV_W, b + QKV_B, XN, nullptr, QKV, 0, 0));
+    PMCE_TRY(f16 ? pmce_vit_attention_f16(QKV, AO, n, N, C, v->heads, stream) : pmce_vit_attention_split_f16(QKV, AO, n, N, C, v->heads, stream));
+    PMCE_TRY(block_product(b + PROJ_W, b + PROJ_B, AO, X, X, 0, 0));
+    PMCE_TRY(block_ln(b + NORM2, nullptr, nullptr));
+    PMCE_TRY(block_product(b + FC1_W, b + FC1_B, XN, nullptr, HID, 1, 1));
+    PMCE_TRY(block_product(b + FC2_W, b + FC2_B, HID, X, X, 0, 0));
   }
   PMCE_TRY(ln(tail, nullptr, nullptr, XN, 1));
   if (feat) {  // the same rows once more, as fp32 NHWC [n][Hp][Wp][C]

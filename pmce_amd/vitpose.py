@@ -17,7 +17,7 @@ folded into each deconvolution on the host in fp64 (``fold_bn_deconv``), a decon
 
 ``precision="split_f16"`` (the default) runs every product as three f16 products of an exact two-term split, at fp32 accuracy;
 ``precision="f16"`` runs the four products and the attention of every block as one f16 product with fp32 accumulation, the operands
-between them stored as single f16 and the block weights in 2 bytes each (csrc/gemm_f16.hip, vit_attention_f16.hip).  The LayerNorm
+between them stored as single f16 and the block weights in 2 bytes each (csrc/gemm_f16.hip; csrc/vit_attention.hip's single-product form).  The LayerNorm
 statistics, the fp32 residual stream, the patch embedding, last_norm and the whole head are the same in both.  The f16 mode's operators
 are bound one by one as well (``pack_f16``, ``gemm_f16``, ``layernorm_rows(out="f16")``, ``vit_attention(precision="f16")``).
 """
