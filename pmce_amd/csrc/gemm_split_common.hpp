@@ -14,6 +14,8 @@ struct SplitParams {
                         // epilogue multiplies row m by it and adds the bias AFTER the scaling (RS instantiations)
   const float* R;       // residual [M][ldc] or null
   float* C;
+  // (The single-product form, gemm_f16.hip, fills the same fields: A = f16 [M][lda], W = f16 blocked [ceil(N/64)][K/32][64][32], wblk = 1,
+  // C = fp32 or f16 [M][ldc]; lda and ldc count elements of those types.)
   int M, N, K;
   unsigned lda, ldc;
   int ntm, ntn;

@@ -356,24 +356,11 @@ extern "C" int pmce_seq_attention_split_f16(const float* qkv, float* out, int ns
   return PMCE_OK;
 }
 
-// The temporal blocks' fused form (qkv product + this attention in one kernel) is part of this translation unit: it shares split8_fused;
-// its softmax is its own (two sequences per tile, V from the accumulators), not attention_head.
+// Two more files are part of this translation unit, and for one reason: they use split8_fused and attention_head, which are defined above.
+// The temporal blocks' fused form (qkv product + this attention in one kernel) shares split8_fused; its softmax is its own (two sequences
+// per tile, V from the accumulators), not attention_head.
 #include "qkv_attention_fused.hip"
 
 // The same attention at the lifter's other head sizes (16 and 48 channels: chunks of 512 and 768 bytes), and the entry pair that serves
 // every width the model accepts: its own staging around split8_fused and attention_head.
 #include "lifter_attention_mfma.hip"
-
-// The feature extractor's convolution (the same three-product split on the same matrix instruction) and its pools are compiled here as
-// well: the library's f16 matrix code stays in the translation units it was in.
-#include "conv.hip"
-
-// ViTPose's attention (sequences of up to 192 tokens, heads of 64 or 80 channels; the same split arithmetic and plane layout, and the
-// single-product form of the opt-in f16 mode) likewise.
-#include "vit_attention.hip"
-
-// The GEMM of ViTPose's opt-in single-product f16 mode (one f16 product where the kernels above spend three).
-#include "gemm_f16.hip"
-
-// The detector's letterbox, upsample and decode kernels (no matrix code; they ride along with the convolution they surround).
-#include "yolo.hip"

@@ -10,7 +10,7 @@ import vitpose_f16_ref as FR
 
 pytestmark = pytest.mark.gpu
 DEV = "cuda:0"
-TILES = {0: (128, 256, 3), 1: (128, 128, 4), 2: (64, 128, 4)}        # tile -> (BM, BN, NS), csrc/gemm_f16.hip F16Cfg
+TILES = {0: (128, 256, 3), 1: (128, 128, 4), 2: (64, 128, 4)}        # tile -> (BM, BN, NS), csrc/gemm_split_kernel.hpp SplitCfg<.., SINGLE>
 KS = lambda ns: (32, 64, 96, 32 * (ns + 1), 1280, 2048)              # noqa: E731
 MAX_M, MAX_N, MAX_K = 4 * 128 + 1, 5 * 256, 2048
 # what tests/test_gpu_ops.py::test_gemm_nt_split grants a product with the GELU epilogue against fp64 (its `e < 2e-5`)
