@@ -841,6 +841,46 @@ int pmce_vitpose_create_precision(int H, int W, int C, int depth, int heads, int
 int pmce_vitpose_precision(const pmce_vitpose* v);
 
 /* ---------------------------------------------------------------------------------------------------------
+ * The feature extractor's single-product f16 mode (FeatureExtractor(..., precision="f16"); csrc/conv_f16.hpp, compiled with csrc/conv.hip):
+ * the convolution with ONE f16 product per k-tile, fp32 accumulation, f16 maps between the layers.  Opt-in; the default mode keeps its bits.
+ *
+ * pmce_conv_packed_halves: f16 of storage of a packed weight = ceil(Cout / 64) * 64 * Kp, Kp = KH KW Cin rounded up to 64; 0 (and the
+ *   error string) for a bad shape.
+ * pmce_conv_pack_f16: W_oihw[Cout][Cin][KH][KW] fp32 (BatchNorm folded) -> Wp = the blocked layout [ceil(Cout / 64)][Kp / 32][64][32] f16 of
+ *   r16(W[n] * 2^s(n)), k = (ky, kx, cin), zeros for k >= KH KW Cin and for the rows past Cout; wscale[Cout] = 2^-s(n) as
+ *   pmce_conv_pack_split_f16 chooses it.  r16: round to nearest even, |x| < 2^-14 -> 0, beyond f16's range -> inf.
+ * pmce_conv2d_act_f16: v = wscale[co] * sum_k a16[m][k] w16[co][k] + bias[co]; res_after_act == 0: y = act(v + R), 1: y = act(v) + R
+ *   (act = 0 none, 1 ReLU, 2 leaky with slope in [0, 1]); out = y (out_dtype 0: fp32, pitch in floats) or r16(y) (out_dtype 1: f16, pitch
+ *   in halves).  Every epilogue step is one fp32 rounding: the f16 result is r16 of the fp32 result, to the bit.
+ *   x_dtype 1: f16 input taken as it is, x_dtype 0: fp32 input, each value rounded by r16 in the gather; both through the four element
+ *   strides.  R (may be NULL) is f16, row m at R + m * res_pitch halves.  Pitches in Cout..2^24, M = n OH OW < 2^30, offsets < 2^40.
+ *   No alignment is required: an f16 input with sc == 1, Cin % 32 == 0, sn, sy, sx multiples of 8 and a 16-byte aligned base is gathered
+ *   by 16-byte loads, every other by element loads - to the same bits.  A result that is not finite (as f16 where f16 is written: a
+ *   finite fp32 beyond 65504 becomes inf) is reported to the calling thread's overflow sink.  One accumulator per output element takes
+ *   the k-tiles in order: bit-identical whatever n is.
+ * pmce_maxpool3x3s2_nhwc_f16 / pmce_avgpool_nhwc_f16_f32 / pmce_upsample2x_nhwc_f16: the fp32 operators' rules on f16 maps (C and the
+ *   pitches % 4 == 0, 8-byte aligned pointers for the pool and the upsample); the max and the copy are exact, the average is one fp64 sum
+ *   in pixel order rounded once to fp32.  pmce_widen_f16_f32: y[i] = (float)x[i], exact.
+ * pmce_extractor_create_precision: precision 0 (split_f16, what pmce_extractor_create passes) or 1 (f16; anything else PMCE_ERR_ARG naming
+ *   the value).  In f16 mode the weights are packed by pmce_conv_pack_f16 (2 bytes per weight), every map between the layers is f16 and
+ *   pmce_extractor_workspace_bytes_for(e, n) is half of the default's; the features and the taps stay fp32 (the taps widened exactly).
+ *   pmce_extractor_precision reads the mode back (-1 for NULL). */
+long long pmce_conv_packed_halves(int Cout, int Cin, int KH, int KW);
+int pmce_conv_pack_f16(const float* W_oihw, int Cout, int Cin, int KH, int KW, void* Wp, float* wscale, pmce_stream_t stream);
+int pmce_conv2d_act_f16(const void* x, int x_dtype, long long sn, long long sc, long long sy, long long sx, int n, int Cin, int H, int W,
+                        const void* Wp, const float* wscale, const float* bias, const void* R, long long res_pitch, void* out,
+                        long long out_pitch, int out_dtype, int Cout, int KH, int KW, int stride, int pad, int act, float slope,
+                        int res_after_act, pmce_stream_t stream);
+int pmce_maxpool3x3s2_nhwc_f16(const void* x, void* y, int n, int H, int W, int C, pmce_stream_t stream);
+int pmce_avgpool_nhwc_f16_f32(const void* x, float* y, int n, int HW, int C, pmce_stream_t stream);
+int pmce_upsample2x_nhwc_f16(const void* x, long long in_pitch, void* out, long long out_pitch, int n, int H, int W, int C,
+                             pmce_stream_t stream);
+int pmce_widen_f16_f32(const void* x, float* y, long long count, pmce_stream_t stream);
+int pmce_extractor_create_precision(int precision, pmce_extractor** out);
+int pmce_extractor_precision(const pmce_extractor* e);
+size_t pmce_extractor_workspace_bytes_for(const pmce_extractor* e, int n);
+
+/* ---------------------------------------------------------------------------------------------------------
  * The tracker's detector: YOLOv3 as the reference calls it (main/run_demo.py:199-215: MPT(detector_type='yolo', yolo_img_size=416)),
  * video frames -> box predictions (csrc/conv.hip, csrc/yolo.hip, csrc/yolo.cpp).  The structure is the published yolov3.cfg's and that of
  * the PyTorch-YOLOv3 lineage; no tensor was recorded from the yolov3 or multi_person_tracker packages.  Non-maximum suppression and SORT follow below
@@ -895,6 +935,13 @@ int pmce_letterbox_u8_f32(const unsigned char* frames, int n_frames, int height,
                           const int* frame_index, int n_jobs, int S, int swap_rb, const float* table, float pad_value, float* out,
                           pmce_stream_t stream);
 int pmce_yolo_create(const int* table, int n_layers, const float* anchors18, int num_classes, pmce_yolo** out);
+/* pmce_yolo_create_precision: pmce_yolo_create with `precision` 0 (split_f16, what pmce_yolo_create passes) or 1 (f16; anything else
+ *   PMCE_ERR_ARG naming the value).  In f16 mode the weights are packed by pmce_conv_pack_f16, every map of the workspace is f16 (the
+ *   same plan, its units counted at 2 bytes: pmce_yolo_workspace_bytes is half of the default's), the stem rounds the fp32 images in its
+ *   gather, shortcuts add an f16 residual and the upsample is pmce_upsample2x_nhwc_f16; the three detection maps are written in fp32 by
+ *   their convolutions and decoded by pmce_yolo_decode_f32 as before.  pmce_yolo_precision reads the mode back (-1 for NULL). */
+int pmce_yolo_create_precision(const int* table, int n_layers, const float* anchors18, int num_classes, int precision, pmce_yolo** out);
+int pmce_yolo_precision(const pmce_yolo* y);
 void pmce_yolo_destroy(pmce_yolo* y);
 int pmce_yolo_layer_count(const pmce_yolo* y);
 int pmce_yolo_conv_shape(const pmce_yolo* y, int i, int* shape4);

@@ -170,11 +170,23 @@ PROTOTYPES = {
     "pmce_vit_attention_f16": [_f, _f, _i, _i, _i, _i, _s],
     "pmce_vitpose_create_precision": [_i, _i, _i, _i, _i, _i, _i, _i, _i, C.POINTER(C.c_void_p)],
     "pmce_vitpose_precision": [C.c_void_p],
+    "pmce_conv_packed_halves": [_i, _i, _i, _i],
+    "pmce_conv_pack_f16": [_f, _i, _i, _i, _i, _f, _f, _s],
+    "pmce_conv2d_act_f16": [_f, _i, _l, _l, _l, _l, _i, _i, _i, _i, _f, _f, _f, _f, _l, _f, _l, _i, _i, _i, _i, _i, _i, _i, _fl, _i, _s],
+    "pmce_maxpool3x3s2_nhwc_f16": [_f, _f, _i, _i, _i, _i, _s],
+    "pmce_avgpool_nhwc_f16_f32": [_f, _f, _i, _i, _i, _s],
+    "pmce_upsample2x_nhwc_f16": [_f, _l, _f, _l, _i, _i, _i, _i, _s],
+    "pmce_widen_f16_f32": [_f, _f, _l, _s],
+    "pmce_extractor_create_precision": [_i, C.POINTER(C.c_void_p)],
+    "pmce_extractor_precision": [C.c_void_p],
+    "pmce_extractor_workspace_bytes_for": [C.c_void_p, _i],
     "pmce_conv2d_act_split_f16": [_f, _l, _l, _l, _l, _i, _i, _i, _i, _f, _f, _f, _f, _l, _f, _l, _i, _i, _i, _i, _i, _i, _fl, _i, _s],
     "pmce_upsample2x_nhwc_f32": [_f, _l, _f, _l, _i, _i, _i, _i, _s],
     "pmce_yolo_decode_f32": [_f, _f, _f, C.POINTER(C.c_longlong), C.POINTER(C.c_int), C.POINTER(C.c_float), _i, _i, _i, _f, _s],
     "pmce_letterbox_u8_f32": [_f, _i, _i, _i, C.POINTER(C.c_int), _f, _i, _i, _i, _f, _fl, _f, _s],
     "pmce_yolo_create": [C.POINTER(C.c_int), _i, C.POINTER(C.c_float), _i, C.POINTER(C.c_void_p)],
+    "pmce_yolo_create_precision": [C.POINTER(C.c_int), _i, C.POINTER(C.c_float), _i, _i, C.POINTER(C.c_void_p)],
+    "pmce_yolo_precision": [C.c_void_p],
     "pmce_yolo_destroy": [C.c_void_p],
     "pmce_yolo_layer_count": [C.c_void_p],
     "pmce_yolo_conv_shape": [C.c_void_p, _i, C.POINTER(C.c_int)],
@@ -215,6 +227,8 @@ _RESTYPES = {
     "pmce_extractor_destroy": None,
     "pmce_extractor_conv_name": C.c_char_p,
     "pmce_extractor_workspace_bytes": C.c_size_t,
+    "pmce_extractor_workspace_bytes_for": C.c_size_t,
+    "pmce_conv_packed_halves": C.c_longlong,
     "pmce_vitpose_destroy": None,
     "pmce_vitpose_tensor_name": C.c_char_p,
     "pmce_vitpose_workspace_bytes": C.c_size_t,

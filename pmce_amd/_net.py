@@ -11,6 +11,16 @@ import torch
 from . import _lib
 
 
+PRECISIONS = ("split_f16", "f16")       # the library's precision 0 and 1 (include/pmce_hip.h: pmce_*_create_precision)
+
+
+def check_precision(precision):
+    """-> the library's number of a precision name; any other value raises a ValueError that lists the two choices."""
+    if precision not in PRECISIONS:
+        raise ValueError(f'precision must be "split_f16" or "f16" (got {precision!r})')
+    return PRECISIONS.index(precision)
+
+
 def clean_state_dict(sd, keep=None):
     """The entries of a state dict with an optional ``module.`` prefix stripped and ``num_batches_tracked`` dropped; ``keep(name)``
     filters the stripped names further."""
@@ -97,4 +107,4 @@ class DeviceNetwork:
             bad = ~torch.isfinite(t).reshape(t.shape[0], -1).all(dim=1)
             if bool(bad.any()):
                 raise _lib.PmceError(f"{self.NAME}: {noun} {int(bad.nonzero()[0])} has non-finite {what} (an input that is not finite, or an "
-                                     "activation beyond the f16 range of the split)")
+                                     "activation beyond the f16 range of the matrix operands)")

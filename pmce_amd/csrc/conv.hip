@@ -398,3 +398,6 @@ extern "C" int pmce_avgpool_nhwc_f32(const float* x, float* y, int n, int HW, in
   hipLaunchKernelGGL(avgpool_kernel, dim3((unsigned)(blocks < 65536 ? blocks : 65536)), dim3(256), 0, stream, x, y, n, HW, C);
   return pmce_check_launch("avgpool_nhwc_f32");
 }
+
+// The single-product f16 mode: the same operators on f16 maps, ONE matrix product per k-tile (kernel, layouts and entries there).
+#include "conv_f16.hpp"

@@ -16,6 +16,7 @@ size_t Param::floats() const {
 size_t Param::planes() const {
   if (kind == LINEAR) return align64(((size_t)shape[0] + 63) / 64 * 64 * (size_t)shape[1]);
   if (kind == LINEAR_F16) return align64(((size_t)pmce_gemm_packed_f16_halves(shape[0], shape[1]) + 1) / 2);
+  if (kind == CONV_F16) return align64(((size_t)pmce_conv_packed_halves(shape[0], shape[1], shape[2], shape[3]) + 1) / 2);
   return align64((size_t)pmce_conv_packed_floats(shape[0], shape[1], shape[2], shape[3]));
 }
 
@@ -37,6 +38,8 @@ static int fill(const char* who, const std::vector<Param*>& params, const std::f
       PMCE_TRY(pmce_gemm_pack_split_f16(p.src, p.shape[0], p.shape[1], p.shape[1], p.dev, p.wscale, 1, stream));
     } else if (p.kind == LINEAR_F16) {
       PMCE_TRY(pmce_gemm_pack_f16(p.src, p.shape[0], p.shape[1], p.shape[1], p.dev, p.wscale, stream));
+    } else if (p.kind == CONV_F16) {
+      PMCE_TRY(pmce_conv_pack_f16(p.src, p.shape[0], p.shape[1], p.shape[2], p.shape[3], p.dev, p.wscale, stream));
     } else if (p.kind == CONV) {
       PMCE_TRY(pmce_conv_pack_split_f16(p.src, p.shape[0], p.shape[1], p.shape[2], p.shape[3], p.dev, p.wscale, stream));
     } else if (hipMemcpyAsync(p.dev, p.src, p.floats() * sizeof(float), hipMemcpyDeviceToDevice, stream) != hipSuccess) {

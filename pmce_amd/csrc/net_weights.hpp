@@ -11,8 +11,9 @@
 namespace pmce_net {
 
 // PLAIN: copied as it is; LINEAR: [N][K] packed for the three-product GEMM; CONV: OIHW packed for the convolution;
-// LINEAR_F16: [N][K] packed for pmce_gemm_nt_f16 (one f16 per weight - half of LINEAR's planes), wscale as for LINEAR
-enum Kind { PLAIN, LINEAR, CONV, LINEAR_F16 };
+// LINEAR_F16: [N][K] packed for pmce_gemm_nt_f16 (one f16 per weight - half of LINEAR's planes), wscale as for LINEAR;
+// CONV_F16: OIHW packed for pmce_conv2d_act_f16 (one f16 per weight - half of CONV's planes), wscale as for CONV
+enum Kind { PLAIN, LINEAR, CONV, LINEAR_F16, CONV_F16 };
 
 struct Param {
   Kind kind = PLAIN;
@@ -40,7 +41,7 @@ struct Arena {
 };
 
 // Checks that every src is set (`label(i)` supplies the words in front of "was not set"), allocates the arena, places every parameter,
-// packs (LINEAR, CONV) or copies (PLAIN) it on `stream` in the order of the list, waits - the caller may free its tensors when this
+// packs (LINEAR, CONV and their F16 forms) or copies (PLAIN) it on `stream` in the order of the list, waits - the caller may free its tensors when this
 // returns - and clears every src.  A failure after the allocation frees the arena: the handle stays un-finalized and may try again.
 int finalize(const char* who, const std::vector<Param*>& params, const std::function<std::string(size_t)>& label, Arena& arena, hipStream_t stream);
 

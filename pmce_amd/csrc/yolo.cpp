@@ -51,6 +51,7 @@ struct pmce_yolo {
   int yolo_layer[3];
   int nc = 0;
   long long total_units = 0;
+  int precision = 0;  // 0: the three-product split on fp32 maps; 1: one f16 product on f16 maps (the same plan, 2 bytes per element)
   pmce_net::Arena arena;
 };
 
@@ -75,7 +76,7 @@ int plan(pmce_yolo* y) {
         l.C = l.filters;
         l.ds = (i == 0 ? 1 : L[i - 1].ds) * l.stride;
         PMCE_REQUIRE(l.ds <= 32, "yolo_create: layer %d: the map is smaller than 1/32 of the input", i);
-        l.w = pmce_net::Param(pmce_net::CONV, 4, l.filters, l.cin, l.size, l.size);
+        l.w = pmce_net::Param(y->precision == 1 ? pmce_net::CONV_F16 : pmce_net::CONV, 4, l.filters, l.cin, l.size, l.size);
         l.b = pmce_net::Param(pmce_net::PLAIN, 1, l.filters);
         break;
       }
@@ -245,11 +246,19 @@ int plan(pmce_yolo* y) {
 }  // namespace
 
 extern "C" int pmce_yolo_create(const int* table, int n_layers, const float* anchors18, int num_classes, pmce_yolo** out) {
+  return pmce_yolo_create_precision(table, n_layers, anchors18, num_classes, 0, out);
+}
+
+extern "C" int pmce_yolo_precision(const pmce_yolo* y) { return y ? y->precision : -1; }
+
+extern "C" int pmce_yolo_create_precision(const int* table, int n_layers, const float* anchors18, int num_classes, int precision, pmce_yolo** out) {
   PMCE_REQUIRE(table && anchors18 && out, "yolo_create: null pointer");
+  PMCE_REQUIRE(precision == 0 || precision == 1, "yolo_create: precision must be 0 (split_f16) or 1 (f16) (got %d)", precision);
   PMCE_REQUIRE(n_layers >= 4 && n_layers <= 4096, "yolo_create: the table has 4..4096 layers (got %d)", n_layers);
   PMCE_REQUIRE(num_classes >= 1 && num_classes <= 255, "yolo_create: num_classes must be in 1..255 (got %d)", num_classes);
   pmce_yolo* y = new pmce_yolo();
   y->nc = num_classes;
+  y->precision = precision;
   for (int a = 0; a < 9; ++a)
     for (int k = 0; k < 2; ++k) {
       y->anchors[a][k] = anchors18[2 * a + k];
@@ -326,8 +335,61 @@ extern "C" size_t pmce_yolo_workspace_bytes(const pmce_yolo* y, int n, int S) {
     pmce_set_error("yolo_workspace_bytes: n must be in 1..1024 and the side a multiple of 32 in 32..1024 (got n=%d S=%d)", n, S);
     return 0;
   }
-  return (size_t)n * (size_t)y->total_units * (size_t)(S / 32) * (size_t)(S / 32) * sizeof(float);
+  return (size_t)n * (size_t)y->total_units * (size_t)(S / 32) * (size_t)(S / 32) * (y->precision == 1 ? 2 : sizeof(float));
 }
+
+namespace {
+
+// The launch sequence of a forward on workspace maps of T: float (the three-product convolution) or _Float16 (the single-product one:
+// the stem rounds the fp32 images in its gather, shortcuts add an f16 residual).  The detection maps are the caller's, fp32 in both.
+template <typename T>
+int run_layers(const pmce_yolo* y, const float* images, long long sn, long long sc, long long sy, long long sx, int n, int S,
+               float* const* maps, void* workspace, hipStream_t stream) {
+  constexpr bool F16 = sizeof(T) == 2;
+  T* ws = static_cast<T*>(workspace);
+  const size_t unit = (size_t)n * (size_t)(S / 32) * (size_t)(S / 32);
+  const std::vector<Layer>& L = y->layers;
+  auto at = [&](int i) -> T* { return ws + unit * (size_t)y->bufs[L[i].buf].offset + L[i].coff; };  // first channel of layer i's workspace map
+  // the convolution of layer ci, its result (and an optional residual) where layer `dst` lives
+  auto conv = [&](int ci, int dst, int res) {
+    const Layer& c = L[ci];
+    const Layer& o = L[dst];
+    const void* x = images;
+    long long xn = sn, xc = sc, xy = sy, xx = sx;
+    int side = S;
+    if (ci > 0) {
+      const Layer& in = L[ci - 1];
+      side = S / in.ds;
+      x = at(ci - 1);
+      xc = 1; xx = in.pitch; xy = (long long)side * in.pitch; xn = (long long)side * side * in.pitch;
+    }
+    const bool det = o.buf == BUF_CALLER;
+    void* out = det ? static_cast<void*>(maps[o.det] + o.coff) : static_cast<void*>(at(dst));
+    const void* r = res >= 0 ? at(res) : nullptr;
+    const long long ldr = res >= 0 ? L[res].pitch : 0;
+    const int pad = (c.size - 1) / 2, act = c.leaky ? 2 : 0;
+    if constexpr (F16)
+      return pmce_conv2d_act_f16(x, ci > 0 ? 1 : 0, xn, xc, xy, xx, n, c.cin, side, side, c.w.dev, c.w.wscale, c.b.dev, r, ldr, out, o.pitch,
+                                 det ? 0 : 1, c.filters, c.size, c.size, c.stride, pad, act, LEAKY_SLOPE, 1, stream);
+    else
+      return pmce_conv2d_act_split_f16(static_cast<const float*>(x), xn, xc, xy, xx, n, c.cin, side, side, c.w.dev, c.w.wscale, c.b.dev,
+                                       static_cast<const float*>(r), ldr, static_cast<float*>(out), o.pitch, c.filters, c.size, c.size, c.stride,
+                                       pad, act, LEAKY_SLOPE, 1, stream);
+  };
+  for (int i = 0; i < (int)L.size(); ++i) {
+    const Layer& l = L[i];
+    if (l.kind == K_CONV && l.fused_into < 0) PMCE_TRY(conv(i, i, -1));
+    else if (l.kind == K_SHORTCUT) PMCE_TRY(conv(i - 1, i, l.src0));
+    else if (l.kind == K_UPSAMPLE) {
+      const Layer& in = L[i - 1];
+      if constexpr (F16) PMCE_TRY(pmce_upsample2x_nhwc_f16(at(i - 1), in.pitch, at(i), l.pitch, n, S / in.ds, S / in.ds, l.C, stream));
+      else PMCE_TRY(pmce_upsample2x_nhwc_f32(at(i - 1), in.pitch, at(i), l.pitch, n, S / in.ds, S / in.ds, l.C, stream));
+    }
+  }
+  return PMCE_OK;
+}
+
+}  // namespace
 
 extern "C" int pmce_yolo_forward(const pmce_yolo* y, const float* images, long long sn, long long sc, long long sy, long long sx, int n, int S,
                                  float* map0, float* map1, float* map2, float* rows, void* workspace, size_t workspace_bytes,
@@ -337,40 +399,10 @@ extern "C" int pmce_yolo_forward(const pmce_yolo* y, const float* images, long l
   PMCE_REQUIRE(n >= 1 && n <= 1024 && S >= 32 && S <= 1024 && S % 32 == 0,
                "yolo_forward: n must be in 1..1024 and the side a multiple of 32 in 32..1024 (got n=%d S=%d)", n, S);
   PMCE_TRY(pmce_net::check_workspace("yolo_forward", workspace, workspace_bytes, pmce_yolo_workspace_bytes(y, n, S)));
-  float* ws = static_cast<float*>(workspace);
   float* maps[3] = {map0, map1, map2};
-  const size_t unit = (size_t)n * (size_t)(S / 32) * (size_t)(S / 32);
   const std::vector<Layer>& L = y->layers;
-  auto at = [&](int i) -> float* {  // first channel of layer i's map
-    const Layer& l = L[i];
-    return (l.buf == BUF_CALLER ? maps[l.det] : ws + unit * (size_t)y->bufs[l.buf].offset) + l.coff;
-  };
-  // the convolution of layer ci, its result (and an optional residual) where layer `dst` lives
-  auto conv = [&](int ci, int dst, int res) {
-    const Layer& c = L[ci];
-    const Layer& o = L[dst];
-    const float* x = images;
-    long long xn = sn, xc = sc, xy = sy, xx = sx;
-    int side = S;
-    if (ci > 0) {
-      const Layer& in = L[ci - 1];
-      side = S / in.ds;
-      x = at(ci - 1);
-      xc = 1; xx = in.pitch; xy = (long long)side * in.pitch; xn = (long long)side * side * in.pitch;
-    }
-    return pmce_conv2d_act_split_f16(x, xn, xc, xy, xx, n, c.cin, side, side, c.w.dev, c.w.wscale, c.b.dev, res >= 0 ? at(res) : nullptr,
-                                     res >= 0 ? L[res].pitch : 0, at(dst), o.pitch, c.filters, c.size, c.size, c.stride, (c.size - 1) / 2,
-                                     c.leaky ? 2 : 0, LEAKY_SLOPE, 1, stream);
-  };
-  for (int i = 0; i < (int)L.size(); ++i) {
-    const Layer& l = L[i];
-    if (l.kind == K_CONV && l.fused_into < 0) PMCE_TRY(conv(i, i, -1));
-    else if (l.kind == K_SHORTCUT) PMCE_TRY(conv(i - 1, i, l.src0));
-    else if (l.kind == K_UPSAMPLE) {
-      const Layer& in = L[i - 1];
-      PMCE_TRY(pmce_upsample2x_nhwc_f32(at(i - 1), in.pitch, at(i), l.pitch, n, S / in.ds, S / in.ds, l.C, stream));
-    }
-  }
+  PMCE_TRY(y->precision == 1 ? run_layers<_Float16>(y, images, sn, sc, sy, sx, n, S, maps, workspace, stream)
+                             : run_layers<float>(y, images, sn, sc, sy, sx, n, S, maps, workspace, stream));
   if (!rows) return PMCE_OK;
   long long pitches[3];
   int grids[3];

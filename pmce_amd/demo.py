@@ -7,7 +7,8 @@ in, what the demo saves per person out - ``pred_cam``, ``mesh``, ``bboxes`` (``f
     video = demo.render_tracklets(outs, frames_u8, (1920, 1080), frame_ids=ids, renderer=render.Renderer(faces, (1920, 1080)))
     outs = demo.run_video(model, frames_u8, [(kp_a[N,17,3], ids_a), (kp_b, ids_b)], extractor, img_wh=(1920, 1080))   # crops included
     tracklets = demo.pose_tracklets(frames_u8, [(boxes_a[N,4], ids_a), (boxes_b, ids_b)], pose2d.TopDownPose(vitpose_net))   # boxes -> run_video's tracklets
-                                     # (vitpose_net in either precision, vitpose.ViTPose(..., precision="split_f16" | "f16"): no change here)
+                                     # (vitpose_net in either precision, vitpose.ViTPose(..., precision="split_f16" | "f16"): no change here;
+                                     #  likewise the extractor and the tracker's detector built with precision="f16": taken as they are)
     boxes, person_ids = demo.track_video(frames_u8, tracker.Tracker(yolo_net))                  # frames -> pose_tracklets' tracklets
     outs = demo.run_frames(model, frames_u8, tracker.Tracker(yolo_net), pose, extractor, img_wh=(1920, 1080))   # the demo up to rendering
     frames_u8, (w, h), names = demo.load_frames("video_frames/")                               # a folder of .jpg files, decoded on the device

@@ -6,6 +6,12 @@
     feats = ext(patches)                                                                   # fp32 [n,2048] on the patches' device
     feats, taps = ext.forward(patches, taps=("layer1", "layer4"))                          # + the named stage outputs, NCHW
     out = demo.run_video(model, frames, tracklets, ext, img_wh)                            # the extractor is a plain callable
+    ext = FeatureExtractor.from_state_dict(sd, device, precision="f16")                    # opt-in: every convolution as ONE f16 product
+
+``precision="split_f16"`` (the default) runs every convolution as three f16 products of an exact two-term split on fp32 maps, at fp32
+accuracy; ``precision="f16"`` runs it as one f16 product with fp32 accumulation on f16 maps (csrc/conv_f16.hpp): half the weight and
+workspace memory, the accuracy of f16 operands.  Features and taps are fp32 in both.  The f16 operators are bound one by one as well
+(``pack_conv_f16``, ``conv2d_f16``, ``maxpool3x3s2`` / ``avgpool`` on f16 tensors).
 
 Eval-mode BatchNorm is folded into each convolution on the host in fp64 (``fold_bn``); the device sees 53 convolutions with a bias.
 The operators are also bound one by one (``pack_conv``, ``conv2d``, ``maxpool3x3s2``, ``avgpool``) on NHWC tensors.  There is no
@@ -19,7 +25,7 @@ from collections import OrderedDict
 import torch
 
 from . import _lib
-from ._net import DeviceNetwork, clean_state_dict, take_tensors
+from ._net import PRECISIONS, DeviceNetwork, check_precision, clean_state_dict, take_tensors
 
 BN_EPS = 1e-5
 SIDE = 224
@@ -123,21 +129,98 @@ def conv2d(x, layout, planes, wscale, weight_shape, bias=None, residual=None, st
     return out
 
 
+def _f32_or_f16(x, what):
+    if x.dtype not in (torch.float32, torch.float16):
+        raise ValueError(f"{what}: the input must be float32 or float16 (got {x.dtype})")
+    return x.dtype == torch.float16
+
+
 def maxpool3x3s2(x):
-    """contiguous NHWC [n,H,W,C] -> [n,(H-1)//2+1,(W-1)//2+1,C]: nn.MaxPool2d(3, 2, 1)."""
+    """contiguous NHWC [n,H,W,C], fp32 or f16 -> [n,(H-1)//2+1,(W-1)//2+1,C] of the same dtype: nn.MaxPool2d(3, 2, 1)."""
     n, h, w, c = x.shape
-    out = torch.empty(n, (h - 1) // 2 + 1, (w - 1) // 2 + 1, c, device=x.device, dtype=torch.float32)
+    fn = _lib.load().pmce_maxpool3x3s2_nhwc_f16 if _f32_or_f16(x, "maxpool3x3s2") else _lib.load().pmce_maxpool3x3s2_nhwc_f32
+    out = torch.empty(n, (h - 1) // 2 + 1, (w - 1) // 2 + 1, c, device=x.device, dtype=x.dtype)
     with torch.cuda.device(x.device):
-        _lib.check(_lib.load().pmce_maxpool3x3s2_nhwc_f32(_lib.ptr(x), _lib.ptr(out), n, h, w, c, _lib.current_stream()), "maxpool3x3s2")
+        _lib.check(fn(_lib.ptr(x), _lib.ptr(out), n, h, w, c, _lib.current_stream()), "maxpool3x3s2")
     return out
 
 
 def avgpool(x):
-    """contiguous NHWC [n,H,W,C] -> [n,C]: the mean over the pixels."""
+    """contiguous NHWC [n,H,W,C], fp32 or f16 -> fp32 [n,C]: the mean over the pixels."""
     n, h, w, c = x.shape
+    fn = _lib.load().pmce_avgpool_nhwc_f16_f32 if _f32_or_f16(x, "avgpool") else _lib.load().pmce_avgpool_nhwc_f32
     out = torch.empty(n, c, device=x.device, dtype=torch.float32)
     with torch.cuda.device(x.device):
-        _lib.check(_lib.load().pmce_avgpool_nhwc_f32(_lib.ptr(x), _lib.ptr(out), n, h * w, c, _lib.current_stream()), "avgpool")
+        _lib.check(fn(_lib.ptr(x), _lib.ptr(out), n, h * w, c, _lib.current_stream()), "avgpool")
+    return out
+
+
+# ---- the single-product f16 mode's operators ----
+
+ACTS = {"none": 0, "relu": 1, "leaky": 2}
+
+
+def pack_conv_f16(weight_oihw):
+    """fp32 device [Cout,Cin,KH,KW] (BatchNorm folded) -> (packed f16 weights, wscale[Cout]) for ``conv2d_f16``."""
+    w = weight_oihw.contiguous()
+    co, ci, kh, kw = (int(s) for s in w.shape)
+    lib = _lib.load()
+    halves = lib.pmce_conv_packed_halves(co, ci, kh, kw)
+    if halves <= 0:
+        raise _lib.PmceError(_lib.last_error())
+    packed = torch.empty(halves, device=w.device, dtype=torch.float16)
+    wscale = torch.empty(co, device=w.device, dtype=torch.float32)
+    with torch.cuda.device(w.device):
+        _lib.check(lib.pmce_conv_pack_f16(_lib.ptr(w), co, ci, kh, kw, _lib.ptr(packed), _lib.ptr(wscale), _lib.current_stream()), "conv_pack_f16")
+    return packed, wscale
+
+
+def conv2d_f16(x, layout, packed, wscale, weight_shape, bias=None, residual=None, stride=1, pad=0, act="none", slope=0.0,
+               res_after_act=False, out=None, out_dtype=torch.float16):
+    """x: a device tensor in ``layout`` "nhwc" or "nchw", f16 (taken as it is) or fp32 (rounded to f16 in the gather), any strides - a
+    channel slice of a wider NHWC buffer included; -> NHWC [n,OH,OW,Cout] of ``out_dtype`` (f16 or fp32), or written into ``out``, an
+    NHWC view with channel stride 1 whose pixel pitch may be that of a wider buffer.  residual: f16 NHWC like the result, likewise a view."""
+    co, ci, kh, kw = weight_shape
+    if layout == "nhwc":
+        n, h, w, c = x.shape
+        sn, sy, sx, sc = x.stride()
+    elif layout == "nchw":
+        n, c, h, w = x.shape
+        sn, sc, sy, sx = x.stride()
+    else:
+        raise ValueError(f"layout must be 'nhwc' or 'nchw' (got {layout!r})")
+    if c != ci:
+        raise ValueError(f"conv2d_f16: the input has {c} channels, the weight reads {ci}")
+    x16 = _f32_or_f16(x, "conv2d_f16")
+    if act not in ACTS:
+        raise ValueError(f"conv2d_f16: act must be one of {tuple(ACTS)} (got {act!r})")
+    oh, ow = (h + 2 * pad - kh) // stride + 1, (w + 2 * pad - kw) // stride + 1
+    if out is None:
+        out = torch.empty(n, oh, ow, co, device=x.device, dtype=out_dtype)
+    _f32_or_f16(out, "conv2d_f16 (out)")
+
+    def pitch(t, what):          # an NHWC view: channel stride 1, pixels one pitch apart in the order (image, row, column)
+        p = t.stride(2)
+        if ow == 1:              # (the stride of a dimension of size 1 says nothing)
+            p = t.stride(1) if oh > 1 else t.stride(0) if n > 1 else co
+        if (tuple(t.shape) != (n, oh, ow, co) or (co > 1 and t.stride(3) != 1) or (oh > 1 and t.stride(1) != ow * p)
+                or (n > 1 and t.stride(0) != oh * ow * p)):
+            raise ValueError(f"conv2d_f16: {what} must be an NHWC view {(n, oh, ow, co)} with one pixel pitch (got {tuple(t.shape)}, strides "
+                             f"{tuple(t.stride())})")
+        return p
+
+    ldo = pitch(out, "out")
+    ldr = 0
+    if residual is not None:
+        if residual.dtype != torch.float16:
+            raise ValueError(f"conv2d_f16: the residual must be float16 (got {residual.dtype})")
+        ldr = pitch(residual, "the residual")
+    with torch.cuda.device(x.device):
+        _lib.check(_lib.load().pmce_conv2d_act_f16(
+            C.c_void_p(x.data_ptr()), 1 if x16 else 0, sn, sc, sy, sx, n, ci, h, w, _lib.ptr(packed), _lib.ptr(wscale), _lib.ptr(bias),
+            None if residual is None else C.c_void_p(residual.data_ptr()), ldr, C.c_void_p(out.data_ptr()), ldo,
+            1 if out.dtype == torch.float16 else 0, co, kh, kw, stride, pad, ACTS[act], float(slope), 1 if res_after_act else 0,
+            _lib.current_stream()), "conv2d_act_f16")
     return out
 
 
@@ -147,15 +230,17 @@ def avgpool(x):
 
 class FeatureExtractor(DeviceNetwork):
     """SPIN's ResNet-50 backbone as HIP convolutions.  ``max_batch``: patches per launch sequence (the workspace, 12.8 MB per patch, is
-    allocated once for it and reused); ``check_finite``: raise when a feature is not finite, naming the first such patch."""
+    allocated once for it and reused; 6.4 MB in f16 mode); ``check_finite``: raise when a feature is not finite, naming the first such
+    patch; ``precision``: "split_f16" (default) or "f16" (the module's docstring), read back as ``ext.precision``."""
     NAME = "extractor"
     MAX_BATCH = 4096
 
-    def __init__(self, folded, device, max_batch: int = 64, check_finite: bool = True):
+    def __init__(self, folded, device, max_batch: int = 64, check_finite: bool = True, precision: str = "split_f16"):
+        mode = check_precision(precision)            # before any device work
         super().__init__(device, max_batch, check_finite)
         lib = _lib.load()
         h = C.c_void_p()
-        _lib.check(lib.pmce_extractor_create(C.byref(h)), "extractor_create")
+        _lib.check(lib.pmce_extractor_create_precision(mode, C.byref(h)), "extractor_create")
         self._h = h
 
         def uploads():
@@ -167,8 +252,14 @@ class FeatureExtractor(DeviceNetwork):
 
         self._finalize(uploads())
 
+    @property
+    def precision(self):
+        """"split_f16" or "f16", as the library's handle reports it."""
+        return PRECISIONS[_lib.load().pmce_extractor_precision(self._h)]
+
     @classmethod
     def from_state_dict(cls, sd, device="cuda", **kw):
+        check_precision(kw.get("precision", "split_f16"))
         t = select_state_dict(sd)
         folded = {ck: fold_bn(t[ck + ".weight"], t[bk + ".weight"], t[bk + ".bias"], t[bk + ".running_mean"], t[bk + ".running_var"])
                   for ck, bk, _ in conv_table()}
@@ -177,6 +268,7 @@ class FeatureExtractor(DeviceNetwork):
     @classmethod
     def from_checkpoint(cls, path, device="cuda", **kw):
         """``torch.load(path)['model']``, as main/run_demo.py:250-251 reads the SPIN checkpoint."""
+        check_precision(kw.get("precision", "split_f16"))
         ckpt = torch.load(path, map_location="cpu", weights_only=False)
         if not hasattr(ckpt, "keys") or "model" not in ckpt:
             raise ValueError(f"{path}: the checkpoint has no 'model' entry")
@@ -195,7 +287,7 @@ class FeatureExtractor(DeviceNetwork):
                    for t in taps}
         lib = _lib.load()
         with torch.cuda.device(self.device):
-            ws = self._workspace(lib.pmce_extractor_workspace_bytes(self.max_batch)) if n else None
+            ws = self._workspace(lib.pmce_extractor_workspace_bytes_for(self._h, self.max_batch)) if n else None
             for i0, m, xi, (sn, sc, sy, sx) in self._chunks(patches):
                 tp = [C.c_void_p(tap_out[t][i0:].data_ptr()) if t in tap_out else None for t in TAPS]
                 _lib.check(lib.pmce_extractor_forward(self._h, C.c_void_p(xi.data_ptr()), sn, sc, sy, sx, C.c_void_p(feats[i0:].data_ptr()), m,

@@ -20,7 +20,7 @@ import numpy as np
 import torch
 
 from . import _lib, ops
-from ._net import clean_state_dict, take_tensors
+from ._net import check_precision, clean_state_dict, take_tensors
 from .extractor import FEAT_DIM, FeatureExtractor
 
 NPOSE, NSHAPE, NCAM = 144, 10, 3
@@ -246,15 +246,23 @@ class HMR:
 
     @classmethod
     def from_state_dict(cls, sd, device="cuda", smpl=None, n_iter=3, **extractor_kw):
+        """``extractor_kw`` go to the backbone: ``precision="split_f16"`` (default) or ``"f16"`` (extractor.py), ``max_batch``, ``check_finite``."""
+        check_precision(extractor_kw.get("precision", "split_f16"))         # before any device work
         return cls(FeatureExtractor.from_state_dict(sd, device, **extractor_kw), RegressorHead.from_state_dict(sd, device, n_iter), smpl)
 
     @classmethod
     def from_checkpoint(cls, path, device="cuda", smpl=None, n_iter=3, **extractor_kw):
         """``torch.load(path)['model']``, as main/run_demo.py:250-251 reads the SPIN checkpoint."""
+        check_precision(extractor_kw.get("precision", "split_f16"))
         ckpt = torch.load(path, map_location="cpu", weights_only=False)
         if not hasattr(ckpt, "keys") or "model" not in ckpt:
             raise ValueError(f"{path}: the checkpoint has no 'model' entry")
         return cls.from_state_dict(ckpt["model"], device, smpl, n_iter, **extractor_kw)
+
+    @property
+    def precision(self):
+        """The backbone's mode ("split_f16" or "f16"); the head is fp32 in both."""
+        return self.extractor.precision
 
     def feature_extractor(self, patches):
         return self.extractor(patches)

@@ -5,7 +5,8 @@ call - for every person of every frame, on frames that are already on the device
     patches, centre_scale, status = pose2d.pose_patches(frames[F,H,W,3] uint8, frame_index[N], boxes[N,4])   # fp32 [N,3,256,192]
     keypoints = pose2d.decode_heatmaps(heat[N,17,64,48], centre_scale, heat_flipped=...)                     # fp32 [N,17,3]
     pose = pose2d.TopDownPose(net)                       # net = vitpose.ViTPose...; flip_test=True as the demo's config has it
-                                                         # (a network built with precision="f16" is served as it is: nothing here changes)
+                                                         # (a network built with precision="f16" is served as it is: nothing here changes,
+                                                         #  nor for the boxes of an f16 detector or the patches an f16 extractor reads)
     keypoints, status = pose(frames, frame_index, boxes) # (x, y, score) in frame pixels, ready for crops.tracklet_boxes / demo.run_video
 
 ``pose_patches`` is ``TopDownAffine`` with ``use_udp`` at rotation 0 (``_box2cs`` included), ``decode_heatmaps`` the flip test's average

@@ -6,6 +6,7 @@ the detector's rows on (main/run_demo.py:199-215) - non-maximum suppression, SOR
     tracks, track_count, status = tracker.sort_tracks(ppl, ppl_count)     # fp64 [F, 64, 5] = (x1, y1, x2, y2, id) in report order
     tracklets, ids = tracker.tracklet_records(tracks, track_count)        # [(boxes fp64 [N_i, 4] cxcywh, frame_ids int64 [N_i]), ...]
     tracklets, ids = tracker.Tracker(yolo.YOLOv3.from_darknet_weights(path))(frames_u8)      # the chain; demo.pose_tracklets takes it
+                                     # (a detector built with precision="f16" is taken as it is: its rows are fp32 too, nothing here changes)
 
 The algorithms are written from the published texts (the PyTorch-YOLOv3 lineage's ``non_max_suppression``, Bewley's ``sort.py`` over
 filterpy's ``KalmanFilter`` formulas, multi_person_tracker's ``run_tracker`` and ``prepare_output_tracks``); no value was recorded from

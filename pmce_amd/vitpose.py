@@ -30,7 +30,7 @@ from collections import OrderedDict
 import torch
 
 from . import _lib
-from ._net import DeviceNetwork, clean_state_dict, take_tensors
+from ._net import PRECISIONS, DeviceNetwork, check_precision, clean_state_dict, take_tensors  # noqa: F401  (the precision check is shared)
 
 BN_EPS = 1e-5
 LN_EPS = 1e-6
@@ -39,16 +39,6 @@ IMG_SIZE = (256, 192)
 MAX_TOKENS = 192
 MAX_BATCH = 256
 PREFIXES = ("backbone.", "keypoint_head.")
-PRECISIONS = ("split_f16", "f16")       # the library's precision 0 and 1 (include/pmce_hip.h: pmce_vitpose_create_precision)
-
-
-def check_precision(precision):
-    """-> the library's number of a precision name; any other value raises a ValueError that lists the two choices."""
-    if precision not in PRECISIONS:
-        raise ValueError(f'precision must be "split_f16" or "f16" (got {precision!r})')
-    return PRECISIONS.index(precision)
-
-
 # ----------------------------------------------------------------------------------------------
 # the state dict
 # ----------------------------------------------------------------------------------------------

@@ -6,6 +6,11 @@
     images, (pad_x, pad_y, ratio) = letterbox(frames_u8[F,H,W,3], frame_index[n], size=416)      # fp32 [n,3,416,416] in [0, 1]
     rows = det(images)                                                   # fp32 [n, 10647, 85] = (cx, cy, w, h, conf, 80 classes)
     rows, maps = det.forward(images, return_maps=True)                   # + the three raw detection maps, NCHW views
+    det = YOLOv3.from_state_dict(sd, device, precision="f16")            # opt-in: every convolution as ONE f16 product on f16 maps
+
+``precision="split_f16"`` (the default) runs every convolution as three f16 products of an exact two-term split on fp32 maps;
+``precision="f16"`` runs it as one f16 product with fp32 accumulation on f16 maps (csrc/conv_f16.hpp; half the weight and workspace
+memory, the accuracy of f16 operands).  The three detection maps and the rows are fp32 in both.
 
 The structure is the published ``yolov3.cfg``'s and that of the PyTorch-YOLOv3 lineage; no tensor was recorded from the ``yolov3`` or
 ``multi_person_tracker`` packages.  Non-maximum suppression, SORT and the tracklet records are ``pmce_amd/tracker.py``.  There is no fallback and no
@@ -20,9 +25,9 @@ import numpy as np
 import torch
 
 from . import _lib
-from ._net import DeviceNetwork, clean_state_dict, take_tensors
+from ._net import PRECISIONS, DeviceNetwork, check_precision, clean_state_dict, take_tensors
 from .crops import CHANNEL_ORDERS, MAX_DIM, _device_of
-from .extractor import BN_EPS, fold_bn
+from .extractor import BN_EPS, conv2d_f16, fold_bn
 
 ANCHORS = ((10, 13), (16, 30), (33, 23), (30, 61), (62, 45), (59, 119), (116, 90), (156, 198), (373, 326))
 KINDS = ("convolutional", "shortcut", "route", "upsample", "yolo")
@@ -269,17 +274,30 @@ def conv2d_act(x, planes, wscale, weight_shape, bias=None, residual=None, stride
     return out
 
 
+def conv2d_act_f16(x, packed, wscale, weight_shape, bias=None, residual=None, stride=1, pad=0, act="none", slope=LEAKY_SLOPE,
+                   residual_after_act=False, out=None, out_dtype=torch.float16):
+    """``conv2d_act`` in the single-product f16 mode (``extractor.pack_conv_f16`` packs): x NHWC f16 (or fp32, rounded in the gather), any
+    pitch; the residual f16; the result f16 or fp32 (``out_dtype``, or the dtype of ``out``) - all three may be channel slices."""
+    return conv2d_f16(x, "nhwc", packed, wscale, weight_shape, bias, residual, stride, pad, act, slope, residual_after_act, out, out_dtype)
+
+
 def upsample2x(x, out=None):
-    """contiguous NHWC [n,H,W,C] -> nearest x2 [n,2H,2W,C]; ``out`` may be a channel slice of a wider NHWC buffer."""
+    """contiguous NHWC [n,H,W,C], fp32 or f16 -> nearest x2 [n,2H,2W,C] of the same dtype; ``out`` may be a channel slice of a wider NHWC
+    buffer."""
     n, h, w, c = x.shape
+    if x.dtype not in (torch.float32, torch.float16):
+        raise ValueError(f"upsample2x: x must be float32 or float16 (got {x.dtype})")
     if out is None:
-        out = torch.empty(n, 2 * h, 2 * w, c, device=x.device, dtype=torch.float32)
+        out = torch.empty(n, 2 * h, 2 * w, c, device=x.device, dtype=x.dtype)
+    if out.dtype != x.dtype:
+        raise ValueError(f"upsample2x: out must have the dtype of x (got {out.dtype} for {x.dtype})")
     if tuple(out.shape) != (n, 2 * h, 2 * w, c) or out.stride(3) != 1 or out.stride(1) != 2 * w * out.stride(2) or \
             out.stride(0) != 4 * h * w * out.stride(2) or not x.is_contiguous():
         raise ValueError(f"upsample2x: x must be contiguous and out NHWC {(n, 2 * h, 2 * w, c)} with rows one pitch apart")
+    lib = _lib.load()
+    fn, what = (lib.pmce_upsample2x_nhwc_f16, "upsample2x_nhwc_f16") if x.dtype == torch.float16 else (lib.pmce_upsample2x_nhwc_f32, "upsample2x_nhwc_f32")
     with torch.cuda.device(x.device):
-        _lib.check(_lib.load().pmce_upsample2x_nhwc_f32(_lib.ptr(x), c, C.c_void_p(out.data_ptr()), out.stride(2), n, h, w, c,
-                                                        _lib.current_stream()), "upsample2x_nhwc_f32")
+        _lib.check(fn(_lib.ptr(x), c, C.c_void_p(out.data_ptr()), out.stride(2), n, h, w, c, _lib.current_stream()), what)
     return out
 
 
@@ -415,30 +433,32 @@ class Plan:
             lib.pmce_yolo_destroy(h)
 
 
-def _create(spec):
+def _create(spec, precision=0):
     table = np.ascontiguousarray(layer_table(spec))
     anchors = spec["anchors"]
     if len(anchors) != 9:
         raise ValueError(f"a spec has nine anchors (got {len(anchors)})")
     anc = (C.c_float * 18)(*[float(v) for a in anchors for v in a])
     h = C.c_void_p()
-    _lib.check(_lib.load().pmce_yolo_create(table.ctypes.data_as(C.POINTER(C.c_int)), table.shape[0], anc, int(spec["num_classes"]), C.byref(h)),
-               "yolo_create")
+    _lib.check(_lib.load().pmce_yolo_create_precision(table.ctypes.data_as(C.POINTER(C.c_int)), table.shape[0], anc, int(spec["num_classes"]),
+                                                      int(precision), C.byref(h)), "yolo_create")
     return h
 
 
 class YOLOv3(DeviceNetwork):
     """A darknet-style detector as HIP convolutions.  ``max_batch``: images per launch sequence (the workspace is allocated for it and
-    the largest side seen, and reused); ``check_finite``: raise when a row is not finite, naming the first such image."""
+    the largest side seen, and reused); ``check_finite``: raise when a row is not finite, naming the first such image; ``precision``:
+    "split_f16" (default) or "f16" (the module's docstring), read back as ``det.precision``."""
     NAME = "yolo"
     MAX_BATCH = 1024
 
-    def __init__(self, folded, device, spec=None, max_batch: int = 12, check_finite: bool = True):
+    def __init__(self, folded, device, spec=None, max_batch: int = 12, check_finite: bool = True, precision: str = "split_f16"):
+        mode = check_precision(precision)            # before any device work
         super().__init__(device, max_batch, check_finite)
         self.spec = spec if spec is not None else yolov3_spec()
         self.num_classes = int(self.spec["num_classes"])
         lib = _lib.load()
-        self._h = h = _create(self.spec)
+        self._h = h = _create(self.spec, mode)
 
         def uploads():
             shape = (C.c_int * 4)()
@@ -451,13 +471,20 @@ class YOLOv3(DeviceNetwork):
 
         self._finalize(uploads())
 
+    @property
+    def precision(self):
+        """"split_f16" or "f16", as the library's handle reports it."""
+        return PRECISIONS[_lib.load().pmce_yolo_precision(self._h)]
+
     @classmethod
     def from_state_dict(cls, sd, device="cuda", spec=None, **kw):
+        check_precision(kw.get("precision", "split_f16"))
         spec = spec if spec is not None else yolov3_spec()
         return cls(fold_state_dict(select_state_dict(sd, spec), spec), device, spec=spec, **kw)
 
     @classmethod
     def from_darknet_weights(cls, path, device="cuda", spec=None, **kw):
+        check_precision(kw.get("precision", "split_f16"))
         spec = spec if spec is not None else yolov3_spec()
         return cls.from_state_dict(read_darknet_weights(path, spec), device, spec=spec, **kw)
 
@@ -465,6 +492,7 @@ class YOLOv3(DeviceNetwork):
     def from_checkpoint(cls, path, device="cuda", spec=None, **kw):
         """A ``.weights`` file is read as darknet's; anything else as ``torch.load(path)`` holding a state dict (or one under
         'state_dict' / 'model')."""
+        check_precision(kw.get("precision", "split_f16"))
         if str(path).endswith(".weights"):
             return cls.from_darknet_weights(path, device, spec=spec, **kw)
         ckpt = torch.load(path, map_location="cpu", weights_only=True)

@@ -7,11 +7,17 @@ the padded K), and - from a second step - every convolution alone on a batch of 
 of passes), of which the ten slowest are kept.  In the same run the baseline is recorded: what a caller passes to ``demo.run_video`` as
 the extractor today, a torch-ROCm nn.Module of the same network (the layer list of tests/extractor_ref.py with BatchNorm folded, fp32,
 ``torch.no_grad()``, the same chunks), under its own time limit; ``--no-torch-baseline`` skips it.  No ratio is fixed in advance: the
-measured ratio goes into the JSON whichever way it falls.  There is no threshold; no test reads this file.  Every GPU step runs in a
+measured ratio goes into the JSON whichever way it falls.  There is no threshold; no test reads this file.
+``--precision f16`` or ``both`` adds an ``f16`` block: the extractor built with ``precision="f16"`` (one f16 product per k-tile on f16
+maps, csrc/conv_f16.hpp) on the same patches with the same chunks in the same run, its ratio to the split mode of that run, the
+per-layer table of the f16 operators (all 53 layers, with each layer's split-mode time beside it when both ran) and the shader clock
+right after each timed loop.  The file is always written whole from the steps of this run: the committed record is regenerated with
+``--precision both``.  Every GPU step runs in a
 child process under its own timeout; the first step that fails ends the run (the baseline is last).  Runs on an MI355X only.  Writes one
 JSON (default profiles/extractor_bench.json).
 
     python scripts/bench_extractor.py [--out profiles/extractor_bench.json] [--patches 2400] [--reps 5] [--max-batch 64] [--no-torch-baseline]
+                                      [--precision split_f16|f16|both]
 """
 import argparse
 import json
@@ -23,7 +29,7 @@ REPO = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, REPO)
 sys.path.insert(0, os.path.join(REPO, "tests"))
 
-STEPS = (("extractor", 420), ("layers", 300), ("torch", 600))           # (name, timeout in seconds)
+STEPS = (("extractor", 420), ("layers", 300), ("extractor_f16", 420), ("layers_f16", 300), ("torch", 600))     # (name, timeout in seconds)
 SEED = 123
 
 
@@ -55,6 +61,16 @@ def conv_work():
     return out
 
 
+def clock_now():
+    """rocm-smi's sclk line(s): the shader clock right after a timed loop (a read; nothing is set)."""
+    try:
+        r = subprocess.run(["rocm-smi", "--showclocks"], capture_output=True, text=True, timeout=20).stdout
+        s = " ; ".join(" ".join(l.split()) for l in r.splitlines() if "sclk" in l)[:400]
+        return s or "rocm-smi --showclocks printed no sclk line"
+    except Exception as e:  # noqa: BLE001
+        return f"rocm-smi unavailable: {e}"
+
+
 def timed(fn, reps):
     import numpy as np
     import torch
@@ -78,28 +94,41 @@ def make_patches(n, dev):
     return torch.randn(n, 3, 224, 224, device=dev, generator=g)
 
 
-def step_extractor(args):
+def step_extractor(args, precision="split_f16"):
     import torch
     from pmce_amd import synth
     from pmce_amd.extractor import FeatureExtractor
     dev = torch.device("cuda:0")
     ext = FeatureExtractor.from_state_dict(synth.make_state_dict(synth.extractor_spec(), SEED), dev, max_batch=args.max_batch,
-                                           check_finite=False)
+                                           check_finite=False, precision=precision)
+    assert ext.precision == precision
     x = make_patches(args.patches, dev)
     f = ext(x)
     assert bool(torch.isfinite(f).all()), "a bench feature is not finite"
     med, best = timed(lambda: ext(x), args.reps)
+    clock = clock_now()                                  # right after the loop
     work = conv_work()
     macs, issued = sum(w[8] for w in work), sum(w[9] for w in work)
+    if precision == "f16":                               # one product per multiply-add, K padded to the 64-wide stage
+        issued = sum(w[7] * w[7] * ((w[1] + 63) // 64 * 64) * ((w[2] * w[3] * w[3] + 63) // 64 * 64) for w in work)
     s = med * 1e-3
-    return {"extractor": {"patches": args.patches, "max_batch": args.max_batch, "reps": args.reps, "ms_median": round(med, 3),
+    return {"extractor": {"precision": precision, "sclk_after": clock, "workspace_mb_per_patch": round(ext._ws.numel() * 4 / args.max_batch / 1e6, 2),
+                          "patches": args.patches, "max_batch": args.max_batch, "reps": args.reps, "ms_median": round(med, 3),
                           "ms_min": round(best, 3), "ms_per_patch": round(med / args.patches, 5), "patches_per_s": round(args.patches / s, 1),
                           "gmac_per_patch": round(macs / 1e9, 3), "tflops_algorithmic": round(2 * macs * args.patches / s / 1e12, 2),
                           "tflops_issued_f16": round(2 * issued * args.patches / s / 1e12, 2),
                           "feature_max": round(float(f.abs().max()), 2), "zero_features": round(float((f == 0).float().mean()), 4)}}
 
 
-def step_layers(args):
+def step_extractor_f16(args):
+    return {"f16_extractor": step_extractor(args, "f16")["extractor"]}
+
+
+def step_layers_f16(args):
+    return {"f16_layers": step_layers(args, "f16")["layers"]}
+
+
+def step_layers(args, precision="split_f16"):
     import torch
     from pmce_amd import extractor as EX
     dev = torch.device("cuda:0")
@@ -107,26 +136,36 @@ def step_layers(args):
     g = torch.Generator(device=dev)
     g.manual_seed(9)
     rows = []
+    f16 = precision == "f16"
+    dt = torch.float16 if f16 else torch.float32
     for name, cout, cin, k, stride, pad, s_in, s_out, macs, issued in conv_work():
         w = torch.randn(cout, cin, k, k, device=dev, generator=g) * (2.0 / (cin * k * k)) ** 0.5
         b = torch.randn(cout, device=dev, generator=g) * 0.1
-        planes, ws = EX.pack_conv(w)
+        planes, ws = EX.pack_conv_f16(w) if f16 else EX.pack_conv(w)
         nchw = name == "conv1"
         x = torch.randn((n, cin, s_in, s_in) if nchw else (n, s_in, s_in, cin), device=dev, generator=g)
-        res = torch.randn(n, s_out, s_out, cout, device=dev, generator=g) if name.endswith(".conv3") else None
+        x = x if nchw else x.to(dt)                      # the stem reads the fp32 patches in both modes
+        res = torch.randn(n, s_out, s_out, cout, device=dev, generator=g).to(dt) if name.endswith(".conv3") else None
         relu = not name.endswith("downsample.0")
-        med, _ = timed(lambda: EX.conv2d(x, "nchw" if nchw else "nhwc", planes, ws, (cout, cin, k, k), b, res, stride=stride, pad=pad,
-                                         relu=relu), args.reps)
+        if f16:
+            med, _ = timed(lambda: EX.conv2d_f16(x, "nchw" if nchw else "nhwc", planes, ws, (cout, cin, k, k), b, res, stride=stride, pad=pad,
+                                                 act="relu" if relu else "none"), args.reps)
+        else:
+            med, _ = timed(lambda: EX.conv2d(x, "nchw" if nchw else "nhwc", planes, ws, (cout, cin, k, k), b, res, stride=stride, pad=pad,
+                                             relu=relu), args.reps)
         rows.append({"layer": name, "shape": f"{cin}x{s_in}x{s_in} -> {cout}x{s_out}x{s_out}, {k}x{k}/{stride}", "ms_per_batch": round(med, 4),
                      "ms_for_all_patches": round(med * args.patches / n, 3), "tflops_algorithmic": round(2 * macs * n / (med * 1e-3) / 1e12, 2)})
-    x = torch.randn(n, 112, 112, 64, device=dev, generator=g)
+    x = torch.randn(n, 112, 112, 64, device=dev, generator=g).to(dt)
     pool, _ = timed(lambda: EX.maxpool3x3s2(x), args.reps)
-    x = torch.randn(n, 7, 7, 2048, device=dev, generator=g)
+    x = torch.randn(n, 7, 7, 2048, device=dev, generator=g).to(dt)
     avg, _ = timed(lambda: EX.avgpool(x), args.reps)
+    clock = clock_now()
     total = sum(r["ms_per_batch"] for r in rows)
+    every = {r["layer"]: r["ms_per_batch"] for r in rows}                 # all 53, in the order of the forward
     rows.sort(key=lambda r: -r["ms_per_batch"])
-    return {"layers": {"batch": n, "sum_of_convolutions_ms_per_batch": round(total, 3), "maxpool_ms_per_batch": round(pool, 4),
-                       "avgpool_ms_per_batch": round(avg, 4), "ten_slowest": rows[:10]}}
+    return {"layers": {"precision": precision, "batch": n, "sum_of_convolutions_ms_per_batch": round(total, 3),
+                       "maxpool_ms_per_batch": round(pool, 4), "avgpool_ms_per_batch": round(avg, 4), "sclk_after": clock,
+                       "ten_slowest": rows[:10], "ms_per_batch_by_layer": every}}
 
 
 def step_torch(args):
@@ -188,6 +227,8 @@ def main():
     ap.add_argument("--reps", type=int, default=5)
     ap.add_argument("--max-batch", type=int, default=64)
     ap.add_argument("--no-torch-baseline", action="store_true")
+    ap.add_argument("--precision", choices=["split_f16", "f16", "both"], default="split_f16",
+                    help="which mode(s) of the extractor to time; the committed record is made with 'both'")
     ap.add_argument("--step", choices=[s for s, _ in STEPS], help="(internal) run one GPU step in this process and print its JSON")
     args = ap.parse_args()
     if args.reps < 5:
@@ -198,6 +239,8 @@ def main():
     results = {}
     for name, limit in STEPS:
         if name == "torch" and args.no_torch_baseline:
+            continue
+        if name.endswith("_f16") and args.precision == "split_f16" or name in ("extractor", "layers") and args.precision == "f16":
             continue
         cmd = [sys.executable, os.path.abspath(__file__), "--step", name, "--reps", str(args.reps), "--patches", str(args.patches),
                "--max-batch", str(args.max_batch)]
@@ -212,8 +255,17 @@ def main():
             return 2
         results.update(json.loads(line[-1][7:]))
     from pmce_amd import _lib
+    if "f16_extractor" in results:                       # the f16 record next to the existing one
+        f16 = {"extractor": results.pop("f16_extractor"), "layers": results.pop("f16_layers")}
+        if "extractor" in results:
+            f16["split_f16_over_f16_time"] = round(results["extractor"]["ms_median"] / f16["extractor"]["ms_median"], 3)
+            split = results["layers"]["ms_per_batch_by_layer"]
+            f16["layers"]["split_f16_over_f16_time_by_layer"] = {k: round(split[k] / v, 3) for k, v in f16["layers"]["ms_per_batch_by_layer"].items()}
+            f16["layers"]["split_f16_over_f16_sum_of_convolutions"] = round(results["layers"]["sum_of_convolutions_ms_per_batch"] /
+                                                                            f16["layers"]["sum_of_convolutions_ms_per_batch"], 3)
+        results["f16"] = f16
     res = {"results": results, "build_id": _lib.build_id(), "patches": args.patches, "side": 224}
-    if "torch_baseline" in results:
+    if "torch_baseline" in results and "extractor" in results:
         res["held_against"] = {"torch_baseline_over_extractor_time":
                                round(results["torch_baseline"]["ms_median"] / results["extractor"]["ms_median"], 3)}
     os.makedirs(os.path.dirname(args.out), exist_ok=True)

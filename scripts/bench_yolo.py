@@ -7,10 +7,14 @@ batch of ``--max-batch`` - each convolution with its own epilogue and pitches, t
 class (convolutions by stage, upsample, decode, letterbox) with the ten slowest layers; and in the same run the torch-ROCm fp32 module
 of tests/yolo_ref.py's structure (BatchNorm as modules, eval mode, ``torch.no_grad()``, the same chunks, its own decoding) on the same
 letterboxed images.  No ratio is fixed in advance: the measured one goes into the JSON whichever way it falls.  What the box reports about
-its clock right after each timed loop is recorded, or the reason there is nothing to record.  There is no threshold; no test reads this
-file.  Every GPU step runs in a child process under its own timeout; the first step that fails ends the run.  Runs on an MI355X only.
+its clock right after each timed loop is recorded, or the reason there is nothing to record.  ``--precision f16`` or ``both`` adds an
+``f16`` block: the detector built with ``precision="f16"`` (one f16 product per k-tile on f16 maps, csrc/conv_f16.hpp) on the same frames
+with the same chunks in the same run, its ratio to the split mode of that run, and the same per-class table of the f16 operators.  The
+file is always written whole from the steps of this run: the committed record is regenerated with ``--precision both``.  There is no
+threshold; no test reads this file.  Every GPU step runs in a child process under its own timeout; the first step that fails ends the run.  Runs on an MI355X only.
 
     python scripts/bench_yolo.py [--out profiles/yolo_bench.json] [--frames 300] [--reps 5] [--max-batch 12] [--no-torch-baseline]
+                                 [--precision split_f16|f16|both]
 """
 import argparse
 import json
@@ -22,7 +26,7 @@ REPO = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, REPO)
 sys.path.insert(0, os.path.join(REPO, "tests"))
 
-STEPS = (("detector", 420), ("layers", 300), ("torch", 420))           # (name, timeout in seconds)
+STEPS = (("detector", 420), ("layers", 300), ("detector_f16", 420), ("layers_f16", 300), ("torch", 420))           # (name, timeout in seconds)
 WH = (1920, 1080)
 SIDE = 416
 
@@ -75,13 +79,22 @@ def stage_of(spec):
     return out
 
 
-def step_detector(args):
+def step_detector_f16(args):
+    return {"f16_detector": step_detector(args, "f16")["detector"]}
+
+
+def step_layers_f16(args):
+    return {"f16_layers": step_layers(args, "f16")["layers"]}
+
+
+def step_detector(args, precision="split_f16"):
     import torch
     import yolo_ref as YR
     from pmce_amd import yolo as Y
     dev = torch.device("cuda:0")
     spec = Y.yolov3_spec()
-    det = Y.YOLOv3.from_state_dict(YR.draw_state_dict(spec), dev, max_batch=args.max_batch, check_finite=False)
+    det = Y.YOLOv3.from_state_dict(YR.draw_state_dict(spec), dev, max_batch=args.max_batch, check_finite=False, precision=precision)
+    assert det.precision == precision
     frames = make_frames(args.frames, dev)
     index = torch.arange(args.frames, device=dev, dtype=torch.int32)
     images, _ = Y.letterbox(frames, index, size=SIDE)
@@ -92,7 +105,7 @@ def step_detector(args):
     fwd, _ = timed(lambda: det(images), args.reps)
     box, _ = timed(lambda: Y.letterbox(frames, index, size=SIDE), args.reps)
     fl = Y.flops(spec, SIDE)
-    return {"detector": {"frames": args.frames, "frame": f"{WH[0]}x{WH[1]}", "side": SIDE, "max_batch": args.max_batch, "reps": args.reps,
+    return {"detector": {"precision": precision, "frames": args.frames, "frame": f"{WH[0]}x{WH[1]}", "side": SIDE, "max_batch": args.max_batch, "reps": args.reps,
                          "ms_median": round(both, 3), "ms_min": round(both_min, 3), "ms_per_frame": round(both / args.frames, 4),
                          "frames_per_s": round(args.frames / (both * 1e-3), 1), "gflop_per_frame": round(fl / 1e9, 2),
                          "tflops_algorithmic": round(fl * args.frames / (both * 1e-3) / 1e12, 2),
@@ -101,11 +114,13 @@ def step_detector(args):
                          "sclk_after": clock}}
 
 
-def step_layers(args):
+def step_layers(args, precision="split_f16"):
     import torch
     from pmce_amd import extractor as EX
     from pmce_amd import yolo as Y
     dev = torch.device("cuda:0")
+    f16 = precision == "f16"
+    dt = torch.float16 if f16 else torch.float32
     spec = Y.yolov3_spec()
     L, shapes, stages = spec["layers"], Y.layer_shapes(spec), stage_of(spec)
     plan = Y.Plan(spec).layers
@@ -113,26 +128,27 @@ def step_layers(args):
     g = torch.Generator(device=dev)
     g.manual_seed(9)
 
-    def pitched(c, side, pitch, off):
-        return torch.randn(n, side, side, pitch, device=dev, generator=g)[..., off:off + c]
+    def pitched(c, side, pitch, off, dtype=None):
+        return torch.randn(n, side, side, pitch, device=dev, generator=g).to(dtype or dt)[..., off:off + c]
 
     rows, classes = [], {}
     for i, (cout, cin, k, _), stride, bn, ds in Y.conv_table(spec):
         s_out, s_in = SIDE // ds, SIDE // ds * stride
         w = torch.randn(cout, cin, k, k, device=dev, generator=g) * (2.0 / (cin * k * k)) ** 0.5
         b = torch.randn(cout, device=dev, generator=g) * 0.1
-        planes, ws = EX.pack_conv(w)
+        planes, ws = EX.pack_conv_f16(w) if f16 else EX.pack_conv(w)
         src = plan[i - 1] if i else {"pitch": 3, "channel_offset": 0}
-        x = pitched(cin, s_in, src["pitch"], src["channel_offset"])
+        x = pitched(cin, s_in, src["pitch"], src["channel_offset"], None if i else torch.float32)       # the stem reads fp32 images
         fused = i + 1 < len(L) and L[i + 1]["kind"] == "shortcut"
         dst = plan[i + 1] if fused else plan[i]
-        out = pitched(cout, s_out, dst["pitch"], dst["channel_offset"])
+        out = pitched(cout, s_out, dst["pitch"], dst["channel_offset"], torch.float32 if dst["buffer"] == -2 else None)   # detection maps: fp32
         res = None
         if fused:
             r = plan[L[i + 1]["frm"]]
             res = pitched(cout, s_out, r["pitch"], r["channel_offset"])
-        med, _ = timed(lambda: Y.conv2d_act(x, planes, ws, (cout, cin, k, k), b, res, stride=stride, pad=(k - 1) // 2,
-                                            act="leaky" if L[i]["leaky"] else "none", residual_after_act=True, out=out), args.reps)
+        conv = Y.conv2d_act_f16 if f16 else Y.conv2d_act
+        med, _ = timed(lambda: conv(x, planes, ws, (cout, cin, k, k), b, res, stride=stride, pad=(k - 1) // 2,
+                                    act="leaky" if L[i]["leaky"] else "none", residual_after_act=True, out=out), args.reps)
         macs = s_out * s_out * cout * cin * k * k
         rows.append({"layer": i, "class": stages[i], "shape": f"{cin}x{s_in}x{s_in} -> {cout}x{s_out}x{s_out}, {k}x{k}/{stride}"
                      + (" + shortcut" if fused else ""), "ms_per_batch": round(med, 4),
@@ -142,7 +158,7 @@ def step_layers(args):
     for i, l in enumerate(L):
         if l["kind"] == "upsample":
             c, side = shapes[i - 1][0], SIDE // shapes[i - 1][1]
-            x = torch.randn(n, side, side, c, device=dev, generator=g)
+            x = torch.randn(n, side, side, c, device=dev, generator=g).to(dt)
             out = pitched(c, 2 * side, plan[i]["pitch"], 0)
             up += timed(lambda: Y.upsample2x(x, out=out), args.reps)[0]
     E = 5 + spec["num_classes"]
@@ -157,7 +173,7 @@ def step_layers(args):
     rows.sort(key=lambda r: -r["ms_per_batch"])
     by_class = {k: round(v, 4) for k, v in classes.items()}
     by_class.update({"upsample": round(up, 4), "decode": round(dec, 4), "letterbox": round(box, 4)})
-    return {"layers": {"batch": n, "sum_of_convolutions_ms_per_batch": round(total, 3), "ms_per_batch_by_class": by_class,
+    return {"layers": {"precision": precision, "batch": n, "sum_of_convolutions_ms_per_batch": round(total, 3), "ms_per_batch_by_class": by_class,
                        "ten_slowest": rows[:10], "sclk_after": clock}}
 
 
@@ -194,6 +210,8 @@ def main():
     ap.add_argument("--reps", type=int, default=5)
     ap.add_argument("--max-batch", type=int, default=12)
     ap.add_argument("--no-torch-baseline", action="store_true")
+    ap.add_argument("--precision", choices=["split_f16", "f16", "both"], default="split_f16",
+                    help="which mode(s) of the detector to time; the committed record is made with 'both'")
     ap.add_argument("--step", choices=[s for s, _ in STEPS], help="(internal) run one GPU step in this process and print its JSON")
     args = ap.parse_args()
     if args.reps < 5:
@@ -204,6 +222,8 @@ def main():
     results = {}
     for name, limit in STEPS:
         if name == "torch" and args.no_torch_baseline:
+            continue
+        if name.endswith("_f16") and args.precision == "split_f16" or name in ("detector", "layers") and args.precision == "f16":
             continue
         cmd = [sys.executable, os.path.abspath(__file__), "--step", name, "--reps", str(args.reps), "--frames", str(args.frames),
                "--max-batch", str(args.max_batch)]
@@ -219,8 +239,17 @@ def main():
         results.update(json.loads(line[-1][7:]))
         print(f"bench_yolo: step {name} done", file=sys.stderr, flush=True)
     from pmce_amd import _lib
+    if "f16_detector" in results:                        # the f16 record next to the existing one
+        f16 = {"detector": results.pop("f16_detector"), "layers": results.pop("f16_layers")}
+        if "detector" in results:
+            f16["split_f16_over_f16_time"] = round(results["detector"]["ms_median"] / f16["detector"]["ms_median"], 3)
+            f16["split_f16_over_f16_forward_only_time"] = round(results["detector"]["forward_only_ms_median"] /
+                                                                f16["detector"]["forward_only_ms_median"], 3)
+            split = results["layers"]["ms_per_batch_by_class"]
+            f16["layers"]["split_f16_over_f16_time_by_class"] = {k: round(split[k] / v, 3) for k, v in f16["layers"]["ms_per_batch_by_class"].items()}
+        results["f16"] = f16
     res = {"results": results, "build_id": _lib.build_id(), "frames": args.frames, "side": SIDE}
-    if "torch_baseline" in results:
+    if "torch_baseline" in results and "detector" in results:
         res["held_against"] = {"torch_module_over_detector_forward_time":
                                round(results["torch_baseline"]["ms_median"] / results["detector"]["forward_only_ms_median"], 3)}
     os.makedirs(os.path.dirname(args.out), exist_ok=True)
