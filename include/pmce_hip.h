@@ -85,7 +85,10 @@ int pmce_model_finalize_on(pmce_model* m, pmce_stream_t stream);
  * pmce_model_split_bytes (after the last pmce_model_set_tensor; whatever the current mode; 0 for a handle that adopted another
  * one's planes) says how much, pmce_model_set_split_arena hands it over (256-byte aligned device memory that must outlive the model
  * and every handle sharing its planes) - before pmce_model_finalize[_on], and again before a pmce_model_set_gemm_mode[_on] that
- * switches a finalized model to split_f16.  Without an arena the library falls back to hipMalloc / hipFree of its own. */
+ * switches a finalized model to split_f16.  Without an arena the library falls back to hipMalloc / hipFree of its own.
+ * A handle in gemm mode 2 reports the larger arena that mode needs (the planes AND the lifter blocks' f16 weights): a caller with an arena
+ * of its own selects mode 2 before it asks, i.e. before pmce_model_finalize[_on] (a finalized model is re-opened by registering a tensor
+ * again). */
 size_t pmce_model_split_bytes(const pmce_model* m);
 int pmce_model_set_split_arena(pmce_model* m, void* arena, size_t bytes);
 /* Arithmetic of the path's 30 large products per forward (the pose lifter's Linear layers, the GRU input projections, the
@@ -93,12 +96,20 @@ int pmce_model_set_split_arena(pmce_model* m, void* arena, size_t bytes);
  * model packs for itself at finalize, 0 = the fp32 matrix pipe.  Both meet fp32 accuracy (tests/test_gpu_ops.py measures
  * each against an fp64 product); may be called at any time between forwards.  In split_f16 mode the GRU recurrence, the decoder's
  * FFNs and 431x431 self-attention and the lifter's attention (pmce_seq_attention_split_f16, for J = 17 / 19) use the same
- * three-product form. */
+ * three-product form.
+ * split_f16 == 2: the opt-in SINGLE-PRODUCT f16 mode of the lifter.  Everything is mode 1 except the 8 * depth products of the lifter's
+ * blocks (qkv, proj, fc1, fc2 of every spatial and temporal block): those run as ONE f16 product with fp32 accumulation
+ * (pmce_gemm_nt_f16) on weights packed by pmce_gemm_pack_f16 beside the planes, their A operands plain f16 rows (the form value 2 of
+ * pmce_ln_chain_f32 and the attention entries).  The residual stream, LayerNorm statistics, the attention's arithmetic, the feature
+ * products, GRU, decoder, upsampler and regression head are mode 1's.  NOT fp32-grade: about 0.2 to 0.6 mm on pose3d with synthetic
+ * weights, which the decoder can amplify beyond 1e-3 m on the mesh of a worst clip.  The LayerNorm-epilogue products (C = 256) and the fused qkv + attention
+ * kernel (C = 512) are not taken in this mode.  pmce_model_set_split_min_batch and the overflow word work as in mode 1.  Any other value
+ * returns PMCE_ERR_ARG. */
 int pmce_model_set_gemm_mode(pmce_model* m, int split_f16);
 /* The same with the packing (when the mode changes on a finalized model) on `stream`; it first waits for the whole device
  * (forwards in flight may read the planes it frees), so it must not be called during a stream capture. */
 int pmce_model_set_gemm_mode_on(pmce_model* m, int split_f16, pmce_stream_t stream);
-int pmce_model_gemm_mode(const pmce_model* m);
+int pmce_model_gemm_mode(const pmce_model* m); /* 0, 1 or 2 */
 /* A second handle on the SAME registered weights (a pipeline lane) takes the source's packed planes instead of packing its own copy:
  * call after the last pmce_model_set_tensor of `dst` and before its pmce_model_finalize; the planes live until the last handle goes. */
 int pmce_model_share_split_weights(pmce_model* dst, const pmce_model* src);
@@ -173,7 +184,7 @@ int pmce_stream_forward(pmce_model* m, const float* x0, const float* gi0, const 
 int pmce_stream_forward_mid(pmce_model* m, const float* x0, const float* x0_mid, const float* gi0, const int* win, int W, int L,
                             float* cam_mesh, float* cam_pose, float* pose3d, float* pred_pose, void* ws, size_t ws_bytes,
                             pmce_stream_t stream);
-/* building blocks of the above; xn_split != 0: XN written pre-split (see pmce_ln_chain_f32) */
+/* building blocks of the above; xn_split 1: XN written pre-split, 2: as plain f16 rows (see pmce_ln_chain_f32) */
 int pmce_window_tokens_f32(const float* x0, const int* win, const float* tpos, const float* w2, const float* b2, float eps2,
                            float* X, float* XN, int W, int L, int T, int J, int C, int xn_split, pmce_stream_t stream);
 /* Rewrites the W * J rows (w, t_mid, j) of X / XN (filled by pmce_window_tokens_f32) from x0_mid: X = x0_mid[m(w),j,:] + tpos[t_mid,:],
@@ -281,15 +292,18 @@ int pmce_gemm_split_path(int M, int N, int K, int act, int a_packed, int c_packe
 int pmce_embed_tokens_f32(const float* pose2d, const float* E, const float* Wje, const float* bje, const float* spos,
                           float* x, long long ntok, int J, int C, pmce_stream_t stream);
 /* The same followed by LayerNorm(w2, b2, eps2) of every token row (SpatialBlocks[0].norm1, PoseEstimation.py:13-29 via :83) in ONE launch:
- * x = the tokens (fp32 [ntok, C]), xn = their LayerNorm - fp32, or pre-split [row][C/16][16 hi | 16 lo*2^11] f16 when xn_split (the operand of a
- * three-product f16 GEMM).  Bit-identical to pmce_embed_tokens_f32 + pmce_ln_chain_f32(out2).  C = 128, 256, 384 or 512. */
+ * x = the tokens (fp32 [ntok, C]), xn = their LayerNorm - fp32, or pre-split [row][C/16][16 hi | 16 lo*2^11] f16 when xn_split is 1 (the operand of a
+ * three-product f16 GEMM), or plain f16 [row][C] when it is 2 (see pmce_ln_chain_f32).  Bit-identical to pmce_embed_tokens_f32 + pmce_ln_chain_f32(out2).  C = 128, 256, 384 or 512. */
 int pmce_embed_ln_f32(const float* pose2d, const float* E, const float* Wje, const float* bje, const float* spos, float* x,
                       long long ntok, int J, int C, const float* w2, const float* b2, float eps2, float* xn, int xn_split,
                       pmce_stream_t stream);
 /* nn.LayerNorm chain over rows of C channels (C = 128, 256, 384 or 512, as for every row kernel of the lifter): y1 = (w1 ? LN(x;w1,b1,eps1) : x) + add[(row/add_div)%add_mod];
  * out1 = y1 (optional); out2 = LN(y1;w2,b2,eps2) (optional).  norm1/norm2/norm_s/norm_t (PoseEstimation.py:17,23,58-59).
  * out2_split (and out_split / xn_split of the entries below) != 0: out2 / out / XN written pre-split ([row][C/16][16 hi | 16 lo*2^11] f16
- * in the bytes of the fp32 row), i.e. directly as the A operand of pmce_gemm_nt_split_f16(a_packed = 1). */
+ * in the bytes of the fp32 row), i.e. directly as the A operand of pmce_gemm_nt_split_f16(a_packed = 1).
+ * The value 2 of the same arguments: plain f16 [row][C], two bytes per channel in the first half of the buffer, every value rounded to
+ * nearest even with |x| < 2^-14 flushed to zero (inf and NaN stay) - the A operand of pmce_gemm_nt_f16 (lda = C).  out1 stays fp32.
+ * Any other value returns PMCE_ERR_ARG. */
 int pmce_ln_chain_f32(const float* x, long long rows, int C, const float* w1, const float* b1, float eps1, const float* add,
                       int add_div, int add_mod, float* out1, const float* w2, const float* b2, float eps2, float* out2,
                       int out2_split, pmce_stream_t stream);
@@ -316,6 +330,11 @@ int pmce_seq_attention_split_f16(const float* qkv, float* out_planes, int nseq, 
 int pmce_lifter_attention_split_supported(int N, int C);
 int pmce_lifter_attention_split_f16(const float* qkv, float* out_planes, int nseq, int N, int C, int seq_div, long long seq_lo,
                                     long long seq_hi, long long tok_stride, pmce_stream_t stream);
+/* The same with the result's form as an argument: out_form 1 = pmce_lifter_attention_split_f16 (which forwards here: the same launch, the
+ * same bits), 2 = plain f16 rows out[token][C] - the hi plane of form 1 with |x| < 2^-14 flushed to zero - the A operand of
+ * pmce_gemm_nt_f16 (half the bytes written).  The arithmetic inside is the same. */
+int pmce_lifter_attention_split_f16_form(const float* qkv, float* out, int nseq, int N, int C, int seq_div, long long seq_lo,
+                                         long long seq_hi, long long tok_stride, int out_form, pmce_stream_t stream);
 /* Temporal block, C = 512, split-f16 form: AO = attention(XN Wqkv^T + b) in ONE kernel - what pmce_gemm_nt_split_f16 (a_packed, blocked weight)
  * into fp32 qkv[M][3C] followed by pmce_seq_attention_split_f16(nseq = B*J, N = 16, seq_div = J, seq_lo = 1, seq_hi = 16*J, tok_stride = J) compute,
  * bit for bit, without the qkv tensor.  xn_planes / out_planes: pre-split rows [B*16*J][C/16][16 hi | 16 lo*2^11] f16; Wp / wscale: the [3C][C]

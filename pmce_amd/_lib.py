@@ -79,6 +79,7 @@ PROTOTYPES = {
     "pmce_lifter_attention_f32": [_f, _f, _i, _i, _i, _i, _l, _l, _l, _i, _s],
     "pmce_lifter_attention_split_supported": [_i, _i],
     "pmce_lifter_attention_split_f16": [_f, _f, _i, _i, _i, _i, _l, _l, _l, _s],
+    "pmce_lifter_attention_split_f16_form": [_f, _f, _i, _i, _i, _i, _l, _l, _l, _i, _s],
     "pmce_qkv_attention_fused_split_f16": [_f, _f, _f, _f, _f, _i, _i, _i, _f, _s],
     "pmce_gemm_split_set_tuning": [_i],
     "pmce_gemm_split_path": [_i, _i, _i, _i, _i, _i, _i, _i],

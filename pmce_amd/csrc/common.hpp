@@ -284,6 +284,15 @@ __device__ __forceinline__ void store4_split_f16(float* __restrict__ row, int c,
   *reinterpret_cast<f16x4*>(p + 16) = lo;
 }
 
+// The same four channels in the operand layout of the single-product f16 GEMM (gemm_f16.hip): plain f16 [row][C], every value r16 of
+// the (pinned) fp32 value - one 8-byte store.  `row` is the row's start in f16 elements.
+__device__ __forceinline__ void store4_f16(_Float16* __restrict__ row, int c, const f32x4& v_) {
+  f16x4 h;
+#pragma unroll
+  for (int e = 0; e < 4; ++e) h[e] = r16(pinned(v_[e]));
+  *reinterpret_cast<f16x4*>(row + c) = h;
+}
+
 // The unbiased std of a slot-layout token whose squared deviations overflow fp32 (a finite |x - mean| beyond 2^63, e.g. one channel at
 // 1e30): the plain sum gives var = inf and 1 / (inf + eps) = 0, which normalises the token to its beta - a finite, wrong AdaLN where the
 // reference's std (accumulated in double) is finite.  The same sum on the deviations scaled by a power of two (exact), scaled back.

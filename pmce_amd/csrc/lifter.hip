@@ -189,7 +189,8 @@ __global__ __launch_bounds__(256) void ln_chain_kernel(const float* __restrict__
 #pragma unroll
       for (int i = 0; i < 4; ++i) t[i] = v[i4 * 4 + i];
       if (!lane_on<C>(i4)) continue;
-      if (out2_split) store4_split_f16(out2 + row * C, i4 * 256 + lane * 4, t);  // operand of a three-product f16 GEMM
+      if (out2_split == 2) store4_f16(reinterpret_cast<_Float16*>(out2) + row * C, i4 * 256 + lane * 4, t);  // operand of a single-product f16 GEMM
+      else if (out2_split) store4_split_f16(out2 + row * C, i4 * 256 + lane * 4, t);  // operand of a three-product f16 GEMM
       else *reinterpret_cast<f32x4*>(out2 + row * C + i4 * 256 + lane * 4) = t;
     }
   }
@@ -263,7 +264,8 @@ __global__ __launch_bounds__(256) void embed_ln_kernel(const float* __restrict__
 #pragma unroll
       for (int i = 0; i < 4; ++i) t[i] = v[i4 * 4 + i];
       if (!lane_on<C>(i4)) continue;
-      if (xn_split) store4_split_f16(xn + tok * C, i4 * 256 + lane * 4, t);
+      if (xn_split == 2) store4_f16(reinterpret_cast<_Float16*>(xn) + tok * C, i4 * 256 + lane * 4, t);
+      else if (xn_split) store4_split_f16(xn + tok * C, i4 * 256 + lane * 4, t);
       else *reinterpret_cast<f32x4*>(xn + tok * C + i4 * 256 + lane * 4) = t;
     }
   }
@@ -343,7 +345,8 @@ __global__ __launch_bounds__(256) void seq_attention_kernel(const float* __restr
     f32x4 t;
 #pragma unroll
     for (int k = 0; k < 4; ++k) t[k] = o[4 * d4 + k] * inv;
-    if (out_split) store4_split_f16(dst, head * HD + 4 * d4, t);  // operand of a three-product f16 GEMM
+    if (out_split == 2) store4_f16(reinterpret_cast<_Float16*>(out) + (base + i * tok_stride) * C, head * HD + 4 * d4, t);  // ... of a single-product one
+    else if (out_split) store4_split_f16(dst, head * HD + 4 * d4, t);  // operand of a three-product f16 GEMM
     else *reinterpret_cast<f32x4*>(dst + head * HD + 4 * d4) = t;
   }
 }
@@ -364,7 +367,7 @@ __global__ __launch_bounds__(256) void seq_attention_kernel(const float* __restr
 // when the region changes hands.  Used at C = 512 (HD = 64): 151 / 139 us per spatial / temporal launch against 195 /
 // 179 us (B = 256); at C = 256 the first kernel already runs 16 waves per CU and both sit at ~4 TB/s, so it stays.
 // ------------------------------------------------------------------------------------------------------
-template <int HD, int N, bool OUT_SPLIT>
+template <int HD, int N, int OUT_FORM>  // the result: 0 fp32 rows, 1 pre-split planes, 2 plain f16 rows
 __global__ __launch_bounds__(128, 2) void seq_attention_pair_kernel(const float* __restrict__ qkv, float* __restrict__ out,
                                                                  int seq_div, long long seq_lo, long long seq_hi,
                                                                  long long tok_stride) {
@@ -524,7 +527,8 @@ __global__ __launch_bounds__(128, 2) void seq_attention_pair_kernel(const float*
     if (idx < CNT) {
       const f32x4 t = *reinterpret_cast<const f32x4*>(R + lds_off(u));
       float* row = out + (base + (idx / C4) * tok_stride) * C;
-      if constexpr (OUT_SPLIT) store4_split_f16(row, 4 * (idx % C4), t);
+      if constexpr (OUT_FORM == 2) store4_f16(reinterpret_cast<_Float16*>(out) + (base + (idx / C4) * tok_stride) * C, 4 * (idx % C4), t);
+      else if constexpr (OUT_FORM == 1) store4_split_f16(row, 4 * (idx % C4), t);
       else *reinterpret_cast<f32x4*>(row + 4 * (idx % C4)) = t;
     }
   }
@@ -630,13 +634,14 @@ extern "C" int pmce_embed_tokens_f32(const float* pose2d, const float* E, const 
 }
 
 // The same followed by LayerNorm(w2, b2, eps2) of every token row in one launch: x = the tokens (fp32), xn = their LayerNorm (pre-split [row][C/16][16 hi |
-// 16 lo*2^11] f16 when xn_split) - pmce_embed_tokens_f32 + pmce_ln_chain_f32(out2) without the round trip of the tokens.  C = 128, 256, 384 or 512.
+// 16 lo*2^11] f16 when xn_split is 1, plain f16 [row][C] of r16 values - the single-product f16 GEMM's operand - when it is 2) - pmce_embed_tokens_f32 + pmce_ln_chain_f32(out2) without the round trip of the tokens.  C = 128, 256, 384 or 512.
 extern "C" int pmce_embed_ln_f32(const float* pose2d, const float* E, const float* Wje, const float* bje, const float* spos, float* x,
                                  long long ntok, int J, int C, const float* w2, const float* b2, float eps2, float* xn, int xn_split,
                                  hipStream_t stream) {
   PMCE_REQUIRE(pose2d && E && Wje && bje && spos && x && w2 && b2 && xn, "embed_ln: null pointer");
   PMCE_REQUIRE(row_width_ok(C) && J > 0 && ntok > 0 && ntok % J == 0 && ntok < (1ll << 31),
                "embed_ln: C must be 128, 256, 384 or 512, J positive, ntok a positive multiple of J (whole frames) below 2^31");
+  PMCE_REQUIRE(xn_split >= 0 && xn_split <= 2, "embed_ln: xn_split is 0 (fp32), 1 (pre-split planes) or 2 (plain f16), got %d", xn_split);
   const long long nframes = ntok / J;
   // wavefronts per frame: enough wavefronts for the chip (8 per SIMD of 256 CUs), as few as that allows
   long long wpf = (8192 + nframes - 1) / nframes;
@@ -652,6 +657,7 @@ extern "C" int pmce_ln_chain_f32(const float* x, long long rows, int C, const fl
   PMCE_REQUIRE(row_width_ok(C), "ln_chain: C must be 128, 256, 384 or 512 (got %d)", C);
   PMCE_REQUIRE(rows > 0 && (out1 || out2), "ln_chain: nothing to do");
   PMCE_REQUIRE(!out2 || (w2 && b2), "ln_chain: out2 needs w2/b2");
+  PMCE_REQUIRE(out2_split >= 0 && out2_split <= 2, "ln_chain: out2_split is 0 (fp32), 1 (pre-split planes) or 2 (plain f16), got %d", out2_split);
   if (add_div <= 0) add_div = 1;
   if (add_mod <= 0) add_mod = 1;
   const unsigned grid = (unsigned)((rows + 3) / 4);
@@ -666,6 +672,7 @@ extern "C" int pmce_window_tokens_f32(const float* x0, const int* win, const flo
                                       hipStream_t stream) {
   PMCE_REQUIRE(row_width_ok(C), "window_tokens: C must be 128, 256, 384 or 512");
   PMCE_REQUIRE(x0 && win && tpos && w2 && b2 && X && XN && W > 0 && L > 0 && T > 0 && J > 0, "window_tokens: bad args");
+  PMCE_REQUIRE(xn_split >= 0 && xn_split <= 2, "window_tokens: xn_split is 0 (fp32), 1 (pre-split planes) or 2 (plain f16), got %d", xn_split);
   const long long rows = (long long)W * T * J;
   const unsigned grid = (unsigned)((rows + 3) / 4);
   PMCE_LAUNCH_C(ln_chain_kernel, C, grid, stream, x0, rows, nullptr, nullptr, 0.f, tpos, J, T, X, w2, b2, eps2, XN, win, L, xn_split);
@@ -720,7 +727,8 @@ __global__ __launch_bounds__(256) void window_mid_tokens_kernel(const float* __r
 #pragma unroll
     for (int i = 0; i < 4; ++i) t[i] = v[i4 * 4 + i];
     if (!lane_on<C>(i4)) continue;
-    if (xn_split) store4_split_f16(XN + row * C, i4 * 256 + lane * 4, t);
+    if (xn_split == 2) store4_f16(reinterpret_cast<_Float16*>(XN) + row * C, i4 * 256 + lane * 4, t);
+    else if (xn_split) store4_split_f16(XN + row * C, i4 * 256 + lane * 4, t);
     else *reinterpret_cast<f32x4*>(XN + row * C + i4 * 256 + lane * 4) = t;
   }
 }
@@ -731,6 +739,7 @@ extern "C" int pmce_window_mid_tokens_f32(const float* x0_mid, const int* win, c
   PMCE_REQUIRE(row_width_ok(C), "window_mid_tokens: C must be 128, 256, 384 or 512");
   PMCE_REQUIRE(x0_mid && win && tpos && w2 && b2 && X && XN && W > 0 && L > 0 && T > 0 && J > 0 && t_mid >= 0 && t_mid < T,
                "window_mid_tokens: bad args");
+  PMCE_REQUIRE(xn_split >= 0 && xn_split <= 2, "window_mid_tokens: xn_split is 0 (fp32), 1 (pre-split planes) or 2 (plain f16), got %d", xn_split);
   const long long rows = (long long)W * J;
   const unsigned grid = (unsigned)((rows + 3) / 4);
   PMCE_LAUNCH_C(window_mid_tokens_kernel, C, grid, stream, x0_mid, win, tpos, w2, b2, eps2, X, XN, W, L, T, J, t_mid, xn_split);
@@ -761,15 +770,19 @@ static int launch_seq_attention_pair(const float* qkv, float* out, int nseq, int
                                      long long tok_stride, int out_split, hipStream_t stream) {
   constexpr int lds = N * 8 * (HD + 4) * (int)sizeof(float);
   if (lds > 65536) {
-    static std::atomic<unsigned long long> attr{0}, attr_s{0};
-    PMCE_TRY(pmce_opt_in_lds((const void*)seq_attention_pair_kernel<HD, N, false>, lds, attr, "seq_attention"));
-    PMCE_TRY(pmce_opt_in_lds((const void*)seq_attention_pair_kernel<HD, N, true>, lds, attr_s, "seq_attention"));
+    static std::atomic<unsigned long long> attr{0}, attr_s{0}, attr_h{0};
+    PMCE_TRY(pmce_opt_in_lds((const void*)seq_attention_pair_kernel<HD, N, 0>, lds, attr, "seq_attention"));
+    PMCE_TRY(pmce_opt_in_lds((const void*)seq_attention_pair_kernel<HD, N, 1>, lds, attr_s, "seq_attention"));
+    PMCE_TRY(pmce_opt_in_lds((const void*)seq_attention_pair_kernel<HD, N, 2>, lds, attr_h, "seq_attention"));
   }
-  if (out_split)
-    hipLaunchKernelGGL((seq_attention_pair_kernel<HD, N, true>), dim3(nseq), dim3(128), lds, stream, qkv, out, seq_div, seq_lo,
+  if (out_split == 2)
+    hipLaunchKernelGGL((seq_attention_pair_kernel<HD, N, 2>), dim3(nseq), dim3(128), lds, stream, qkv, out, seq_div, seq_lo,
+                       seq_hi, tok_stride);
+  else if (out_split)
+    hipLaunchKernelGGL((seq_attention_pair_kernel<HD, N, 1>), dim3(nseq), dim3(128), lds, stream, qkv, out, seq_div, seq_lo,
                        seq_hi, tok_stride);
   else
-    hipLaunchKernelGGL((seq_attention_pair_kernel<HD, N, false>), dim3(nseq), dim3(128), lds, stream, qkv, out, seq_div, seq_lo,
+    hipLaunchKernelGGL((seq_attention_pair_kernel<HD, N, 0>), dim3(nseq), dim3(128), lds, stream, qkv, out, seq_div, seq_lo,
                        seq_hi, tok_stride);
   return pmce_check_launch("seq_attention");
 }
@@ -814,6 +827,7 @@ extern "C" int pmce_seq_attention_f32(const float* qkv, float* out, int nseq, in
                                       long long seq_hi, long long tok_stride, int out_split, hipStream_t stream) {
   PMCE_REQUIRE(C == 256 || C == 512, "seq_attention: C must be 256 or 512 (8 heads of 32/64)");
   PMCE_REQUIRE(N >= 1 && N <= 32 && nseq > 0, "seq_attention: N must be in 1..32 (got %d)", N);
+  PMCE_REQUIRE(out_split >= 0 && out_split <= 2, "seq_attention: out_split is 0 (fp32), 1 (pre-split planes) or 2 (plain f16), got %d", out_split);
   return launch_seq_attention(qkv, out, nseq, N, C, seq_div, seq_lo, seq_hi, tok_stride, out_split, stream);
 }
 
@@ -824,6 +838,7 @@ extern "C" int pmce_lifter_attention_f32(const float* qkv, float* out, int nseq,
   PMCE_REQUIRE(qkv && out, "lifter_attention: null pointer");
   PMCE_REQUIRE(row_width_ok(C), "lifter_attention: C must be 128, 256, 384 or 512 (8 heads of 16, 32, 48 or 64; got %d)", C);
   PMCE_REQUIRE(N >= 1 && N <= 32 && nseq > 0, "lifter_attention: N must be in 1..32 (got %d)", N);
+  PMCE_REQUIRE(out_split >= 0 && out_split <= 2, "lifter_attention: out_split is 0 (fp32), 1 (pre-split planes) or 2 (plain f16), got %d", out_split);
   return launch_seq_attention(qkv, out, nseq, N, C, seq_div, seq_lo, seq_hi, tok_stride, out_split, stream);
 }
 

@@ -32,7 +32,7 @@ struct LifterAttnCfg {
   static constexpr int OUTP = N * P4, NO = (OUTP + 63) / 64;
 };
 
-template <int HD, int N>
+template <int HD, int N, bool OUT16>
 __global__ __launch_bounds__(256) void lifter_attention_mfma_kernel(const float* __restrict__ qkv, float* __restrict__ out, int nseq,
                                                                   int seq_div, long long seq_lo, long long seq_hi,
                                                                   long long tok_stride, unsigned* oflow) {
@@ -111,21 +111,26 @@ __global__ __launch_bounds__(256) void lifter_attention_mfma_kernel(const float*
       const int idx = lane + 64 * i;
       const int row = idx / P4, piece = idx - row * P4;
       if (idx < Cfg::OUTP) {
-        const f32x4 t = *reinterpret_cast<const f32x4*>(U + row * RS + piece * 16);
-        *reinterpret_cast<f32x4*>(out + (tb + (long long)row * tok_stride) * C + col0 + piece * 4) = t;
+        if constexpr (OUT16) {  // channels 4 piece + [0, 4) of the strip: the hi half of group piece >> 2, flushed (flush4_f16); 8 bytes per lane
+          const f16x4 h = *reinterpret_cast<const f16x4*>(U + row * RS + (piece >> 2) * 64 + (piece & 3) * 8);
+          *reinterpret_cast<f16x4*>(reinterpret_cast<_Float16*>(out) + (tb + (long long)row * tok_stride) * C + col0 + piece * 4) = flush4_f16(h);
+        } else {
+          const f32x4 t = *reinterpret_cast<const f32x4*>(U + row * RS + piece * 16);
+          *reinterpret_cast<f32x4*>(out + (tb + (long long)row * tok_stride) * C + col0 + piece * 4) = t;
+        }
       }
     }
   }
   report_nonfinite(oflow, bad);
 }
 
-template <int HD, int N>
+template <int HD, int N, bool OUT16>
 int launch_lifter_attention(const float* qkv, float* out, int nseq, int seq_div, long long seq_lo, long long seq_hi, long long tok_stride,
                             hipStream_t stream) {
   using Cfg = LifterAttnCfg<HD, N>;
   const long long units = (long long)nseq * Cfg::UPS;
   const int grid = units < 1024 ? (int)units : 1024;  // persistent beyond four workgroups per CU
-  hipLaunchKernelGGL((lifter_attention_mfma_kernel<HD, N>), dim3(grid), dim3(256), 0, stream, qkv, out, nseq, seq_div, seq_lo, seq_hi, tok_stride,
+  hipLaunchKernelGGL((lifter_attention_mfma_kernel<HD, N, OUT16>), dim3(grid), dim3(256), 0, stream, qkv, out, nseq, seq_div, seq_lo, seq_hi, tok_stride,
                      pmce_overflow_sink());
   return pmce_check_launch("lifter_attention_split_f16");
 }
@@ -138,16 +143,21 @@ extern "C" int pmce_lifter_attention_split_supported(int N, int C) {
   return (C == 128 || C == 256 || C == 384 || C == 512) && (N == 16 || N == 17 || N == 19) ? 1 : 0;
 }
 
-extern "C" int pmce_lifter_attention_split_f16(const float* qkv, float* out, int nseq, int N, int C, int seq_div, long long seq_lo,
-                                               long long seq_hi, long long tok_stride, hipStream_t stream) {
+// out_form 1: the result pre-split [16 hi | 16 lo*2^11] per 16 channels in the bytes of the fp32 rows (the three-product GEMM's A operand);
+// 2: plain f16 rows [token][C] - the hi plane with |x| < 2^-14 flushed to zero - the single-product GEMM's (half the bytes written).
+extern "C" int pmce_lifter_attention_split_f16_form(const float* qkv, float* out, int nseq, int N, int C, int seq_div, long long seq_lo,
+                                                    long long seq_hi, long long tok_stride, int out_form, hipStream_t stream) {
   PMCE_REQUIRE(qkv && out && nseq > 0, "lifter_attention_split_f16: bad arguments");
   PMCE_REQUIRE(pmce_lifter_attention_split_supported(N, C),
                "lifter_attention_split_f16: C must be 128, 256, 384 or 512 and N 16, 17 or 19 (got N=%d C=%d)", N, C);
-  if (C == 256 || C == 512) return pmce_seq_attention_split_f16(qkv, out, nseq, N, C, seq_div, seq_lo, seq_hi, tok_stride, stream);
+  PMCE_REQUIRE(out_form == 1 || out_form == 2, "lifter_attention_split_f16: out_form is 1 (pre-split planes) or 2 (plain f16), got %d", out_form);
+  if (C == 256 || C == 512) return seq_attention_split_form(qkv, out, nseq, N, C, seq_div, seq_lo, seq_hi, tok_stride, out_form, stream);
   if (seq_div <= 0) seq_div = 0x7fffffff;  // (as pmce_seq_attention_f32: sequence s starts at token s * seq_lo)
   PMCE_REQUIRE(tok_stride > 0 && (long long)nseq * 2 < (1ll << 31), "lifter_attention_split_f16: bad token stride or too many sequences");
-#define PMCE_LATTN_CASE(HD_, N_) \
-  if (C == 8 * HD_ && N == N_) return launch_lifter_attention<HD_, N_>(qkv, out, nseq, seq_div, seq_lo, seq_hi, tok_stride, stream)
+#define PMCE_LATTN_CASE(HD_, N_)                                                                                                        \
+  if (C == 8 * HD_ && N == N_)                                                                                                          \
+  return out_form == 2 ? launch_lifter_attention<HD_, N_, true>(qkv, out, nseq, seq_div, seq_lo, seq_hi, tok_stride, stream)             \
+                       : launch_lifter_attention<HD_, N_, false>(qkv, out, nseq, seq_div, seq_lo, seq_hi, tok_stride, stream)
   PMCE_LATTN_CASE(16, 16);
   PMCE_LATTN_CASE(16, 17);
   PMCE_LATTN_CASE(16, 19);
@@ -156,4 +166,10 @@ extern "C" int pmce_lifter_attention_split_f16(const float* qkv, float* out, int
   PMCE_LATTN_CASE(48, 19);
 #undef PMCE_LATTN_CASE
   return PMCE_OK;
+}
+
+// the pre-split form (the same launch, the same bits as before the form argument existed)
+extern "C" int pmce_lifter_attention_split_f16(const float* qkv, float* out, int nseq, int N, int C, int seq_div, long long seq_lo,
+                                               long long seq_hi, long long tok_stride, hipStream_t stream) {
+  return pmce_lifter_attention_split_f16_form(qkv, out, nseq, N, C, seq_div, seq_lo, seq_hi, tok_stride, 1, stream);
 }

@@ -61,6 +61,8 @@ struct LifterBlockSplit {
 // everything build_split_weights fills (pointers into the split arena; split_items lists them)
 struct SplitPlanes {
   LifterBlockSplit sblk[2][8];
+  // gemm mode 2 only: the same 8 * depth weights as plain f16 + 2^-s (pmce_gemm_pack_f16; wp points at f16 there), beside the planes
+  LifterBlockSplit fblk[2][8];
   SplitW s_ie, s_wih0, s_wih1, s_whh0, s_whh1, s_ada, s_final;
   const float* ffn_img[3][2];  // per vertex block: the LDS images of the two FFNs' f16 form (vca, vsa)
   const float* qkv_img[3];     // per vertex block: the self-attention qkv weight's f16 form (vertex_sab)
@@ -109,6 +111,9 @@ struct pmce_model {
   bool concurrent = true;  // pmce_model_set_concurrency
   // the large products on the f16 matrix pipe (three-product split, fp32 accuracy) instead of the fp32 one
   bool split_gemm = true;  // pmce_model_set_gemm_mode / PMCE_SPLIT_F16=0 at create
+  // gemm mode 2 (split_gemm is true as well): the products of the lifter's BLOCKS as one f16 product each (gemm_f16.hip) on plain f16
+  // operands; everything else is the split mode.  Opt-in, never from the environment.
+  bool f16_blocks = false;
   std::shared_ptr<float> split_arena;  // every packed weight + its per-row 2^-s; shared by handles cloned onto the same weights.
                                        // Caller memory (pmce_model_set_split_arena: no-op deleter) or, without one, hipMalloc'ed.
   float* caller_arena = nullptr;       // set by pmce_model_set_split_arena, consumed by the next (re)build of the planes
@@ -129,6 +134,7 @@ struct pmce_model {
   // (A/B builds of one source: -DPMCE_QKV_ATTN_FUSED_DEFAULT=0 through PMCE_EXTRA_HIPCC_FLAGS makes a library whose default is the two launches.)
   int qkv_attn_fused = PMCE_QKV_ATTN_FUSED_DEFAULT;  // pmce_model_set_qkv_attention_fused
   bool split_now = false;  // decision for the call in progress (set by check_ws, the first thing every entry point does)
+  bool f16_now = false;    // ... and for its lifter blocks: the single-product form (split_now is true as well)
   // Sticky "a product of this model produced a non-finite value" word: 4 bytes of pinned host memory the device can write
   // (hipHostMalloc, mapped), so that reading it costs no synchronisation.  Set by the split-f16 products' epilogues (an activation
   // beyond f16's 65504 turns into inf / nan there, and so does fp32 overflow), checked by every entry point BEFORE it launches.
@@ -394,6 +400,16 @@ int lgemm(const pmce_model* m, const float* A, const float* W, const SplitW& sw,
 // them pre-split (hi | lo*2^11 f16 planes in the bytes of the fp32 row): the products then spend no vector work on splitting.
 // The decoder's token-local kernels run in the same form.
 inline int pk(const pmce_model* m) { return m->split_now ? 1 : 0; }
+// The form of the lifter blocks' operands (the form argument of the row kernels and the attention): 0 fp32, 1 pre-split, 2 plain f16 rows
+// in the first half of the same buffers (gemm mode 2).
+inline int blk_form(const pmce_model* m) { return m->f16_now ? 2 : pk(m); }
+// a product of the lifter's blocks: the single-product f16 form on the mode's own weights (A plain f16, lda in f16 elements; c_packed: fc1's
+// f16 result) in gemm mode 2, lgemm otherwise
+int bgemm(const pmce_model* m, const float* A, const float* W, const SplitW& sw, const SplitW& fw, const float* bias, const float* R,
+          float* Cc, int M, int N, int K, long long lda, long long ldc, int act, hipStream_t s, int a_packed = 0, int c_packed = 0) {
+  if (m->f16_now) return pmce_gemm_nt_f16(A, fw.wp, fw.scale, bias, R, Cc, M, N, K, lda, ldc, act, c_packed, nullptr, s);
+  return lgemm(m, A, W, sw, bias, R, Cc, M, N, K, lda, ldc, act, s, a_packed, c_packed);
+}
 
 // ---- GraphormerNet.forward --------------------------------------------------------------------------------
 // Everything up to and including SpatialBlocks[0] is PER FRAME (its attention runs over the J joints of one frame,
@@ -417,7 +433,7 @@ PostNorm post_norm_of(const pmce_model* m, int kind, int i) {
 }
 // C = 256 in split mode: the N = 256 products own whole rows (64 x 256 tiles), so the LayerNorm that follows them runs in their epilogue
 // (pmce_gemm_nt_split_f16_ln) instead of a launch of its own that re-reads the row.  (C = 512: a 512-wide tile does not fit)
-inline bool ln_in_product(const pmce_model* m) { return m->split_now && m->C == 256; }
+inline bool ln_in_product(const pmce_model* m) { return m->split_now && !m->f16_now && m->C == 256; }  // (the single-product form has no such epilogue)
 
 // The fused qkv + attention kernel walks units of 8 sequences x 1 head on up to 512 persistent workgroups, each unit a serial chain of 32 k-tiles
 // and an attention phase that only the CU's other workgroup hides; the product alone picks smaller tiles and shorter chains on small grids.
@@ -426,7 +442,7 @@ inline bool ln_in_product(const pmce_model* m) { return m->split_now && m->C == 
 // one unit per workgroup, B >= 31 at J = 17; smaller batches keep the two launches (B = 1 latency is untouched).
 constexpr int kQkvFusedMinUnits = 512;
 inline bool qkv_attn_fused_now(const pmce_model* m, int kind, int B) {
-  if (!(m->split_now && kind == 1 && m->C == 512 && T == 16 && m->qkv_attn_fused != 0)) return false;
+  if (!(m->split_now && !m->f16_now && kind == 1 && m->C == 512 && T == 16 && m->qkv_attn_fused != 0)) return false;
   return m->qkv_attn_fused == 2 || ((long long)B * m->J + 7) / 8 * 8 >= kQkvFusedMinUnits;
 }
 
@@ -437,6 +453,8 @@ int lifter_block_body(pmce_model* m, int kind, int i, long long M, int nframes, 
   const int J = m->J, C = m->C;
   const LifterBlockW& bw = m->w.blk[kind][i];
   const LifterBlockSplit& sw = m->sp.sblk[kind][i];
+  const LifterBlockSplit& fw = m->sp.fblk[kind][i];
+  const int form = blk_form(m);
   // split mode: the attention runs on the f16 matrix pipe too (seq_attention_mfma.hip, lifter_attention_mfma.hip at C = 128 / 384; reads the
   // fp32 q, k, v, writes AO pre-split)
   const int N_seq = kind == 0 ? J : T;
@@ -445,14 +463,15 @@ int lifter_block_body(pmce_model* m, int kind, int i, long long M, int nframes, 
   if (fused_attn) {  // XN -> AO in one launch, timed with the products; w.QKV is not touched
     RUN(P_GEMM_LIFTER, stream, pmce_qkv_attention_fused_split_f16(w.XN, sw.qkv.wp, sw.qkv.scale, bw.qkv_b, w.AO, B, J, C, nullptr, stream));
   } else {
-    RUN(P_GEMM_LIFTER, stream, lgemm(m, w.XN, bw.qkv_w, sw.qkv, bw.qkv_b, nullptr, w.QKV,
+    RUN(P_GEMM_LIFTER, stream, bgemm(m, w.XN, bw.qkv_w, sw.qkv, fw.qkv, bw.qkv_b, nullptr, w.QKV,
                                      (int)M, 3 * C, C, C, 3 * C, 0, stream, pk(m)));
+    // (gemm mode 2: the same kernels on the same fp32 q, k, v; only the result's form differs - plain f16 rows)
     if (kind == 0) {  // sequences = frames, tokens j contiguous                      (PoseEstimation.py:78,101)
-      if (mfma_attn) RUN(P_SEQ_ATTN, stream, pmce_lifter_attention_split_f16(w.QKV, w.AO, nframes, J, C, 0, J, 0, 1, stream));
-      else RUN(P_SEQ_ATTN, stream, pmce_lifter_attention_f32(w.QKV, w.AO, nframes, J, C, 0, J, 0, 1, pk(m), stream));
+      if (mfma_attn) RUN(P_SEQ_ATTN, stream, pmce_lifter_attention_split_f16_form(w.QKV, w.AO, nframes, J, C, 0, J, 0, 1, form, stream));
+      else RUN(P_SEQ_ATTN, stream, pmce_lifter_attention_f32(w.QKV, w.AO, nframes, J, C, 0, J, 0, 1, form, stream));
     } else {  // sequences = (b,j), tokens t at stride J                              (PoseEstimation.py:87,104)
-      if (mfma_attn) RUN(P_SEQ_ATTN, stream, pmce_lifter_attention_split_f16(w.QKV, w.AO, B * J, T, C, J, 1, (long long)T * J, J, stream));
-      else RUN(P_SEQ_ATTN, stream, pmce_lifter_attention_f32(w.QKV, w.AO, B * J, T, C, J, 1, (long long)T * J, J, pk(m), stream));
+      if (mfma_attn) RUN(P_SEQ_ATTN, stream, pmce_lifter_attention_split_f16_form(w.QKV, w.AO, B * J, T, C, J, 1, (long long)T * J, J, form, stream));
+      else RUN(P_SEQ_ATTN, stream, pmce_lifter_attention_f32(w.QKV, w.AO, B * J, T, C, J, 1, (long long)T * J, J, form, stream));
     }
   }
   const bool fuse = ln_in_product(m) && sw.proj.wp && sw.fc2.wp;
@@ -460,24 +479,24 @@ int lifter_block_body(pmce_model* m, int kind, int i, long long M, int nframes, 
     RUN(P_GEMM_LIFTER, stream, pmce_gemm_nt_split_f16_ln(w.AO, sw.proj.wp, 1, sw.proj.scale, bw.proj_b, w.X, (int)M, C, nullptr, nullptr, 0.f,
                                                          w.X, bw.norm2_w, bw.norm2_b, 1e-6f, w.XN, stream));
   } else {
-    RUN(P_GEMM_LIFTER, stream, lgemm(m, w.AO, bw.proj_w, sw.proj, bw.proj_b, w.X, w.X, (int)M, C,
+    RUN(P_GEMM_LIFTER, stream, bgemm(m, w.AO, bw.proj_w, sw.proj, fw.proj, bw.proj_b, w.X, w.X, (int)M, C,
                                      C, C, C, 0, stream, pk(m)));
     RUN(P_LN, stream, pmce_ln_chain_f32(w.X, M, C, nullptr, nullptr, 0.f, nullptr, 1, 1, nullptr, bw.norm2_w,
-                                        bw.norm2_b, 1e-6f, w.XN, pk(m), stream));
+                                        bw.norm2_b, 1e-6f, w.XN, form, stream));
   }
   float* Hid = w.QKV;
-  RUN(P_GEMM_LIFTER, stream, lgemm(m, w.XN, bw.fc1_w, sw.fc1, bw.fc1_b, nullptr, Hid, (int)M,
+  RUN(P_GEMM_LIFTER, stream, bgemm(m, w.XN, bw.fc1_w, sw.fc1, fw.fc1, bw.fc1_b, nullptr, Hid, (int)M,
                                    2 * C, C, C, 2 * C, 1, stream, pk(m), pk(m)));
   if (fuse && post) {  // x = norm_s/t(x + fc2(h)); XN = next norm1(x)
     RUN(P_GEMM_LIFTER, stream, pmce_gemm_nt_split_f16_ln(Hid, sw.fc2.wp, 1, sw.fc2.scale, bw.fc2_b, w.X, (int)M, 2 * C, post->w1, post->b1, 1e-6f,
                                                          w.X, post->w2, post->b2, 1e-6f, post->w2 ? w.XN : nullptr, stream));
     return PMCE_OK;
   }
-  RUN(P_GEMM_LIFTER, stream, lgemm(m, Hid, bw.fc2_w, sw.fc2, bw.fc2_b, w.X, w.X, (int)M, C,
+  RUN(P_GEMM_LIFTER, stream, bgemm(m, Hid, bw.fc2_w, sw.fc2, fw.fc2, bw.fc2_b, w.X, w.X, (int)M, C,
                                    2 * C, 2 * C, C, 0, stream, pk(m)));
   if (post)
     RUN(P_LN, stream, pmce_ln_chain_f32(w.X, M, C, post->w1, post->b1, 1e-6f, nullptr, J, T, w.X, post->w2, post->b2, 1e-6f,
-                                        post->w2 ? w.XN : nullptr, pk(m), stream));
+                                        post->w2 ? w.XN : nullptr, form, stream));
   return PMCE_OK;
 }
 
@@ -510,7 +529,7 @@ int lifter_frames(pmce_model* m, const float* pose2d, const float* img_feat, int
                                      nframes, C, F, F, C, 0, stream));
   // tokens + SpatialBlocks[0].norm1 in one pass (the tokens do not travel to HBM and back between the two)
   RUN(P_EMBED, stream, pmce_embed_ln_f32(pose2d, w.E, m->w.je_w, m->w.je_b, m->w.spos, w.X, M, J, C, m->w.blk[0][0].norm1_w,
-                                         m->w.blk[0][0].norm1_b, 1e-6f, w.XN, pk(m), stream));
+                                         m->w.blk[0][0].norm1_b, 1e-6f, w.XN, blk_form(m), stream));
   return lifter_block_body(m, 0, 0, M, nframes, 0, w, stream);
 }
 
@@ -519,7 +538,7 @@ int lifter_frames(pmce_model* m, const float* pose2d, const float* img_feat, int
 int lifter_post_norm(pmce_model* m, int kind, int i, long long M, LifterWs& w, hipStream_t stream) {
   const PostNorm pn = post_norm_of(m, kind, i);
   const float* add = (kind == 0 && i == 0) ? m->w.tpos : nullptr;
-  RUN(P_LN, stream, pmce_ln_chain_f32(w.X, M, m->C, pn.w1, pn.b1, 1e-6f, add, m->J, T, w.X, pn.w2, pn.b2, 1e-6f, pn.w2 ? w.XN : nullptr, pk(m), stream));
+  RUN(P_LN, stream, pmce_ln_chain_f32(w.X, M, m->C, pn.w1, pn.b1, 1e-6f, add, m->J, T, w.X, pn.w2, pn.b2, 1e-6f, pn.w2 ? w.XN : nullptr, blk_form(m), stream));
   return PMCE_OK;
 }
 
@@ -795,7 +814,8 @@ struct SplitItem {
   std::function<int(float*, hipStream_t)> pack;  // fills them at the pointer given and records it in the model's SplitPlanes
 };
 // the planes of a model of (C, depth) with / without lifter and decoder: from the weights `w`, recorded in `sp`
-std::vector<SplitItem> split_items(const Weights& w, SplitPlanes& sp, int C, int depth, bool lifter, bool decoder) {
+// f16_blocks (gemm mode 2): also the lifter blocks' weights as plain f16 (pmce_gemm_pack_f16), after the lifter's planes
+std::vector<SplitItem> split_items(const Weights& w, SplitPlanes& sp, int C, int depth, bool lifter, bool decoder, bool f16_blocks) {
   std::vector<SplitItem> items;
   auto pad64 = [](size_t n) { return (n + 63) & ~(size_t)63; };
   // every weight in the blocked layout (what a tile - or a GRU step's workgroup - fetches per k-tile is contiguous): rows padded to its 64-row blocks
@@ -804,6 +824,13 @@ std::vector<SplitItem> split_items(const Weights& w, SplitPlanes& sp, int C, int
     items.push_back({planes + pad64(n), [=, &dst](float* p, hipStream_t s) {
                        dst = {p, p + planes};
                        return pmce_gemm_pack_split_f16(W, n, k, k, p, p + planes, 1, s);
+                     }});
+  };
+  auto weight16 = [&](const float* W, int n, int k, SplitW& dst) {
+    const size_t floats = pad64(n) * k / 2;  // pmce_gemm_packed_f16_halves(n, k) f16
+    items.push_back({floats + pad64(n), [=, &dst](float* p, hipStream_t s) {
+                       dst = {p, p + floats};
+                       return pmce_gemm_pack_f16(W, n, k, k, p, p + floats, s);
                      }});
   };
   auto image = [&](int floats, const float*& dst, std::function<int(float*, hipStream_t)> fill) {
@@ -823,6 +850,16 @@ std::vector<SplitItem> split_items(const Weights& w, SplitPlanes& sp, int C, int
         weight(bw.fc1_w, 2 * C, C, sw.fc1);
         weight(bw.fc2_w, C, 2 * C, sw.fc2);
       }
+    if (f16_blocks)
+      for (int kind = 0; kind < 2; ++kind)
+        for (int i = 0; i < depth; ++i) {
+          const LifterBlockW& bw = w.blk[kind][i];
+          LifterBlockSplit& fw = sp.fblk[kind][i];
+          weight16(bw.qkv_w, 3 * C, C, fw.qkv);
+          weight16(bw.proj_w, C, C, fw.proj);
+          weight16(bw.fc1_w, 2 * C, C, fw.fc1);
+          weight16(bw.fc2_w, C, 2 * C, fw.fc2);
+        }
   }
   if (decoder) {
     weight(w.wih0, 6 * GH, F, sp.s_wih0);
@@ -857,7 +894,7 @@ int build_split_weights(pmce_model* m, hipStream_t stream) {
   }
   m->sp = {};
   if (!m->split_gemm) return PMCE_OK;
-  const std::vector<SplitItem> items = split_items(m->w, m->sp, m->C, m->depth, m->has_lifter, m->has_decoder);
+  const std::vector<SplitItem> items = split_items(m->w, m->sp, m->C, m->depth, m->has_lifter, m->has_decoder, m->f16_blocks);
   if (items.empty()) return PMCE_OK;
   const size_t floats = split_floats(items);
   if (m->caller_arena) {  // the caller's memory (its allocator, its lifetime): pmce_model_set_split_arena
@@ -980,7 +1017,7 @@ size_t pmce_model_split_bytes(const pmce_model* m) {
   for (auto& s : m->names)
     if (m->ptr.count(s)) (s.rfind("lifter.", 0) == 0 ? lifter : decoder) = true;
   SplitPlanes unused;
-  return split_floats(split_items(m->w, unused, m->C, m->depth, lifter, decoder)) * sizeof(float);
+  return split_floats(split_items(m->w, unused, m->C, m->depth, lifter, decoder, m->f16_blocks)) * sizeof(float);
 }
 int pmce_model_set_split_arena(pmce_model* m, void* arena, size_t bytes) {
   PMCE_REQUIRE(m, "model_set_split_arena: null model");
@@ -1025,13 +1062,18 @@ int pmce_model_finalize_on(pmce_model* m, pmce_stream_t stream) {
 int pmce_model_set_gemm_mode(pmce_model* m, int split_f16) { return pmce_model_set_gemm_mode_on(m, split_f16, nullptr); }
 int pmce_model_set_gemm_mode_on(pmce_model* m, int split_f16, pmce_stream_t stream) {
   PMCE_REQUIRE(m, "model_set_gemm_mode: null model");
-  if (m->split_gemm != (split_f16 != 0)) {
-    m->split_gemm = split_f16 != 0;
+  PMCE_REQUIRE(split_f16 >= 0 && split_f16 <= 2, "model_set_gemm_mode: the mode is 0 (fp32 pipe), 1 (split f16) or 2 (single-product f16 lifter blocks), got %d",
+               split_f16);
+  const bool split = split_f16 != 0, f16_blocks = split_f16 == 2;
+  if (m->split_gemm != split || m->f16_blocks != f16_blocks) {
+    if (m->f16_blocks != f16_blocks) m->split_adopted = false;  // another handle's arena holds what ITS mode needs
+    m->split_gemm = split;
+    m->f16_blocks = f16_blocks;
     if (m->finalized) PMCE_TRY(build_split_weights(m, stream));
   }
   return PMCE_OK;
 }
-int pmce_model_gemm_mode(const pmce_model* m) { return m && m->split_gemm ? 1 : 0; }
+int pmce_model_gemm_mode(const pmce_model* m) { return m && m->split_gemm ? (m->f16_blocks ? 2 : 1) : 0; }
 int pmce_model_share_split_weights(pmce_model* dst, const pmce_model* src) {
   PMCE_REQUIRE(dst && src && src->finalized, "model_share_split_weights: need a destination and a finalized source");
   PMCE_REQUIRE(dst->J == src->J && dst->C == src->C && dst->depth == src->depth, "model_share_split_weights: different configurations");
@@ -1045,6 +1087,7 @@ int pmce_model_share_split_weights(pmce_model* dst, const pmce_model* src) {
   dst->split_arena = src->split_arena;
   dst->sp = src->sp;
   dst->split_gemm = true;
+  dst->f16_blocks = src->f16_blocks;  // (the arena holds the f16 weights exactly when the source is in mode 2)
   dst->split_adopted = true;
   dst->oflow = src->oflow;  // lanes of one model report to one word
   dst->strict_overflow = src->strict_overflow;  // ... and follow its policy and its small-batch threshold
@@ -1132,6 +1175,7 @@ static int check_ws(pmce_model* m, int batch, void* ws, size_t ws_bytes) {
     return PMCE_ERR_WORKSPACE;
   }
   m->split_now = m->split_gemm && batch >= m->split_min_batch;  // arithmetic (and with it the stream schedule) of this call
+  m->f16_now = m->split_now && m->f16_blocks && m->has_lifter;
   pmce_set_overflow_sink(m->oflow.get());  // (thread-local; the entry point's Call clears it again)
   pmce_set_clock_sink(m->clk);
   return PMCE_OK;
@@ -1280,10 +1324,10 @@ static int stream_forward_impl(pmce_model* m, const float* x0, const float* x0_m
   PMCE_TRY(gru_rest(m, W, dw, gs));
   if (!single) PMCE_TRY(ev_record(m->ev_join, m->side, "stream_forward join"));
   RUN(P_LN, stream, pmce_window_tokens_f32(x0, win, m->w.tpos, m->w.blk[1][0].norm1_w, m->w.blk[1][0].norm1_b, 1e-6f, lw.X, lw.XN, W, L,
-                                           T, m->J, m->C, pk(m), stream));
+                                           T, m->J, m->C, blk_form(m), stream));
   if (x0_mid)
     RUN(P_LN, stream, pmce_window_mid_tokens_f32(x0_mid, win, m->w.tpos, m->w.blk[1][0].norm1_w, m->w.blk[1][0].norm1_b, 1e-6f, lw.X, lw.XN, W,
-                                                 L, T, m->J, m->C, T / 2, pk(m), stream));
+                                                 L, T, m->J, m->C, T / 2, blk_form(m), stream));
   return forward_tail(m, cam_mesh, cam_pose, pose3d, pred_pose, W, lw, dw, stream, "stream_forward join");
 }
 

@@ -40,6 +40,8 @@
 // qkv product, which runs at the chip's power limit; the same kernel splitting all three strips in LDS: 149 / 131 us.)
 #include "gemm_split_common.hpp"
 
+extern "C" int pmce_seq_attention_split_supported(int N, int C);
+
 namespace {
 
 // split8 (common.hpp) in the fused form
@@ -179,6 +181,15 @@ __device__ __forceinline__ void attention_head(unsigned char* U, int hoff, int r
   }
 }
 
+// The result's other form (OUT16 of the two kernels' store loops): plain f16 rows, the A operand of a single-product f16 GEMM.  The head
+// stage has left [16 hi | 16 lo*2^11] groups in LDS; the store takes the hi halves - rne16 of the fp32 result - and flushes |x| < 2^-14 to
+// zero, as r16 does (no operand relies on f16 sub-normals; inf and NaN stay).
+__device__ __forceinline__ f16x4 flush4_f16(f16x4 h) {
+#pragma unroll
+  for (int e = 0; e < 4; ++e) h[e] = fabsf((float)h[e]) < 6.103515625e-05f ? (_Float16)0.0f : h[e];
+  return h;
+}
+
 template <int HD, int N>
 struct AttnCfg {
   static constexpr int C = 8 * HD;
@@ -193,7 +204,7 @@ struct AttnCfg {
   static constexpr int QL = 2 * HeadCfg<HD, N>::KSTEPS * HPW;  // 16-byte Q loads per lane and unit
 };
 
-template <int HD, int N>
+template <int HD, int N, bool OUT16>
 __global__ __launch_bounds__(256, 2) void seq_attention_mfma_kernel(const float* __restrict__ qkv, float* __restrict__ out, int nseq,
                                                                    int seq_div, long long seq_lo, long long seq_hi,
                                                                    long long tok_stride, unsigned* oflow) {
@@ -312,8 +323,13 @@ __global__ __launch_bounds__(256, 2) void seq_attention_mfma_kernel(const float*
       for (int i = 0; i < ST; ++i) {
         const int row = 4 * i + (lane >> 4), piece = lane & 15;
         if (row < N) {
-          const f32x4 t = *reinterpret_cast<const f32x4*>(U + row * RS + wave * 256 + piece * 16);
-          *reinterpret_cast<f32x4*>(out + (tb + row * tok_stride) * C + g * 256 + wave * 64 + piece * 4) = t;
+          if constexpr (OUT16) {  // channels 4 piece + [0, 4) of the strip: the hi half of group piece >> 2; 128-byte row segments
+            const f16x4 h = *reinterpret_cast<const f16x4*>(U + row * RS + wave * 256 + (piece >> 2) * 64 + (piece & 3) * 8);
+            *reinterpret_cast<f16x4*>(reinterpret_cast<_Float16*>(out) + (tb + row * tok_stride) * C + g * 256 + wave * 64 + piece * 4) = flush4_f16(h);
+          } else {
+            const f32x4 t = *reinterpret_cast<const f32x4*>(U + row * RS + wave * 256 + piece * 16);
+            *reinterpret_cast<f32x4*>(out + (tb + row * tok_stride) * C + g * 256 + wave * 64 + piece * 4) = t;
+          }
         }
       }
     }
@@ -322,30 +338,29 @@ __global__ __launch_bounds__(256, 2) void seq_attention_mfma_kernel(const float*
   report_nonfinite(oflow, bad);
 }
 
-template <int HD, int N>
+template <int HD, int N, bool OUT16>
 int launch(const float* qkv, float* out, int nseq, int seq_div, long long seq_lo, long long seq_hi, long long tok_stride, hipStream_t stream) {
   using Cfg = AttnCfg<HD, N>;
   static std::atomic<unsigned long long> done{0};
-  PMCE_TRY(pmce_opt_in_lds(reinterpret_cast<const void*>(&seq_attention_mfma_kernel<HD, N>), Cfg::LDS_BYTES, done, "seq_attention_split_f16"));
+  PMCE_TRY(pmce_opt_in_lds(reinterpret_cast<const void*>(&seq_attention_mfma_kernel<HD, N, OUT16>), Cfg::LDS_BYTES, done, "seq_attention_split_f16"));
   const int units = nseq * Cfg::UPS;
   const int grid = units < 512 ? units : 512;
-  hipLaunchKernelGGL((seq_attention_mfma_kernel<HD, N>), dim3(grid), dim3(256), Cfg::LDS_BYTES, stream, qkv, out, nseq, seq_div, seq_lo, seq_hi,
+  hipLaunchKernelGGL((seq_attention_mfma_kernel<HD, N, OUT16>), dim3(grid), dim3(256), Cfg::LDS_BYTES, stream, qkv, out, nseq, seq_div, seq_lo, seq_hi,
                      tok_stride, pmce_overflow_sink());
   return pmce_check_launch("seq_attention_split_f16");
 }
 
-}  // namespace
-
-extern "C" int pmce_seq_attention_split_supported(int N, int C) { return (C == 256 || C == 512) && (N == 16 || N == 17 || N == 19) ? 1 : 0; }
-
-extern "C" int pmce_seq_attention_split_f16(const float* qkv, float* out, int nseq, int N, int C, int seq_div, long long seq_lo,
-                                            long long seq_hi, long long tok_stride, hipStream_t stream) {
+// C = 256 or 512; out_form 1: the result pre-split, 2: plain f16 rows (what pmce_lifter_attention_split_f16_form forwards here)
+int seq_attention_split_form(const float* qkv, float* out, int nseq, int N, int C, int seq_div, long long seq_lo, long long seq_hi,
+                             long long tok_stride, int out_form, hipStream_t stream) {
   PMCE_REQUIRE(qkv && out && nseq > 0, "seq_attention_split_f16: bad arguments");
   if (seq_div <= 0) seq_div = 0x7fffffff;  // (as pmce_seq_attention_f32: sequence s starts at token s * seq_lo)
   PMCE_REQUIRE(pmce_seq_attention_split_supported(N, C), "seq_attention_split_f16: C must be 256 or 512 and N 16, 17 or 19 (got N=%d C=%d)", N, C);
   PMCE_REQUIRE(tok_stride > 0 && (long long)N * tok_stride * 3 * C * 4 < (1ll << 32), "seq_attention_split_f16: a sequence spans 4 GiB or more");
-#define PMCE_ATTN_CASE(HD_, N_) \
-  if (C == 8 * HD_ && N == N_) return launch<HD_, N_>(qkv, out, nseq, seq_div, seq_lo, seq_hi, tok_stride, stream)
+#define PMCE_ATTN_CASE(HD_, N_)                                                                                                 \
+  if (C == 8 * HD_ && N == N_)                                                                                                  \
+  return out_form == 2 ? launch<HD_, N_, true>(qkv, out, nseq, seq_div, seq_lo, seq_hi, tok_stride, stream)                      \
+                       : launch<HD_, N_, false>(qkv, out, nseq, seq_div, seq_lo, seq_hi, tok_stride, stream)
   PMCE_ATTN_CASE(64, 16);
   PMCE_ATTN_CASE(64, 17);
   PMCE_ATTN_CASE(64, 19);
@@ -354,6 +369,15 @@ extern "C" int pmce_seq_attention_split_f16(const float* qkv, float* out, int ns
   PMCE_ATTN_CASE(32, 19);
 #undef PMCE_ATTN_CASE
   return PMCE_OK;
+}
+
+}  // namespace
+
+extern "C" int pmce_seq_attention_split_supported(int N, int C) { return (C == 256 || C == 512) && (N == 16 || N == 17 || N == 19) ? 1 : 0; }
+
+extern "C" int pmce_seq_attention_split_f16(const float* qkv, float* out, int nseq, int N, int C, int seq_div, long long seq_lo,
+                                            long long seq_hi, long long tok_stride, hipStream_t stream) {
+  return seq_attention_split_form(qkv, out, nseq, N, C, seq_div, seq_lo, seq_hi, tok_stride, 1, stream);
 }
 
 // Two more files are part of this translation unit, and for one reason: they use split8_fused and attention_head, which are defined above.

@@ -227,7 +227,7 @@ class Pipeline:
             # every lane is a handle of its own (the model's handle and workspace stay free for direct forward() calls)
             self._main = main
             self.engines = [main.clone_shared() for _ in range(self.depth)]
-            if main.gemm_mode() == "split_f16" and not _lib.split_overlap():
+            if main.gemm_mode() != "f32" and not _lib.split_overlap():
                 # diagnostic (PMCE_SPLIT_OVERLAP=0): the lanes keep their own handles and workspaces (batches are enqueued ahead
                 # of the GPU) but run down ONE stream, in order
                 st = torch.cuda.Stream(device=main.device)

@@ -219,15 +219,24 @@ def gru_step(gi, whh, bhh, h_prev, out, form="split", blocked=True, backward_onl
     return out if ndir == 2 else out[0]
 
 
+def f16_rows(buf):
+    """The plain f16 rows that form 2 of a row kernel or an attention (``out2_split`` / ``xn_split`` / ``out_split`` / ``out_form`` = 2) left in
+    the first half of an fp32-typed [rows, C] buffer: a float16 [rows, C] view of them (the A operand of pmce_gemm_nt_f16)."""
+    rows, Cc = buf.shape
+    return buf.contiguous().view(torch.float16).reshape(-1)[:rows * Cc].view(rows, Cc)
+
+
 def ln_chain(x, w1=None, b1=None, eps1=1e-6, add=None, add_div=1, add_mod=1, want_out1=True, w2=None, b2=None, eps2=1e-6,
              out2_split=False):
+    """out2_split (and xn_split / out_split of the wrappers below): False / 0 fp32, True / 1 pre-split planes, 2 plain f16 rows
+    (:func:`f16_rows` views them)."""
     lib = _lib.load()
     x = _c(x)
     rows, Cc = x.shape
     out1 = torch.empty_like(x) if want_out1 else None
     out2 = torch.empty_like(x) if w2 is not None else None
     _lib.check(lib.pmce_ln_chain_f32(P(x), rows, Cc, P(w1), P(b1), eps1, P(add), add_div, add_mod, P(out1), P(w2), P(b2), eps2,
-                                     P(out2), 1 if out2_split else 0, _st()), "ln_chain")
+                                     P(out2), int(out2_split), _st()), "ln_chain")
     return out1, out2
 
 
@@ -249,7 +258,7 @@ def embed_ln(pose2d, E, Wje, bje, spos, w2, b2, eps2=1e-6, xn_split=False):
     x = torch.empty(BT * J, Cc, device=E.device, dtype=torch.float32)
     xn = torch.empty_like(x)
     _lib.check(lib.pmce_embed_ln_f32(P(_c(pose2d)), P(_c(E)), P(_c(Wje)), P(_c(bje)), P(_c(spos)), P(x), BT * J, J, Cc, P(_c(w2)), P(_c(b2)), eps2,
-                                     P(xn), 1 if xn_split else 0, _st()), "embed_ln")
+                                     P(xn), int(xn_split), _st()), "embed_ln")
     return x, xn
 
 
@@ -281,7 +290,7 @@ def seq_attention(qkv, nseq, N, Cc, seq_div, seq_lo, seq_hi, tok_stride, out_spl
     qkv = _c(qkv)
     out = _attention_out(qkv, Cc, out)
     _lib.check(lib.pmce_seq_attention_f32(P(qkv), P(out), nseq, N, Cc, seq_div, seq_lo, seq_hi, tok_stride,
-                                          1 if out_split else 0, _st()), "seq_attention")
+                                          int(out_split), _st()), "seq_attention")
     return out
 
 
@@ -301,17 +310,22 @@ def lifter_attention(qkv, nseq, N, Cc, seq_div, seq_lo, seq_hi, tok_stride, out_
     qkv = _c(qkv)
     out = _attention_out(qkv, Cc, out)
     _lib.check(lib.pmce_lifter_attention_f32(P(qkv), P(out), nseq, N, Cc, seq_div, seq_lo, seq_hi, tok_stride,
-                                             1 if out_split else 0, _st()), "lifter_attention")
+                                             int(out_split), _st()), "lifter_attention")
     return out
 
 
-def lifter_attention_split(qkv, nseq, N, Cc, seq_div, seq_lo, seq_hi, tok_stride, out=None):
-    """:func:`seq_attention_split` at every width the model accepts (C = 128, 256, 384, 512): the entry the model calls."""
+def lifter_attention_split(qkv, nseq, N, Cc, seq_div, seq_lo, seq_hi, tok_stride, out=None, out_form=None):
+    """:func:`seq_attention_split` at every width the model accepts (C = 128, 256, 384, 512): the entry the model calls.  out_form (None:
+    the entry without a form argument): 1 pre-split planes, 2 plain f16 rows (:func:`f16_rows`)."""
     lib = _lib.load()
     qkv = _c(qkv)
     out = _attention_out(qkv, Cc, out)
-    _lib.check(lib.pmce_lifter_attention_split_f16(P(qkv), P(out), nseq, N, Cc, seq_div, seq_lo, seq_hi, tok_stride, _st()),
-               "lifter_attention_split_f16")
+    if out_form is None:
+        _lib.check(lib.pmce_lifter_attention_split_f16(P(qkv), P(out), nseq, N, Cc, seq_div, seq_lo, seq_hi, tok_stride, _st()),
+                   "lifter_attention_split_f16")
+    else:
+        _lib.check(lib.pmce_lifter_attention_split_f16_form(P(qkv), P(out), nseq, N, Cc, seq_div, seq_lo, seq_hi, tok_stride, int(out_form),
+                                                            _st()), "lifter_attention_split_f16_form")
     return out
 
 

@@ -82,14 +82,15 @@ class HipEngine:
         self.regressor_rows = rows
 
     def _give_split_arena(self):
-        """The f16 planes of the split mode live in memory of PyTorch's allocator (the library allocates none of its own)."""
+        """The f16 planes of the split mode - and, in "f16" mode, the lifter blocks' f16 weights beside them: the library reports the larger
+        arena for a handle in that mode - live in memory of PyTorch's allocator (the library allocates none of its own)."""
         n = int(self.lib.pmce_model_split_bytes(self.handle))
         if n and self.device is not None:
             self.split_arena = torch.empty(n, dtype=torch.uint8, device=self.device)
             _lib.check(self.lib.pmce_model_set_split_arena(self.handle, C.c_void_p(self.split_arena.data_ptr()), n), "model_set_split_arena")
 
     def finalize(self):
-        if self.gemm_mode() == "split_f16":
+        if self.gemm_mode() != "f32":
             self._give_split_arena()
         # on the CURRENT stream: the packed fp32 tensors registered above were produced on it, and the library's own packing of the
         # f16 planes reads them (a torch side stream is non-blocking: the null stream is not ordered behind it)
@@ -104,7 +105,7 @@ class HipEngine:
         other.set_gemm_mode(self.gemm_mode())
         other.register(self.packed)
         _lib.check(other.lib.pmce_model_share_split_weights(other.handle, self.handle), "model_share_split_weights")
-        if self.gemm_mode() != "split_f16":     # (nothing to share on the fp32 pipe: copy the two settings by hand)
+        if self.gemm_mode() == "f32":     # (nothing to share on the fp32 pipe: copy the two settings by hand)
             other.set_split_min_batch(self.get_split_min_batch())
             other.set_overflow_policy(self.strict_overflow)
         if self.regressor_rows:
@@ -136,18 +137,33 @@ class HipEngine:
 
     def set_gemm_mode(self, mode: str):
         """'split_f16' (default): the lifter's Linear layers on the f16 matrix pipe in the three-product form (fp32 operands,
-        fp32 accumulate, fp32 accuracy); 'f32': on the fp32 matrix pipe."""
-        if mode not in ("split_f16", "f32"):
-            raise ValueError("gemm mode must be 'split_f16' or 'f32'")
-        if mode == "split_f16" and self.gemm_mode() != "split_f16" and self._finalized:
+        fp32 accumulate, fp32 accuracy); 'f32': on the fp32 matrix pipe; 'f16' (opt-in, NOT fp32-grade): 'split_f16' except that the
+        products of the lifter's blocks run as one f16 product each on plain f16 operands (HipModuleBase.set_gemm_mode)."""
+        if mode not in self.GEMM_MODES:
+            raise ValueError("gemm mode must be 'split_f16', 'f32' or 'f16'")
+        cur = self.gemm_mode()
+        if self._finalized and mode != cur and mode != "f32" and "f16" in (mode, cur):
+            # The arena's size depends on the mode ('f16' adds the blocks' f16 weights), and the library reports it for the mode a handle is
+            # IN: re-open the finalized handle (registering a tensor again does that), select the mode, then finalize with a new arena.
+            torch.cuda.synchronize(self.device)      # forwards in flight read the arena that is about to be replaced
+            name = next(n for n in self.packed if not n.startswith("jreg."))
+            _lib.check(self.lib.pmce_model_set_tensor(self.handle, name.encode(), C.c_void_p(self.packed[name].data_ptr())), f"set_tensor({name})")
+            self._finalized = False
+            _lib.check(self.lib.pmce_model_set_gemm_mode_on(self.handle, self.GEMM_MODES.index(mode), None), "model_set_gemm_mode")
+            self.finalize()
+            return
+        if mode == "split_f16" and cur == "f32" and self._finalized:
             self._give_split_arena()      # a finalized fp32-mode model is about to pack its planes
-        _lib.check(self.lib.pmce_model_set_gemm_mode_on(self.handle, 1 if mode == "split_f16" else 0, _lib.current_stream()),
+        # (a handle that is not finalized packs nothing: no stream, and no GPU, is needed to select its mode)
+        _lib.check(self.lib.pmce_model_set_gemm_mode_on(self.handle, self.GEMM_MODES.index(mode), _lib.current_stream() if self._finalized else None),
                    "model_set_gemm_mode")
         if mode == "f32":
             self.split_arena = None       # (the library waited for the device before it let go of the planes)
 
+    GEMM_MODES = ("f32", "split_f16", "f16")     # pmce_model_set_gemm_mode's 0, 1, 2
+
     def gemm_mode(self) -> str:
-        return "split_f16" if self.lib.pmce_model_gemm_mode(self.handle) else "f32"
+        return self.GEMM_MODES[self.lib.pmce_model_gemm_mode(self.handle)]
 
     def set_split_min_batch(self, clips: int):
         _lib.check(self.lib.pmce_model_set_split_min_batch(self.handle, int(clips)), "model_set_split_min_batch")
@@ -233,8 +249,16 @@ class HipModuleBase(nn.Module):
 
     def set_gemm_mode(self, mode, min_batch=None):
         """Arithmetic of the large products (min_batch: calls with fewer clips stay on the fp32 pipe, default 1 = none): 'split_f16' (three f16 products per fp32 product on the f16 matrix
-        pipe, fp32 accumulate; fp32-grade accuracy, the default) or 'f32' (fp32 matrix pipe).  Takes effect at the next
+        pipe, fp32 accumulate; fp32-grade accuracy, the default), 'f32' (fp32 matrix pipe) or 'f16' (opt-in).  Takes effect at the next
         forward; pipelines and captured graphs made before must be rebuilt.
+
+        'f16' is 'split_f16' in everything except the 24 products of the lifter's blocks (qkv, proj, fc1, fc2 of 3 spatial + 3 temporal
+        blocks at depth 3): those run as ONE f16 product with fp32 accumulation on plain f16 operands.  The feature products, the GRU,
+        the decoder, the upsampler, j_regress, LayerNorm statistics, the fp32 residual stream and the regression head are untouched.  It
+        trades accuracy for time: about 0.2 to 0.6 mm on pose3d with synthetic weights, which the decoder can amplify beyond 1e-3 m on
+        the mesh of a worst clip (no claim on a real checkpoint); it gains at large batches (1.47 x at C = 512,
+        B = 256) and not at B = 1.  min_batch, the overflow policies (a "rerun" is computed on the fp32
+        pipe, bit-identical to 'f32'), clones, pipelines, graphs and streaming work as in 'split_f16'.
 
         On MI355X a wave executing f16 matrix instructions corrupts packed-fp32 arithmetic (v_pk_{fma,mul,add}_f32) of other waves
         on the same CU (scripts/microbench/victims.py).  The library is therefore built without any packed-fp32 instruction
@@ -245,8 +269,8 @@ class HipModuleBase(nn.Module):
         compiler-generated packed fp32 stay bit-correct beside forwards in both modes; the affected form is hand-written
         v_pk_fma_f32 with op_sel operands - code like that should not run concurrently with a forward in 'split_f16' mode
         ('f32' mode has no such restriction; PMCE_SPLIT_OVERLAP=0 restores the strictly serial schedule)."""
-        if mode not in (None, "split_f16", "f32"):
-            raise ValueError("gemm mode must be 'split_f16', 'f32' or None")
+        if mode not in (None, "split_f16", "f32", "f16"):
+            raise ValueError("gemm mode must be 'split_f16', 'f32', 'f16' or None")
         self._gemm_mode = mode
         self._split_min_batch = min_batch
         self._dirty = True
@@ -309,7 +333,7 @@ class HipModuleBase(nn.Module):
         ``_overflow_carried`` - still reported by :meth:`overflowed` and ``Pipeline.synchronize`` until :meth:`clear_overflow` - and the
         word is cleared before the launch, so that only this call's products can set it."""
         eng = eng or self._ensure_packed()
-        rerun = self.overflow_policy() == "rerun" and eng.gemm_mode() == "split_f16" and not torch.cuda.is_current_stream_capturing()
+        rerun = self.overflow_policy() == "rerun" and eng.gemm_mode() != "f32" and not torch.cuda.is_current_stream_capturing()
         if rerun and eng.overflowed():
             torch.cuda.current_stream(eng.device).synchronize()
             self._overflow_carried = True
