@@ -1010,6 +1010,20 @@ int pmce_yolo_forward(const pmce_yolo* y, const float* images, long long sn, lon
  *   first: reported when time_since_update < 1 and (hit_streak >= min_hits or frame_count <= min_hits), deleted when
  *   time_since_update > max_age.  A sequence computes the same bits alone or beside others.
  *
+ * pmce_sort_track_resume_f64: pmce_sort_track_f64 on a piece of each sequence, with the trackers carried in ``state``: S records of
+ *   pmce_sort_state_bytes() bytes each (device memory, 8-byte aligned), record i for sequence i.  Each wave loads its record before its
+ *   first frame and stores it, in place, after its last (after that frame's time_since_update > max_age deletion); the outputs are
+ *   indexed by the frames of this call.  Feeding a video in pieces of any lengths gives, frame for frame, the bits of the one
+ *   pmce_sort_track_f64 launch over the whole video.  A record, with t = tracker slot 0..63 the minor index everywhere:
+ *     double x[7][64]       the filter state (u, v, s, r, du, dv, ds)
+ *     double P[7][7][64]    its covariance, row-major
+ *     int    alive[64], id[64] (from 0), time_since_update[64], hit_streak[64]
+ *     int    frame_count, next_id
+ *   An all-zero record is a fresh tracker (hipMemset makes one), and a slot that is not alive is stored as zeros, so equal histories
+ *   give equal bytes.  A sequence without a frame in the call (seq_offsets[i] == seq_offsets[i + 1]) and a call with F == 0 leave the
+ *   records untouched.  The rule: the same max_tracks, max_age, min_hits, iou_threshold and update_on_empty on every call of one state;
+ *   the record does not store them and the kernel cannot tell.  K may differ between calls.
+ *
  * pmce_tracklet_boxes_f64: multi_person_tracker's prepare_output_tracks for a gathered list of reported rows: row index[i] of
  *   tracks[total][5] (an index outside gives zeros) -> out[n][4] = (cx, cy, s, s), w = x2 - x1, h = y2 - y1, cx = x1 + w / 2,
  *   cy = y1 + h / 2, s = w if w / h > 1 else h, in fp64. */
@@ -1019,6 +1033,10 @@ int pmce_yolo_nms_f32(const float* rows, int n, int R, int nc, float conf_thres,
 int pmce_sort_track_f64(const double* people, const int* people_count, const int* seq_offsets_host, const int* seq_offsets, int F, int K,
                         int S, int max_age, int min_hits, double iou_threshold, int max_tracks, int update_on_empty, double* tracks,
                         int* track_count, int* status, pmce_stream_t stream);
+size_t pmce_sort_state_bytes(void);
+int pmce_sort_track_resume_f64(const double* people, const int* people_count, const int* seq_offsets_host, const int* seq_offsets, int F,
+                               int K, int S, int max_age, int min_hits, double iou_threshold, int max_tracks, int update_on_empty,
+                               double* tracks, int* track_count, int* status, void* state, pmce_stream_t stream);
 int pmce_tracklet_boxes_f64(const double* tracks, const int* index, int total, int n, double* out, pmce_stream_t stream);
 
 /* ---------------------------------------------------------------------------------------------------------

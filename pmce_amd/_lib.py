@@ -200,6 +200,8 @@ PROTOTYPES = {
     "pmce_yolo_nms_f32": [_f, _i, _i, _i, _fl, _fl, _i, _i, _f, _f, _f, _f, _f, _f, _i, _d, _i, _d, _d, _d, _s],
     "pmce_tracklet_boxes_f64": [_f, _f, _i, _i, _f, _s],
     "pmce_sort_track_f64": [_f, _f, C.POINTER(C.c_int), _f, _i, _i, _i, _i, _i, _d, _i, _i, _f, _f, _f, _s],
+    "pmce_sort_state_bytes": [],
+    "pmce_sort_track_resume_f64": [_f, _f, C.POINTER(C.c_int), _f, _i, _i, _i, _i, _i, _d, _i, _i, _f, _f, _f, _f, _s],
     "pmce_jpeg_entropy": [_f, _l, _f, _i, _i, _f, _i, _f, _i, _f, _l, _f, _i, _i, _s],
     "pmce_jpeg_entropy_parallel": [_f, _l, _f, _i, _i, _f, _i, _f, _i, _f, _l, _f, _i, _i, _f, _i, _i, _f, _l, _i, _s],
     "pmce_jpeg_parallel_run": [],
@@ -237,6 +239,7 @@ _RESTYPES = {
     "pmce_yolo_workspace_units": C.c_longlong,
     "pmce_yolo_workspace_bytes": C.c_size_t,
     "pmce_jpeg_encode_workspace_bytes": C.c_size_t,
+    "pmce_sort_state_bytes": C.c_size_t,
 }
 
 _lib = None

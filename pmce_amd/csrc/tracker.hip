@@ -28,6 +28,9 @@
 //   reversed walk that reports is "descending id" and needs a rank, not a compaction; a new tracker takes the lowest free slot.  The
 //   assignment is exact: shortest augmenting paths with potentials over the matrix cost[d][t] = -IoU (0 for a free slot, which is a
 //   dummy column: rows <= 64 = columns always holds), lane t owns column t, one wave minimum per step.
+//   With a state record (pmce_sort_track_resume_f64) the wave loads lane state, covariance, frame_count and next_id before its first
+//   frame and stores them after its last, [element][lane] like the LDS copy: every load and store is 64 consecutive words.  A slot that
+//   is not alive is stored as zeros, and an all-zero record is the fresh tracker, so the bits of a video do not depend on its cuts.
 #include "common.hpp"
 
 #include <math.h>
@@ -275,6 +278,12 @@ constexpr int SORT_MAX = 64;
 // LDS doubles: P [49][64], AP [49][64], cost [64][64], det [64][4], u [65]; ints: p [65], way [65], d2t [64]
 constexpr int SORT_LDS_DOUBLES = 49 * 64 * 2 + 64 * 64 + 64 * 4 + 65;
 constexpr int SORT_LDS_BYTES = SORT_LDS_DOUBLES * 8 + (65 + 65 + 64) * 4;
+// the state record of one sequence (include/pmce_hip.h): doubles x [7][64], P [49][64]; ints alive, id, tsu, streak [4][64], then
+// frame_count, next_id.  A whole number of doubles, so consecutive records stay aligned.
+constexpr int SORT_STATE_DOUBLES = (7 + 49) * 64;
+constexpr int SORT_STATE_INTS = 4 * 64 + 2;
+constexpr size_t SORT_STATE_BYTES = (size_t)SORT_STATE_DOUBLES * 8 + (size_t)SORT_STATE_INTS * 4;
+static_assert(SORT_STATE_BYTES % 8 == 0, "records must keep the doubles aligned");
 
 __device__ __forceinline__ double wave_min_f64(double v) {
 #pragma unroll
@@ -296,7 +305,8 @@ __device__ __forceinline__ Box4 state_box(const double* x) {
 __global__ __launch_bounds__(64) void sort_kernel(const double* __restrict__ people, const int* __restrict__ people_count,
                                                    const int* __restrict__ seq, int F, int K, int max_age, int min_hits, double iou_thr,
                                                    int max_tracks, int update_on_empty, double* __restrict__ tracks,
-                                                   int* __restrict__ track_count, int* __restrict__ status) {
+                                                   int* __restrict__ track_count, int* __restrict__ status,
+                                                   unsigned char* __restrict__ state) {
 #pragma clang fp contract(off)
   extern __shared__ __align__(16) unsigned char sort_lds[];
   double* Pm = reinterpret_cast<double*>(sort_lds);
@@ -319,6 +329,24 @@ __global__ __launch_bounds__(64) void sort_kernel(const double* __restrict__ peo
   bool alive = false;
   int id = -1, tsu = 0, streak = 0;
   int frame_count = 0, next_id = 0;
+
+  double* sd = nullptr;  // this sequence's record
+  int* si = nullptr;
+  if (state) {
+    if (f0 >= f1) return;  // no frame in this call: the record is not touched (uniform)
+    sd = reinterpret_cast<double*>(state + (size_t)blockIdx.x * SORT_STATE_BYTES);
+    si = reinterpret_cast<int*>(sd + SORT_STATE_DOUBLES);
+    alive = si[lane] != 0;
+    id = si[64 + lane];
+    tsu = si[128 + lane];
+    streak = si[192 + lane];
+    frame_count = si[256];
+    next_id = si[257];
+#pragma unroll
+    for (int i = 0; i < 7; ++i) x[i] = sd[i * 64 + lane];
+#pragma unroll
+    for (int e = 0; e < 49; ++e) Pm[e * 64 + lane] = sd[(7 + e) * 64 + lane];
+  }
 
   for (int f = f0; f < f1; ++f) {
     int nd = people_count[f];
@@ -598,6 +626,20 @@ __global__ __launch_bounds__(64) void sort_kernel(const double* __restrict__ peo
     if (alive && tsu > max_age) alive = false;
     __syncthreads();
   }
+  if (state) {  // a slot that is not alive is zeros: equal histories give equal bytes
+    si[lane] = alive ? 1 : 0;
+    si[64 + lane] = alive ? id : 0;
+    si[128 + lane] = alive ? tsu : 0;
+    si[192 + lane] = alive ? streak : 0;
+    if (lane == 0) {
+      si[256] = frame_count;
+      si[257] = next_id;
+    }
+#pragma unroll
+    for (int i = 0; i < 7; ++i) sd[i * 64 + lane] = alive ? x[i] : 0.0;
+#pragma unroll
+    for (int e = 0; e < 49; ++e) sd[(7 + e) * 64 + lane] = alive ? Pm[e * 64 + lane] : 0.0;
+  }
 #undef PE
 #undef AP
 }
@@ -657,10 +699,12 @@ extern "C" int pmce_yolo_nms_f32(const float* rows, int n, int R, int nc, float 
   return pmce_check_launch(what);
 }
 
-extern "C" int pmce_sort_track_f64(const double* people, const int* people_count, const int* seq_offsets_host, const int* seq_offsets,
-                                   int F, int K, int S, int max_age, int min_hits, double iou_threshold, int max_tracks,
-                                   int update_on_empty, double* tracks, int* track_count, int* status, hipStream_t stream) {
-  const char* what = "sort_track_f64";
+namespace {
+
+// the one launcher: state == nullptr is the whole-video form
+int sort_track_launch(const char* what, const double* people, const int* people_count, const int* seq_offsets_host, const int* seq_offsets,
+                      int F, int K, int S, int max_age, int min_hits, double iou_threshold, int max_tracks, int update_on_empty,
+                      double* tracks, int* track_count, int* status, unsigned char* state, hipStream_t stream) {
   PMCE_REQUIRE(people && people_count && tracks && track_count && status, "%s: null pointer", what);
   PMCE_REQUIRE(F >= 0 && S >= 1, "%s: F must be >= 0 and S >= 1 (got %d, %d)", what, F, S);
   PMCE_REQUIRE(K >= 1 && K <= SORT_MAX, "%s: K (detections per frame) must be in 1..%d (got %d)", what, SORT_MAX, K);
@@ -680,8 +724,30 @@ extern "C" int pmce_sort_track_f64(const double* people, const int* people_count
   if (F == 0) return PMCE_OK;
   PMCE_TRY(pmce_opt_in_lds((const void*)sort_kernel, SORT_LDS_BYTES, sort_lds_done, what));
   hipLaunchKernelGGL(sort_kernel, dim3(S), dim3(64), SORT_LDS_BYTES, stream, people, people_count, seq_offsets, F, K, max_age, min_hits,
-                     iou_threshold, max_tracks, update_on_empty, tracks, track_count, status);
+                     iou_threshold, max_tracks, update_on_empty, tracks, track_count, status, state);
   return pmce_check_launch(what);
+}
+
+}  // namespace
+
+extern "C" int pmce_sort_track_f64(const double* people, const int* people_count, const int* seq_offsets_host, const int* seq_offsets,
+                                   int F, int K, int S, int max_age, int min_hits, double iou_threshold, int max_tracks,
+                                   int update_on_empty, double* tracks, int* track_count, int* status, hipStream_t stream) {
+  return sort_track_launch("sort_track_f64", people, people_count, seq_offsets_host, seq_offsets, F, K, S, max_age, min_hits,
+                           iou_threshold, max_tracks, update_on_empty, tracks, track_count, status, nullptr, stream);
+}
+
+extern "C" size_t pmce_sort_state_bytes(void) { return SORT_STATE_BYTES; }
+
+extern "C" int pmce_sort_track_resume_f64(const double* people, const int* people_count, const int* seq_offsets_host,
+                                          const int* seq_offsets, int F, int K, int S, int max_age, int min_hits, double iou_threshold,
+                                          int max_tracks, int update_on_empty, double* tracks, int* track_count, int* status, void* state,
+                                          hipStream_t stream) {
+  const char* what = "sort_track_resume_f64";
+  PMCE_REQUIRE(state, "%s: null pointer (state)", what);
+  PMCE_REQUIRE(reinterpret_cast<uintptr_t>(state) % 8 == 0, "%s: state must be aligned to 8 bytes", what);
+  return sort_track_launch(what, people, people_count, seq_offsets_host, seq_offsets, F, K, S, max_age, min_hits, iou_threshold,
+                           max_tracks, update_on_empty, tracks, track_count, status, static_cast<unsigned char*>(state), stream);
 }
 
 extern "C" int pmce_tracklet_boxes_f64(const double* tracks, const int* index, int total, int n, double* out, hipStream_t stream) {

@@ -15,6 +15,8 @@ in, what the demo saves per person out - ``pred_cam``, ``mesh``, ``bboxes`` (``f
     outs = demo.run_folder(model, "video_frames/", tracker.Tracker(yolo_net), pose, extractor)  # load_frames, then run_frames
     names = demo.save_frames("out_frames/", video)                                             # %06d.jpg, encoded on the device
     outs = demo.render_folder(model, "video_frames/", "out_frames/", trk, pose, extractor, renderer, input_folder="in_frames/")   # folder in, folders out
+    outs = demo.render_folder(model, "video_frames/", "out_frames/", trk, pose, extractor, renderer, frames_per_pass=128)        # any length: 128 frames on the device at a time
+    for first, frames_u8, names in demo.iter_frames("video_frames/", 128): ...                 # load_frames in steps
 
 Per frame k the demo builds one window (``streaming.demo_window_list``), prepares the fit target from the window's middle frame
 (csrc/demo_prep.hip: add_pelvis_and_neck, get_bbox, process_bbox, j2d_processing), runs the model on the window and fits the
@@ -232,7 +234,21 @@ def crop_tracklets(frames, tracklets, scale: float = 1.1, size: int = 224, chann
     A tracklet without a usable frame keeps no row."""
     from . import crops
     crops.check_patch_args(frames, np.zeros(0, np.int32), np.zeros((0, 4)), scale, size, channel_order)
-    F = int(frames.shape[0])
+    ids = _tracklet_frame_ids(tracklets, int(frames.shape[0]))
+    if not isinstance(frames, torch.Tensor) or not frames.is_cuda:
+        frames = torch.as_tensor(np.ascontiguousarray(frames)).to(torch.device("cuda", torch.cuda.current_device()))
+    res = _trim_tracklets(tracklets, ids, frames.device, vis_thresh)
+    out = crops.crop_patches(frames, res.pop("frame_index"), res.pop("rows"), scale=scale, size=size, channel_order=channel_order,
+                             return_raw=return_raw)
+    res.update(patches=out[0], status=out[-1])
+    if return_raw:
+        res["raw"] = out[1]
+    return res
+
+
+def _tracklet_frame_ids(tracklets, F):
+    """``crop_tracklets``' checks of [(keypoints[N_i,17,3], frame_ids[N_i]), ...] against a video of F frames -> the ids as int64 arrays."""
+    from . import crops
     ids = []
     for i, (kp, fid) in enumerate(tracklets):
         crops.check_keypoints(kp)
@@ -242,9 +258,15 @@ def crop_tracklets(frames, tracklets, scale: float = 1.1, size: int = 224, chann
         if fid.size and (fid.min() < 0 or fid.max() >= F):
             raise ValueError(f"tracklet {i}: frame_ids run {int(fid.min())}..{int(fid.max())}, there are {F} frames")
         ids.append(fid.astype(np.int64))
-    if not isinstance(frames, torch.Tensor) or not frames.is_cuda:
-        frames = torch.as_tensor(np.ascontiguousarray(frames)).to(torch.device("cuda", torch.cuda.current_device()))
-    dev = frames.device
+    return ids
+
+
+def _trim_tracklets(tracklets, ids, dev, vis_thresh):
+    """``crop_tracklets`` up to the cut, which needs no frame: the boxes over whole tracklets (``crops.tracklet_boxes`` interpolates over
+    unusable frames wherever they lie), the spans - the one host read - and every tracklet trimmed to its span -> ``crop_tracklets``'
+    dict without 'patches' and 'status', plus the cut's job table: 'frame_index' (host, int32 [sum n_i]) and 'rows' (the boxes, fp64
+    [sum n_i, 4] on the device)."""
+    from . import crops
     kps = [torch.as_tensor(kp).to(device=dev, dtype=torch.float32) for kp, _ in tracklets]
     results = [crops.tracklet_boxes(kp, vis_thresh) for kp in kps]
     spans = torch.stack([r[2] for r in results]).cpu().numpy() if results else np.zeros((0, 2), np.int64)     # the one host wait
@@ -256,11 +278,7 @@ def crop_tracklets(frames, tracklets, scale: float = 1.1, size: int = 224, chann
     offsets = np.concatenate([[0], np.cumsum([len(f) for f in ids])]).astype(np.int64)
     fi = np.concatenate(ids).astype(np.int32) if ids else np.zeros(0, np.int32)
     bx = torch.cat(boxes) if boxes else torch.zeros(0, 4, device=dev, dtype=torch.float64)
-    out = crops.crop_patches(frames, fi, bx, scale=scale, size=size, channel_order=channel_order, return_raw=return_raw)
-    res = {"patches": out[0], "status": out[-1], "offsets": offsets, "keypoints": kps, "frame_ids": ids, "spans": spans, "boxes": boxes}
-    if return_raw:
-        res["raw"] = out[1]
-    return res
+    return {"offsets": offsets, "keypoints": kps, "frame_ids": ids, "spans": spans, "boxes": boxes, "frame_index": fi, "rows": bx}
 
 
 @torch.no_grad()
@@ -327,8 +345,14 @@ def load_frames(folder, device=None, strict: bool = True, chunk: int = 32, entro
     (``cv2.imread`` would rotate such a file; ffmpeg's frames carry none).  ``chunk``: images per round of the decoder (``jpeg.decode``; 9.4 MB of
     workspace per 1080p image).  ``entropy``: ``jpeg.decode``'s - "auto" gives files without restart markers, which is what ffmpeg
     writes, the entropy stage with many lanes per scan; "serial" and "parallel" force one stage.  The same frames either way."""
+    names = _frame_names(folder)
+    frames = _decode_files(folder, names, device, strict, chunk, entropy)
+    return frames, (int(frames.shape[2]), int(frames.shape[1])), names
+
+
+def _frame_names(folder):
+    """The JPEG files of ``folder`` in frame order (sorted by name); a .png and an empty folder are ValueErrors."""
     import os
-    from . import jpeg
     entries = sorted(os.listdir(folder))
     png = [x for x in entries if x.lower().endswith(".png")]
     if png:
@@ -336,6 +360,14 @@ def load_frames(folder, device=None, strict: bool = True, chunk: int = 32, entro
     names = [x for x in entries if x.lower().endswith((".jpg", ".jpeg"))]
     if not names:
         raise ValueError(f"{folder}: no .jpg or .jpeg file")
+    return names
+
+
+def _decode_files(folder, names, device, strict, chunk, entropy):
+    """Read ``names`` of ``folder`` from disk and decode them by one ``jpeg.decode`` call -> frames uint8 [n, H, W, 3]; ``strict`` as
+    ``load_frames`` has it."""
+    import os
+    from . import jpeg
     files = []
     for x in names:
         with open(os.path.join(folder, x), "rb") as fh:
@@ -349,15 +381,138 @@ def load_frames(folder, device=None, strict: bool = True, chunk: int = 32, entro
             what = " and ".join(w for bit, w in ((jpeg.STATUS_TRUNCATED, "truncated"), (jpeg.STATUS_CORRUPT, "corrupt"),
                                                 (jpeg.STATUS_RECORD, "not decodable")) if st[bad[0]] & bit)
             raise ValueError(f"{os.path.join(folder, names[int(bad[0])])}: the scan is {what} (status {int(st[bad[0]])})")
-    return frames, (int(frames.shape[2]), int(frames.shape[1])), names
+    return frames
+
+
+def check_frames_per_pass(frames_per_pass) -> int:
+    if isinstance(frames_per_pass, bool) or not isinstance(frames_per_pass, (int, np.integer)) or int(frames_per_pass) < 1:
+        raise ValueError(f"frames_per_pass must be a whole number >= 1 (got {frames_per_pass!r})")
+    return int(frames_per_pass)
+
+
+def iter_frames(folder, frames_per_pass, device=None, strict: bool = True, chunk: int = 32, entropy: str = "auto"):
+    """``load_frames`` in steps, for a video that does not fit on the device: a generator of (first_index, frames uint8 [n, H, W, 3],
+    names) over the folder's files in frame order, ``frames_per_pass`` files per step (the last step has the rest).  Per step the files
+    are read from disk, uploaded and decoded, so the host holds one step's files and the device one step's frames; the caller drops a
+    chunk before it asks for the next.  The folder's rules are ``load_frames``' own; all steps must have one size - a file of another
+    size is a ValueError naming it.  The chunks in a row are the frames ``load_frames`` returns, to the bit."""
+    import os
+    from . import jpeg
+    k = check_frames_per_pass(frames_per_pass)
+    names = _frame_names(folder)
+    shape = None
+    for first in range(0, len(names), k):
+        part = names[first:first + k]
+        frames = _decode_files(folder, part, device, strict, chunk, entropy)
+        if shape is None:
+            shape = tuple(frames.shape[1:])
+        elif tuple(frames.shape[1:]) != shape:
+            for x in part:                                   # the error path only: parse again to name the file
+                with open(os.path.join(folder, x), "rb") as fh:
+                    hd = jpeg.parse(fh.read(), os.path.join(folder, x))
+                if (hd.height, hd.width) != shape[:2]:
+                    raise ValueError(f"{hd.name}: {hd.width} x {hd.height}, but {os.path.join(folder, names[0])} is {shape[1]} x {shape[0]}: "
+                                     f"all files of one folder must have one size")
+        yield first, frames, part
+        del frames                       # before the next step decodes: one chunk at a time, if the caller dropped its own name too
+
+
+def plan_passes(frame_index, num_frames: int, frames_per_pass: int):
+    """The chunk table of a pass, on the host: frame_index int [N] (the frame of every job row, any order), a video of ``num_frames``
+    frames cut every ``frames_per_pass`` -> [(first, n, rows int64 [m], relative int32 [m]), ...], one entry per chunk in frame order:
+    the rows whose frame lies in first..first + n - 1, in row order, and their frame counted from ``first``.  Every row is in exactly
+    one chunk."""
+    k = check_frames_per_pass(frames_per_pass)
+    fi = np.asarray(frame_index, dtype=np.int64).reshape(-1)
+    if fi.size and (fi.min() < 0 or fi.max() >= num_frames):
+        raise ValueError(f"frame_index runs {int(fi.min())}..{int(fi.max())}, there are {num_frames} frames")
+    order = np.argsort(fi // k, kind="stable")
+    cuts = np.searchsorted((fi // k)[order], np.arange(-(-int(num_frames) // k) + 1))
+    return [(c * k, min(k, int(num_frames) - c * k), order[cuts[c]:cuts[c + 1]], (fi[order[cuts[c]:cuts[c + 1]]] - c * k).astype(np.int32))
+            for c in range(len(cuts) - 1)]
 
 
 def run_folder(model, folder, tracker, pose, extractor, device=None, strict: bool = True, chunk: int = 32, entropy=None,
-               **run_frames_kwargs):
+               frames_per_pass=None, **run_frames_kwargs):
     """``load_frames`` then ``run_frames``, with ``img_wh`` taken from the files -> ``run_frames``' dicts.  ``entropy``: passed to
-    ``load_frames``; None leaves it at ``load_frames``' default ("auto")."""
+    ``load_frames``; None leaves it at ``load_frames``' default ("auto").  ``frames_per_pass``: serve a video of any length - only that
+    many frames are on the device at a time (``run_folder_in_passes``); the same results, to the bit."""
+    if frames_per_pass is not None:
+        return run_folder_in_passes(model, folder, tracker, pose, extractor, frames_per_pass, device=device, strict=strict, chunk=chunk,
+                                    entropy=entropy, **run_frames_kwargs)[0]
     frames, img_wh, _ = load_frames(folder, device=device, strict=strict, chunk=chunk, **({} if entropy is None else dict(entropy=entropy)))
     return run_frames(model, frames, tracker, pose, extractor, img_wh, **run_frames_kwargs)
+
+
+@torch.no_grad()
+def run_folder_in_passes(model, folder, tracker, pose, extractor, frames_per_pass, device=None, strict: bool = True, chunk: int = 32,
+                         entropy=None, min_frames: int = 25, extract_batch: int = 256, crop_scale: float = 1.1, crop_size: int = 224,
+                         channel_order: str = "rgb", vis_thresh: float = 0.3, **run_tracklets_kwargs):
+    """``run_folder`` for a video of any length: two passes over ``iter_frames``, ``frames_per_pass`` frames on the device at a time ->
+    (``run_frames``' dicts, img_wh, a function that starts another pass over the folder).
+
+    Pass A, per chunk: ``tracker.stream().feed(frames, report=True)`` - the resumed SORT - and ``pose`` on the reported boxes while the
+    chunk is there; the keypoints (204 B per reported row) are kept.  Then the stream's ``records(min_frames)``, the kept tracklets'
+    keypoints gathered in record order, and ``crop_tracklets``' boxes and spans over WHOLE tracklets, which interpolate across chunk
+    borders as they do across any frame.  Pass B, per chunk: ``crops.crop_patches`` for the tracklet rows whose frame is in the chunk
+    (``plan_passes``) and ``extractor`` on them, the features scattered to their rows.  Then ``run_tracklets`` as ``run_video`` calls it.
+
+    What stays on the device is per person and frame, not per frame: ``run_tracklets``' results (82,680 B of mesh per row), keypoints,
+    features (8 KB per row) and the tracker's tables (2.5 KB per frame) - about 1/75 of a 1080p frame per person and frame.  The model
+    stage itself is not chunked.  The results equal ``run_folder``'s to the bit if every stage is batch-invariant - it sees other batches
+    here: ``pose`` the rows of a chunk (of every reported person, also those ``min_frames`` drops later), ``extractor`` the rows of a
+    chunk.  The project's ``YOLOv3``, ``TopDownPose`` and ``FeatureExtractor`` are; a caller's torch module need not be."""
+    k = check_frames_per_pass(frames_per_pass)
+    if getattr(pose, "box_format", "cxcywh") != "cxcywh":
+        raise ValueError(f"run_frames: the tracker's boxes are cxcywh, pose.box_format is {pose.box_format!r}")
+    if int(extract_batch) < 1:
+        raise ValueError(f"extract_batch must be >= 1 (got {extract_batch})")
+    from . import crops
+
+    def frames_of():
+        return iter_frames(folder, k, device=device, strict=strict, chunk=chunk, **({} if entropy is None else dict(entropy=entropy)))
+
+    # pass A
+    stream, kp_parts, row_of, F, img_wh, at = tracker.stream(), [], {}, 0, None, 0
+    for first, frames, _ in frames_of():
+        _, _, boxes, rel, pids = stream.feed(frames, report=True)
+        if len(rel):
+            kp_parts.append(pose(frames, rel, boxes)[0])
+        for f, pid in zip(rel.tolist(), pids.tolist()):
+            row_of[(first + f, pid)] = at
+            at += 1
+        F, img_wh = first + int(frames.shape[0]), (int(frames.shape[2]), int(frames.shape[1]))
+        dev = frames.device
+        del frames
+    recs, ids = stream.records(min_frames)
+    if not recs:
+        return [], img_wh, frames_of
+    kp_all = torch.cat(kp_parts)
+    tracklets = []
+    for (_, fid), pid in zip(recs, ids):
+        rows = torch.from_numpy(np.asarray([row_of[(int(f), pid)] for f in fid], np.int64)).to(dev)
+        tracklets.append((kp_all[rows], fid))
+    del kp_all, kp_parts
+    crops.check_patch_args(torch.zeros(0, img_wh[1], img_wh[0], 3, dtype=torch.uint8), np.zeros(0, np.int32), np.zeros((0, 4)), crop_scale,
+                           crop_size, channel_order)
+    c = _trim_tracklets(tracklets, _tracklet_frame_ids(tracklets, F), dev, vis_thresh)
+    _refuse_short(c["offsets"])          # before pass B: no extractor work for a video that is refused
+    fi, bx = c.pop("frame_index"), c.pop("rows")
+    # pass B
+    feats = torch.empty(len(fi), FEAT_DIM, device=dev, dtype=torch.float32)
+    plan = plan_passes(fi, F, k)
+    for (first, frames, _), (p_first, n, rows, rel) in zip(frames_of(), plan):
+        if (first, int(frames.shape[0])) != (p_first, n):
+            raise ValueError(f"{folder}: the files changed between two passes (chunk {p_first}: {frames.shape[0]} frames, {n} before)")
+        if len(rows):
+            rows_dev = torch.from_numpy(rows).to(dev)
+            patches = crops.crop_patches(frames, rel, bx[rows_dev], scale=crop_scale, size=crop_size, channel_order=channel_order)[0]
+            feats[rows_dev] = torch.cat(_extract(extractor, patches, extract_batch)).to(torch.float32)
+        del frames
+    outs = _lift_tracklets(model, c, feats, img_wh, run_tracklets_kwargs)
+    for o, pid in zip(outs, ids):
+        o["person_id"] = pid
+    return outs, img_wh, frames_of
 
 
 def save_frames(folder, frames, first: int = 0, names=None, **encode_kwargs):
@@ -381,11 +536,33 @@ def save_frames(folder, frames, first: int = 0, names=None, **encode_kwargs):
 
 
 def render_folder(model, folder, out_folder, tracker, pose, extractor, renderer, input_folder=None, device=None, strict: bool = True,
-                  chunk: int = 32, entropy=None, order: str = "reference", encode_kwargs=None, **run_frames_kwargs):
+                  chunk: int = 32, entropy=None, order: str = "reference", encode_kwargs=None, frames_per_pass=None, **run_frames_kwargs):
     """Folder in, folder out: ``load_frames``, ``run_frames``, ``render_tracklets`` and ``save_frames`` - the frames are decoded, drawn on
     and encoded on the device.  The overlaid frames go to ``out_folder``; ``input_folder``, if given, receives the input frames again, as
     main/run_demo.py:424-426 writes both folders for ffmpeg.  Both are named ``%06d.jpg`` from 0.  ``renderer``: a ``render.Renderer``
-    or the mesh's face array; ``encode_kwargs``: a dict for ``jpeg.encode``.  -> ``run_frames``' dicts."""
+    or the mesh's face array; ``encode_kwargs``: a dict for ``jpeg.encode``.  -> ``run_frames``' dicts.  ``frames_per_pass``: as
+    ``run_folder``'s, with a third pass over the folder that draws and writes chunk by chunk; the same files, to the byte."""
+    if frames_per_pass is not None:
+        from . import render as R
+        outs, img_wh, frames_of = run_folder_in_passes(model, folder, tracker, pose, extractor, frames_per_pass, device=device,
+                                                       strict=strict, chunk=chunk, entropy=entropy, **run_frames_kwargs)
+        if renderer is not None and not isinstance(renderer, R.Renderer):
+            renderer = R.Renderer(renderer, img_wh)          # once, not per chunk
+        kw = dict(encode_kwargs or {})
+        # pass C: the rows of a tracklet are in frame order, so a chunk's rows are one slice of each
+        for first, frames, _ in frames_of():
+            if input_folder is not None:
+                save_frames(input_folder, frames, first=first, **kw)         # before the chunk is drawn on
+            part, ids = [], []
+            for o in outs:
+                a, b = np.searchsorted(o["frame_ids"], [first, first + int(frames.shape[0])])
+                part.append({k: o[k][a:b] for k in ("mesh", "orig_cam", "bboxes")})
+                ids.append(o["frame_ids"][a:b] - first)
+            if sum(len(i) for i in ids) or renderer is None:         # (no renderer: render_tracklets' own error)
+                frames = render_tracklets(part, frames, img_wh, frame_ids=ids, renderer=renderer, order=order, inplace=True)
+            save_frames(out_folder, frames, first=first, **kw)
+            del frames
+        return outs
     frames, img_wh, _ = load_frames(folder, device=device, strict=strict, chunk=chunk, **({} if entropy is None else dict(entropy=entropy)))
     outs = run_frames(model, frames, tracker, pose, extractor, img_wh, **run_frames_kwargs)
     rendered = render_tracklets(outs, frames, img_wh, renderer=renderer, order=order)
@@ -408,18 +585,32 @@ def run_video(model, frames, tracklets, extractor, img_wh, extract_batch: int = 
     if len(tracklets) == 0:
         return []
     c = crop_tracklets(frames, tracklets, scale=crop_scale, size=crop_size, channel_order=channel_order, vis_thresh=vis_thresh)
-    patches, off = c["patches"], c["offsets"]
-    short = [i for i in range(len(tracklets)) if off[i + 1] - off[i] < SEQLEN]
-    if short:                            # before the extractor runs: run_tracklets' own error
+    _refuse_short(c["offsets"])          # before the extractor runs
+    return _lift_tracklets(model, c, torch.cat(_extract(extractor, c["patches"], extract_batch)), img_wh, run_tracklets_kwargs)
+
+
+def _refuse_short(off):
+    """``run_tracklets``' own error for a tracklet shorter than a window after trimming, from the row ranges alone."""
+    short = [i for i in range(len(off) - 1) if off[i + 1] - off[i] < SEQLEN]
+    if short:
         raise ValueError(f"tracklet {short[0]}: the demo's window list needs at least {SEQLEN} frames (got {int(off[short[0] + 1] - off[short[0]])})")
+
+
+def _extract(extractor, patches, extract_batch):
+    """``extractor`` on batches of ``extract_batch`` patches -> the list of its results, each checked to be [n, 2048]."""
     feats = []
     for k in range(0, patches.shape[0], int(extract_batch)):
         f = extractor(patches[k:k + int(extract_batch)])
         if f.ndim != 2 or f.shape[0] != min(int(extract_batch), patches.shape[0] - k) or f.shape[1] != FEAT_DIM:
             raise ValueError(f"the extractor must return [n, {FEAT_DIM}] (got {tuple(f.shape)})")
         feats.append(f)
-    feats = torch.cat(feats)
-    outs = run_tracklets(model, [(c["keypoints"][i], feats[int(off[i]):int(off[i + 1])]) for i in range(len(tracklets))], img_wh,
+    return feats
+
+
+def _lift_tracklets(model, c, feats, img_wh, run_tracklets_kwargs):
+    """``run_tracklets`` on the trimmed keypoints of ``c`` (``crop_tracklets``' dict) and features [sum n_i, 2048], 'frame_ids' added."""
+    off = c["offsets"]
+    outs = run_tracklets(model, [(c["keypoints"][i], feats[int(off[i]):int(off[i + 1])]) for i in range(len(off) - 1)], img_wh,
                          **run_tracklets_kwargs)
     for o, fid in zip(outs, c["frame_ids"]):
         o["frame_ids"] = fid

@@ -6,6 +6,9 @@ the detector's rows on (main/run_demo.py:199-215) - non-maximum suppression, SOR
     tracks, track_count, status = tracker.sort_tracks(ppl, ppl_count)     # fp64 [F, 64, 5] = (x1, y1, x2, y2, id) in report order
     tracklets, ids = tracker.tracklet_records(tracks, track_count)        # [(boxes fp64 [N_i, 4] cxcywh, frame_ids int64 [N_i]), ...]
     tracklets, ids = tracker.Tracker(yolo.YOLOv3.from_darknet_weights(path))(frames_u8)      # the chain; demo.pose_tracklets takes it
+    state = tracker.SortState()                                           # a tracker that can be fed: the trackers live in a device record
+    tracks, track_count, status = tracker.sort_tracks(ppl, ppl_count, state=state)   # ... of this piece; the bits of the one launch over all pieces
+    stream = tracker.Tracker(det).stream(); stream.feed(frames_a); stream.feed(frames_b); tracklets, ids = stream.records()
                                      # (a detector built with precision="f16" is taken as it is: its rows are fp32 too, nothing here changes)
 
 The algorithms are written from the published texts (the PyTorch-YOLOv3 lineage's ``non_max_suppression``, Bewley's ``sort.py`` over
@@ -107,14 +110,58 @@ def check_seq_offsets(seq_offsets, F):
     return np.ascontiguousarray(s, dtype=np.int32)
 
 
+SORT_ARGS = ("max_age", "min_hits", "iou_threshold", "max_tracks", "update_on_empty")
+
+
+class SortState:
+    """SORT's trackers between two ``sort_tracks(..., state=)`` calls: ``n_seq`` records of ``pmce_sort_state_bytes()`` bytes on the
+    device (include/pmce_hip.h has the layout), all zero = fresh.  The buffer is made at the first use, on ``device`` or else on the
+    device of that call's ``people``.  The state remembers the arguments of its first use - the record does not hold them, and a piece
+    tracked under another ``max_age`` would silently be another tracker - and how many frames each sequence has seen (``frames``, host)."""
+
+    def __init__(self, n_seq: int = 1, device=None):
+        self.n_seq = _whole(n_seq, 1, 1 << 20, "n_seq")
+        self.device = None if device is None else torch.device(device)
+        self.buffer, self.args = None, None
+        self.frames = np.zeros(self.n_seq, np.int64)
+
+    def bind(self, n_seq: int, **args):
+        """The check before every use: ``n_seq`` sequences, and SORT_ARGS as on the first use (which this call is, if none was)."""
+        if int(n_seq) != self.n_seq:
+            raise ValueError(f"the state holds n_seq = {self.n_seq} sequence(s), the call has {int(n_seq)}")
+        args = {k: (float(args[k]) if k == "iou_threshold" else int(args[k])) for k in SORT_ARGS}
+        if self.args is None:
+            self.args = args
+        for k in SORT_ARGS:
+            if args[k] != self.args[k]:
+                raise ValueError(f"{k} = {args[k]!r}, but this state was first used with {k} = {self.args[k]!r}: one state, one set of arguments")
+
+    def buffer_on(self, dev):
+        if self.device is not None and self.device != dev:
+            raise ValueError(f"the state is on {self.device}, the call on {dev}")
+        if self.buffer is None:
+            self.device = dev
+            self.buffer = torch.zeros(self.n_seq, int(_lib.load().pmce_sort_state_bytes()), device=dev, dtype=torch.uint8)
+        return self.buffer
+
+    def clone(self):
+        c = SortState(self.n_seq, self.device)
+        c.buffer = None if self.buffer is None else self.buffer.clone()
+        c.args = None if self.args is None else dict(self.args)
+        c.frames = self.frames.copy()
+        return c
+
+
 @torch.no_grad()
 def sort_tracks(people, people_count, seq_offsets=None, max_age: int = 1, min_hits: int = 3, iou_threshold: float = 0.3,
-                max_tracks: int = 64, update_on_empty: bool = False):
+                max_tracks: int = 64, update_on_empty: bool = False, state=None):
     """people fp64 [F, K <= 64, 5] = (x1, y1, x2, y2, score), people_count int32 [F] (device) -> (tracks fp64 [F, max_tracks, 5] =
     (x1, y1, x2, y2, id) in sort.py's report order, track_count int32 [F], status int32 [F]; 1 = a new tracker did not fit into
     ``max_tracks``) by ONE pmce_sort_track_f64 launch, no host wait.  seq_offsets [S + 1] over frames: several videos in one launch,
     one wave each, ids from 1 per video.  A frame without detections leaves the tracker untouched (multi_person_tracker's rule) unless
-    ``update_on_empty``."""
+    ``update_on_empty``.  ``state``: a ``SortState`` - the frames are the next piece of each sequence, tracked by ONE
+    pmce_sort_track_resume_f64 launch from the state's records, which are updated in place; the outputs are this piece's, and the pieces'
+    outputs in a row are bit for bit those of one launch over the whole.  No host wait either way."""
     shape = tuple(getattr(people, "shape", ()))
     if not isinstance(people, torch.Tensor) or people.dtype != torch.float64 or len(shape) != 3 or shape[2] != 5 or not 1 <= shape[1] <= MAX_KEEP:
         raise ValueError(f"people must be a float64 tensor [F, K in 1..{MAX_KEEP}, 5] (got {getattr(people, 'dtype', type(people).__name__)} {shape})")
@@ -127,6 +174,11 @@ def sort_tracks(people, people_count, seq_offsets=None, max_age: int = 1, min_hi
     if not np.isfinite(float(iou_threshold)):
         raise ValueError(f"iou_threshold must be finite (got {iou_threshold!r})")
     seq = check_seq_offsets(seq_offsets, F)
+    if state is not None:
+        if not isinstance(state, SortState):
+            raise ValueError(f"state must be a SortState (got {type(state).__name__})")
+        state.bind(len(seq) - 1 if seq is not None else 1, max_age=max_age, min_hits=min_hits, iou_threshold=iou_threshold, max_tracks=T,
+                   update_on_empty=1 if update_on_empty else 0)
     if not people.is_cuda:
         people = people.to(torch.device("cuda", torch.cuda.current_device()))
     dev = people.device
@@ -135,6 +187,16 @@ def sort_tracks(people, people_count, seq_offsets=None, max_age: int = 1, min_hi
     track_count = torch.empty(F, device=dev, dtype=torch.int32)
     status = torch.empty(F, device=dev, dtype=torch.int32)
     seq_dev = torch.from_numpy(seq).to(dev) if seq is not None else None
+    if state is not None:
+        buf = state.buffer_on(dev)
+        with torch.cuda.device(dev):
+            if F:
+                _lib.check(_lib.load().pmce_sort_track_resume_f64(
+                    _lib.ptr(people), _lib.ptr(people_count), seq.ctypes.data_as(C.POINTER(C.c_int)) if seq is not None else None,
+                    _lib.ptr(seq_dev), F, K, state.n_seq, int(max_age), int(min_hits), float(iou_threshold), T, 1 if update_on_empty else 0,
+                    _lib.ptr(tracks), _lib.ptr(track_count), _lib.ptr(status), _lib.ptr(buf), _lib.current_stream()), "sort_track_resume_f64")
+        state.frames += np.diff(seq) if seq is not None else F
+        return tracks, track_count, status
     with torch.cuda.device(dev):
         if F:
             _lib.check(_lib.load().pmce_sort_track_f64(_lib.ptr(people), _lib.ptr(people_count),
@@ -162,6 +224,18 @@ def record_index(ids, counts, min_frames, seq):
     return out
 
 
+def _gather_boxes(tracks, flat):
+    """tracks fp64 [F, T, 5] (device, contiguous) and flat row indices into [F * T] -> their squared boxes fp64 [n, 4], one launch."""
+    F, T, dev = tracks.shape[0], tracks.shape[1], tracks.device
+    boxes = torch.empty(len(flat), 4, device=dev, dtype=torch.float64)
+    if len(flat):
+        index = torch.from_numpy(np.asarray(flat, np.int32)).to(dev)
+        with torch.cuda.device(dev):
+            _lib.check(_lib.load().pmce_tracklet_boxes_f64(_lib.ptr(tracks), _lib.ptr(index), F * T, len(flat), _lib.ptr(boxes),
+                                                           _lib.current_stream()), "tracklet_boxes_f64")
+    return boxes
+
+
 def _records(tracks, track_count, min_frames, seq_offsets, statuses=()):
     shape = tuple(getattr(tracks, "shape", ()))
     if not isinstance(tracks, torch.Tensor) or tracks.dtype != torch.float64 or len(shape) != 3 or shape[2] != 5 or not tracks.is_cuda:
@@ -182,13 +256,7 @@ def _records(tracks, track_count, min_frames, seq_offsets, statuses=()):
         extra.append(packed[at:at + s.numel()].astype(np.int64))
         at += s.numel()
     per_seq = record_index(ids, counts, min_frames, [0, F] if seq is None else seq)
-    flat = [i for rows, _, _ in per_seq for r in rows for i in r]
-    boxes = torch.empty(len(flat), 4, device=dev, dtype=torch.float64)
-    if flat:
-        index = torch.from_numpy(np.asarray(flat, np.int32)).to(dev)
-        with torch.cuda.device(dev):
-            _lib.check(_lib.load().pmce_tracklet_boxes_f64(_lib.ptr(tracks), _lib.ptr(index), F * T, len(flat), _lib.ptr(boxes),
-                                                           _lib.current_stream()), "tracklet_boxes_f64")
+    boxes = _gather_boxes(tracks, [i for rows, _, _ in per_seq for r in rows for i in r])
     res, at = [], 0
     for rows, frames, pids in per_seq:
         recs = []
@@ -261,6 +329,10 @@ class Tracker:
         """frames uint8 [F, H, W, 3] (a host array is uploaded once) -> (tracklets, ids) as ``tracklet_records`` returns them."""
         ppl, cnt, nms_status = self.detect(frames_u8)
         tracks, track_count, sort_status = sort_tracks(ppl, cnt, **self.sort_args)
+        return self._checked_records(tracks, track_count, nms_status, sort_status, min_frames)
+
+    def _checked_records(self, tracks, track_count, nms_status, sort_status, min_frames):
+        """The records of a whole video's tables and the cap errors, naming the frame: the one host read."""
         (recs, ids), (ns, ss) = _records(tracks, track_count, self.min_frames if min_frames is None else min_frames, None,
                                          statuses=(nms_status, sort_status))
         bad = np.nonzero(ns)[0]
@@ -273,3 +345,47 @@ class Tracker:
             raise ValueError(f"frame {int(bad[0])}: SORT exceeded max_tracks = {self.sort_args['max_tracks']} and dropped a detection "
                              f"({bad.size} such frame(s) in all)")
         return recs, ids
+
+    def stream(self):
+        """A ``TrackerStream``: this tracker fed chunk by chunk, for videos whose frames do not fit on the device at once."""
+        return TrackerStream(self)
+
+
+class TrackerStream:
+    """``Tracker`` on frames that arrive in chunks: ``feed`` runs letterbox, detector, NMS and the resumed SORT on a chunk and keeps its
+    tracks [n, max_tracks, 5], counts and status words (2.5 KB per frame at 64 tracks) on the device; ``records`` is ``Tracker.__call__``
+    of the concatenated frames, through the same ``_records``.  The frames themselves are not kept."""
+
+    def __init__(self, tracker):
+        self.tracker, self.state, self.frames = tracker, SortState(1), 0
+        self.tables = []                 # per chunk (tracks, track_count, nms_status, sort_status)
+
+    @torch.no_grad()
+    def feed(self, frames_u8, report: bool = False):
+        """frames uint8 [n, H, W, 3], the next n frames -> (tracks fp64 [n, max_tracks, 5], track_count int32 [n]) of the chunk, no host
+        wait.  ``report``: one host read of the chunk's ids and counts, and three more results for every reported row of the chunk, frame
+        after frame in report order: boxes fp64 [m, 4] = (cx, cy, s, s) on the device (pmce_tracklet_boxes_f64: the records' boxes),
+        frame_index int32 [m] counted from the chunk's first frame and person ids int64 [m] (host)."""
+        ppl, cnt, nms_status = self.tracker.detect(frames_u8)
+        tracks, track_count, sort_status = sort_tracks(ppl, cnt, state=self.state, **self.tracker.sort_args)
+        self.tables.append((tracks, track_count, nms_status, sort_status))
+        self.frames += int(tracks.shape[0])
+        if not report:
+            return tracks, track_count
+        n, T = int(tracks.shape[0]), int(tracks.shape[1])
+        packed = torch.cat([tracks[:, :, 4].reshape(-1), track_count.double()]).cpu().numpy()
+        ids = packed[:n * T].reshape(n, T).astype(np.int64)
+        counts = np.clip(packed[n * T:].astype(np.int64), 0, T)
+        frame_index = np.repeat(np.arange(n, dtype=np.int32), counts)
+        slot = np.concatenate([np.arange(c) for c in counts]).astype(np.int64) if n else np.zeros(0, np.int64)
+        flat = frame_index.astype(np.int64) * T + slot
+        return tracks, track_count, _gather_boxes(tracks, flat), frame_index, ids.reshape(-1)[flat]
+
+    @torch.no_grad()
+    def records(self, min_frames=None):
+        """(tracklets, ids) exactly as ``Tracker.__call__`` returns them for all frames fed so far; its cap errors name the frame
+        counted from the first frame fed."""
+        if not self.tables:
+            raise ValueError("records: no frames were fed")
+        cat = [torch.cat([t[i] for t in self.tables]) for i in range(4)]
+        return self.tracker._checked_records(cat[0], cat[1], cat[2], cat[3], min_frames)
