@@ -1150,6 +1150,38 @@ int pmce_jpeg_encode_entropy(const short* coefficients, int n_frames, long long 
                              unsigned char* data, long long data_bytes, long long* offsets, int* status, long long first_frame, int stage,
                              pmce_stream_t stream);
 
+/* ---------------------------------------------------------------------------------------------------------
+ * The demo's debug overlay (csrc/overlay.hip, csrc/overlay_cover.hpp): the tracker's boxes and ids and the pose stage's 2D skeletons
+ * drawn on uint8 frames[n_frames][height][width][3], in place.  A row is one person in one frame; rows of a frame are drawn in the
+ * order given, inside a row the box's edges (top, right, bottom, left), the label, the limbs in the skeleton's order, the discs in
+ * keypoint order; the last primitive that covers a pixel decides it, and the pixel is blended once:
+ * (alpha colour + (255 - alpha) pixel + 127) / 255.  The rules are integer: a coordinate v becomes rint(16 v),
+ * pixel (x, y) has its centre at (16 x + 8, 16 y + 8); a segment of thickness t covers the centres within 8 t units of it, a disc those
+ * within 16 radius of the keypoint; the label is the id in decimal, a 5 x 7 font in 6 x 8 cells of label_scale-sized blocks (the glyph
+ * at columns 1..5, rows 1..7 of its cell) in text_color on the person's colour, its left column floor(x1), its rows ending above
+ * row floor(y1), clamped into the frame (none if it is larger than the frame).  Integer atomics only: the same bytes whatever the
+ * launch order, the other rows and frames of the call, and the chunking.  No host wait.
+ *   frame_index int32 [n_rows] (device); frame_index_host: NULL, or the same table on the host when it is ASCENDING (rows of a frame
+ *     still in drawing order) - a chunk of frames then launches its own rows only, otherwise every chunk launches all rows and the
+ *     kernel skips those of other chunks; boxes fp64 [n_rows][4] or NULL, box_format 0 (x1, y1, x2, y2), 1 (cx, cy, w, h), 2 (x, y, w, h);
+ *   ids int64 [n_rows] or NULL, 0 <= id < 10^9: the label, and the colour palette[id % n_palette] (palette[0] without ids);
+ *   keypoints fp64 [n_rows][n_keypoints][keypoint_dim = 2 or 3] or NULL; a keypoint is drawn when it is finite and, with a third
+ *     component, that score is >= score_thresh; skeleton int32 [n_limbs][2] (device): a limb needs both its ends drawn;
+ *   font uint8 [10][7] (device): a glyph's rows, bit 4 the left column; palette uint8 [n_palette][3] (device), stored channel order;
+ *   text_color: three bytes on the HOST; thickness, radius 1..64; label_scale 1..64; alpha 0..255;
+ *   status int32 [n_rows] (device, out): 1 = a non-finite box, a box with w <= 0 or h <= 0, a non-finite keypoint (that primitive, and a
+ *     limb that names the keypoint, are skipped) or an id out of range (the row is skipped); 2 = a primitive with an endpoint beyond
+ *     |v| > 2^14 px was dropped; 4 = frame_index outside 0 .. n_frames - 1 (the row is skipped);
+ *   workspace: 4-byte aligned device memory of at least pmce_overlay_workspace_bytes(width, height, 1) bytes, one 32-bit key per pixel
+ *     of a chunk; the frames are processed in chunks of as many as fit.  Its content on entry does not matter.  width, height <= 8192.
+ * The query returns 0 (and sets the error string) for arguments out of range. */
+size_t pmce_overlay_workspace_bytes(int width, int height, int chunk_frames);
+int pmce_draw_overlays(unsigned char* frames, int n_frames, int width, int height, const int* frame_index_host, const int* frame_index,
+                       const double* boxes, int box_format, const long long* ids, const double* keypoints, int n_keypoints, int keypoint_dim,
+                       const int* skeleton, int n_limbs, double score_thresh, int thickness, int radius, int label_scale,
+                       const unsigned char* font, const unsigned char* palette, int n_palette, const unsigned char* text_color, int alpha,
+                       int n_rows, int* status, void* workspace, size_t workspace_bytes, pmce_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -213,6 +213,9 @@ PROTOTYPES = {
     "pmce_jpeg_encode_workspace_bytes": [_i, _l, _i, _i],
     "pmce_jpeg_encode_coefficients": [_f, _l, _i, _i, _i, _i, _i, _i, _f, _f, _l, _s],
     "pmce_jpeg_encode_entropy": [_f, _i, _l, _i, _i, _f, _i, _l, C.c_void_p, C.c_size_t, _f, _l, _f, _f, _l, _i, _s],
+    "pmce_overlay_workspace_bytes": [_i, _i, _i],
+    "pmce_draw_overlays": [_f, _i, _i, _i, C.POINTER(C.c_int), _f, _f, _i, _f, _f, _i, _i, _f, _i, _d, _i, _i, _i, _f, _f, _i, C.POINTER(C.c_ubyte), _i, _i, _f,
+                           C.c_void_p, C.c_size_t, _s],
 }
 _RESTYPES = {
     "pmce_last_error_string": C.c_char_p,
@@ -240,6 +243,7 @@ _RESTYPES = {
     "pmce_yolo_workspace_bytes": C.c_size_t,
     "pmce_jpeg_encode_workspace_bytes": C.c_size_t,
     "pmce_sort_state_bytes": C.c_size_t,
+    "pmce_overlay_workspace_bytes": C.c_size_t,
 }
 
 _lib = None

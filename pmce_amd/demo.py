@@ -17,6 +17,12 @@ in, what the demo saves per person out - ``pred_cam``, ``mesh``, ``bboxes`` (``f
     outs = demo.render_folder(model, "video_frames/", "out_frames/", trk, pose, extractor, renderer, input_folder="in_frames/")   # folder in, folders out
     outs = demo.render_folder(model, "video_frames/", "out_frames/", trk, pose, extractor, renderer, frames_per_pass=128)        # any length: 128 frames on the device at a time
     for first, frames_u8, names in demo.iter_frames("video_frames/", 128): ...                 # load_frames in steps
+    wide = demo.render_tracklets(outs, frames_u8, (1920, 1080), renderer=r, plain=True, sideview=True)   # --render_plain, --sideview: [F,H,2W,3]
+    outs = demo.run_frames(model, frames_u8, trk, pose, extractor, img_wh=(1920, 1080), keep_inputs=True)   # + 'track_boxes', 'keypoints'
+    debug, status = demo.draw_tracklets(outs, frames_u8)                                       # the tracker's boxes and ids, the 2D skeletons
+    outs = demo.render_folder(model, "video_frames/", "out_frames/", trk, pose, extractor, renderer, sideview=True, plain=True,
+                              debug_folder="debug_frames/", obj_folder="out/", pkl_path="out/pmce_output.pkl")   # the demo's output switches
+    demo.save_results("out/pmce_output.pkl", outs); demo.save_meshes("out/", outs, faces)      # --save_pkl, --save_obj
 
 Per frame k the demo builds one window (``streaming.demo_window_list``), prepares the fit target from the window's middle frame
 (csrc/demo_prep.hip: add_pelvis_and_neck, get_bbox, process_bbox, j2d_processing), runs the model on the window and fits the
@@ -320,14 +326,19 @@ def track_video(frames, tracker, min_frames: int = 25):
 
 
 @torch.no_grad()
-def run_frames(model, frames, tracker, pose, extractor, img_wh, min_frames: int = 25, **run_video_kwargs):
+def run_frames(model, frames, tracker, pose, extractor, img_wh, min_frames: int = 25, keep_inputs: bool = False, **run_video_kwargs):
     """The whole demo up to rendering: ``track_video``, then ``pose_tracklets``, then ``run_video`` -> ``run_video``'s dicts, each with
-    'person_id' (the tracker's id) added.  ``tracker``'s boxes are (cx, cy, w, h): ``pose.box_format`` must be "cxcywh"."""
+    'person_id' (the tracker's id) added.  ``tracker``'s boxes are (cx, cy, w, h): ``pose.box_format`` must be "cxcywh".
+    ``keep_inputs``: every dict also carries what the mesh stage was given, row-aligned with 'frame_ids' (trimmed by the same span):
+    'track_boxes' fp64 [N_i,4], the tracker's (cx, cy, s, s), and 'keypoints' fp32 [N_i,17,3] as ``pose_tracklets`` returned them -
+    ``draw_tracklets``' input."""
     if getattr(pose, "box_format", "cxcywh") != "cxcywh":
         raise ValueError(f"run_frames: the tracker's boxes are cxcywh, pose.box_format is {pose.box_format!r}")
     if not isinstance(frames, torch.Tensor) or not frames.is_cuda:
         frames = torch.as_tensor(np.ascontiguousarray(frames)).to(torch.device("cuda", torch.cuda.current_device()))     # one upload for all stages
     boxes, ids = track_video(frames, tracker, min_frames=min_frames)
+    if keep_inputs:
+        run_video_kwargs = dict(run_video_kwargs, track_boxes=[b for b, _ in boxes])
     outs = run_video(model, frames, pose_tracklets(frames, boxes, pose), extractor, img_wh, **run_video_kwargs)
     for o, pid in zip(outs, ids):
         o["person_id"] = pid
@@ -447,7 +458,7 @@ def run_folder(model, folder, tracker, pose, extractor, device=None, strict: boo
 @torch.no_grad()
 def run_folder_in_passes(model, folder, tracker, pose, extractor, frames_per_pass, device=None, strict: bool = True, chunk: int = 32,
                          entropy=None, min_frames: int = 25, extract_batch: int = 256, crop_scale: float = 1.1, crop_size: int = 224,
-                         channel_order: str = "rgb", vis_thresh: float = 0.3, **run_tracklets_kwargs):
+                         channel_order: str = "rgb", vis_thresh: float = 0.3, keep_inputs: bool = False, **run_tracklets_kwargs):
     """``run_folder`` for a video of any length: two passes over ``iter_frames``, ``frames_per_pass`` frames on the device at a time ->
     (``run_frames``' dicts, img_wh, a function that starts another pass over the folder).
 
@@ -461,7 +472,8 @@ def run_folder_in_passes(model, folder, tracker, pose, extractor, frames_per_pas
     features (8 KB per row) and the tracker's tables (2.5 KB per frame) - about 1/75 of a 1080p frame per person and frame.  The model
     stage itself is not chunked.  The results equal ``run_folder``'s to the bit if every stage is batch-invariant - it sees other batches
     here: ``pose`` the rows of a chunk (of every reported person, also those ``min_frames`` drops later), ``extractor`` the rows of a
-    chunk.  The project's ``YOLOv3``, ``TopDownPose`` and ``FeatureExtractor`` are; a caller's torch module need not be."""
+    chunk.  The project's ``YOLOv3``, ``TopDownPose`` and ``FeatureExtractor`` are; a caller's torch module need not be.
+    ``keep_inputs``: as ``run_frames``' - 'track_boxes' and 'keypoints' in every dict."""
     k = check_frames_per_pass(frames_per_pass)
     if getattr(pose, "box_format", "cxcywh") != "cxcywh":
         raise ValueError(f"run_frames: the tracker's boxes are cxcywh, pose.box_format is {pose.box_format!r}")
@@ -509,7 +521,7 @@ def run_folder_in_passes(model, folder, tracker, pose, extractor, frames_per_pas
             patches = crops.crop_patches(frames, rel, bx[rows_dev], scale=crop_scale, size=crop_size, channel_order=channel_order)[0]
             feats[rows_dev] = torch.cat(_extract(extractor, patches, extract_batch)).to(torch.float32)
         del frames
-    outs = _lift_tracklets(model, c, feats, img_wh, run_tracklets_kwargs)
+    outs = _lift_tracklets(model, c, feats, img_wh, run_tracklets_kwargs, [b for b, _ in recs] if keep_inputs else None)
     for o, pid in zip(outs, ids):
         o["person_id"] = pid
     return outs, img_wh, frames_of
@@ -536,19 +548,45 @@ def save_frames(folder, frames, first: int = 0, names=None, **encode_kwargs):
 
 
 def render_folder(model, folder, out_folder, tracker, pose, extractor, renderer, input_folder=None, device=None, strict: bool = True,
-                  chunk: int = 32, entropy=None, order: str = "reference", encode_kwargs=None, frames_per_pass=None, **run_frames_kwargs):
+                  chunk: int = 32, entropy=None, order: str = "reference", encode_kwargs=None, frames_per_pass=None, sideview: bool = False,
+                  plain: bool = False, debug_folder=None, obj_folder=None, pkl_path=None, overlay_kwargs=None, **run_frames_kwargs):
     """Folder in, folder out: ``load_frames``, ``run_frames``, ``render_tracklets`` and ``save_frames`` - the frames are decoded, drawn on
     and encoded on the device.  The overlaid frames go to ``out_folder``; ``input_folder``, if given, receives the input frames again, as
     main/run_demo.py:424-426 writes both folders for ffmpeg.  Both are named ``%06d.jpg`` from 0.  ``renderer``: a ``render.Renderer``
     or the mesh's face array; ``encode_kwargs``: a dict for ``jpeg.encode``.  -> ``run_frames``' dicts.  ``frames_per_pass``: as
-    ``run_folder``'s, with a third pass over the folder that draws and writes chunk by chunk; the same files, to the byte."""
+    ``run_folder``'s, with a third pass over the folder that draws and writes chunk by chunk; the same files, to the byte.
+
+    The reference's output switches: ``sideview`` (--sideview: the written frames are 2W wide, ``render_tracklets``' side view on the
+    right) and ``plain`` (--render_plain: the meshes on black; ``input_folder`` still gets the untouched frames); ``obj_folder``
+    (--save_obj, ``save_meshes``: needs ``renderer``'s faces) and ``pkl_path`` (--save_pkl, ``save_results``).  ``debug_folder`` (what
+    --display is for): ``draw_tracklets`` on the input frames - the tracker's boxes and ids, the 2D skeletons - named ``%06d.jpg``; it
+    turns ``keep_inputs`` on, so the dicts carry 'track_boxes' and 'keypoints'; ``overlay_kwargs``: a dict for ``overlay.draw``.  The
+    three picture folders must differ: their files have the same names."""
+    import os
+    from . import render as R
+    sideview, plain = _flag(sideview, "sideview"), _flag(plain, "plain")
+    named = [(n, os.path.abspath(os.fspath(f))) for n, f in (("out_folder", out_folder), ("input_folder", input_folder),
+                                                              ("debug_folder", debug_folder)) if f is not None]
+    for i, (n, f) in enumerate(named):
+        for m, g in named[:i]:
+            if f == g:
+                raise ValueError(f"{n} and {m} are the same folder ({f}): both write %06d.jpg files, one would replace the other's")
+    if overlay_kwargs is not None and debug_folder is None:
+        raise ValueError("overlay_kwargs are for the debug frames: give debug_folder= too")
+    if obj_folder is not None and renderer is None:
+        raise ValueError("obj_folder needs the mesh's faces: give renderer= (a render.Renderer, or the face array)")
+    views = {k: v for k, v in (("plain", plain), ("sideview", sideview)) if v}           # without the switches: the call it was
+    if debug_folder is not None:
+        run_frames_kwargs = dict(run_frames_kwargs, keep_inputs=True)
+    okw, kw = dict(overlay_kwargs or {}), dict(encode_kwargs or {})
+    faces = None if obj_folder is None else (renderer.faces if isinstance(renderer, R.Renderer) else R._host(renderer))
     if frames_per_pass is not None:
-        from . import render as R
         outs, img_wh, frames_of = run_folder_in_passes(model, folder, tracker, pose, extractor, frames_per_pass, device=device,
                                                        strict=strict, chunk=chunk, entropy=entropy, **run_frames_kwargs)
         if renderer is not None and not isinstance(renderer, R.Renderer):
             renderer = R.Renderer(renderer, img_wh)          # once, not per chunk
-        kw = dict(encode_kwargs or {})
+        keys = ("mesh", "orig_cam", "bboxes") + (("track_boxes", "keypoints") if debug_folder is not None else ())
+        extras = debug_folder is not None or obj_folder is not None      # the debug frames and the .obj files name person and frame
         # pass C: the rows of a tracklet are in frame order, so a chunk's rows are one slice of each
         for first, frames, _ in frames_of():
             if input_folder is not None:
@@ -556,37 +594,165 @@ def render_folder(model, folder, out_folder, tracker, pose, extractor, renderer,
             part, ids = [], []
             for o in outs:
                 a, b = np.searchsorted(o["frame_ids"], [first, first + int(frames.shape[0])])
-                part.append({k: o[k][a:b] for k in ("mesh", "orig_cam", "bboxes")})
+                part.append({k: o[k][a:b] for k in keys})
+                if extras:
+                    part[-1].update(person_id=o["person_id"], frame_ids=o["frame_ids"][a:b])
                 ids.append(o["frame_ids"][a:b] - first)
+            if debug_folder is not None:                                     # on a copy, before the meshes are drawn in place
+                save_frames(debug_folder, draw_tracklets(part, frames, frame_ids=ids, **okw)[0], first=first, **kw)
+            if obj_folder is not None:
+                save_meshes(obj_folder, part, faces)
             if sum(len(i) for i in ids) or renderer is None:         # (no renderer: render_tracklets' own error)
-                frames = render_tracklets(part, frames, img_wh, frame_ids=ids, renderer=renderer, order=order, inplace=True)
+                frames = render_tracklets(part, frames, img_wh, frame_ids=ids, renderer=renderer, order=order,
+                                          **(dict(views) if sideview else dict(views, inplace=True)))
+            elif views:
+                frames = _empty_views(frames, plain, sideview)
             save_frames(out_folder, frames, first=first, **kw)
             del frames
+        if pkl_path is not None:
+            save_results(pkl_path, outs)
         return outs
     frames, img_wh, _ = load_frames(folder, device=device, strict=strict, chunk=chunk, **({} if entropy is None else dict(entropy=entropy)))
     outs = run_frames(model, frames, tracker, pose, extractor, img_wh, **run_frames_kwargs)
-    rendered = render_tracklets(outs, frames, img_wh, renderer=renderer, order=order)
-    kw = dict(encode_kwargs or {})
+    rendered = render_tracklets(outs, frames, img_wh, renderer=renderer, order=order, **views)
     save_frames(out_folder, rendered, **kw)
+    del rendered
     if input_folder is not None:
         save_frames(input_folder, frames, **kw)
+    if debug_folder is not None:
+        save_frames(debug_folder, draw_tracklets(outs, frames, **okw)[0], **kw)
+    if obj_folder is not None:
+        save_meshes(obj_folder, outs, faces)
+    if pkl_path is not None:
+        save_results(pkl_path, outs)
     return outs
+
+
+def _flag(v, name):
+    if not isinstance(v, (bool, np.bool_)):
+        raise ValueError(f"{name} must be True or False (got {v!r})")
+    return bool(v)
+
+
+def _empty_views(frames, plain, sideview):
+    """What ``render_tracklets(plain=, sideview=)`` returns for frames without a person."""
+    zeros = torch.zeros_like(frames) if isinstance(frames, torch.Tensor) else np.zeros_like(frames)
+    left = zeros if plain else frames
+    if not sideview:
+        return left
+    return torch.cat([left, zeros], 2) if isinstance(frames, torch.Tensor) else np.concatenate([left, zeros], 2)
+
+
+def _person_ids(results):
+    """-> (keys, person ids) of ``run_frames``' list, or of a dict by person id."""
+    keys = list(results.keys()) if isinstance(results, dict) else list(range(len(results)))
+    return keys, [int(results[k].get("person_id", k)) for k in keys]
+
+
+def save_results(pkl_path, outs):
+    """--save_pkl (main/run_demo.py:360-373): ``run_frames``' dicts (a list, or a dict by person id) -> a pickle of {person_id:
+    {'pred_cam' [N,3], 'mesh' [N,6890,3], 'bboxes' [N,4], 'frame_ids' [N]}} as numpy arrays - the reference's keys.  Written with the
+    standard ``pickle`` module; the reference writes with joblib, and reading this file with ``joblib.load`` has not been checked.
+    -> the dict written."""
+    import os
+    import pickle
+    keys, pids = _person_ids(outs)
+    if len(set(pids)) != len(pids):
+        raise ValueError(f"save_results: person ids repeat ({pids})")
+    data = {}
+    for k, pid in zip(keys, pids):
+        o = outs[k]
+        data[pid] = {name: np.asarray(o[name].detach().cpu().numpy() if isinstance(o[name], torch.Tensor) else o[name])
+                     for name in ("pred_cam", "mesh", "bboxes", "frame_ids")}
+    folder = os.path.dirname(os.path.abspath(os.fspath(pkl_path)))
+    os.makedirs(folder, exist_ok=True)
+    with open(pkl_path, "wb") as fh:
+        pickle.dump(data, fh, protocol=pickle.HIGHEST_PROTOCOL)
+    return data
+
+
+def save_meshes(obj_folder, outs, faces):
+    """--save_obj (main/run_demo.py:407-411): per person and frame ``obj_folder/meshes/{person_id:04d}/{frame:06d}.obj``.  The
+    reference exports inside its renderer after the flip by Rx(180 deg) and before the side view's rotation (demo/renderer.py:65-74),
+    so the vertices written are (x, -y, -z) of 'mesh'.  The file is ``v x y z`` lines with %.8f, then ``f a b c`` lines, 1-based - this
+    project's layout (trimesh, the reference's exporter, is not at hand: its text will differ in formatting).  The one place where the
+    meshes cross to the host.  -> the files' paths."""
+    import os
+    f = np.asarray(faces)
+    if f.ndim != 2 or f.shape[1] != 3 or not np.issubdtype(f.dtype, np.integer):
+        raise ValueError(f"faces must be an integer array [F, 3] (got {f.dtype} {f.shape})")
+    tail = "".join(f"f {a} {b} {c}\n" for a, b, c in (f.astype(np.int64) + 1).tolist())
+    keys, pids = _person_ids(outs)
+    paths = []
+    for k, pid in zip(keys, pids):
+        o = outs[k]
+        mesh = o["mesh"].detach().cpu().numpy() if isinstance(o["mesh"], torch.Tensor) else np.asarray(o["mesh"])
+        fid = o["frame_ids"] if "frame_ids" in o else np.arange(len(mesh))
+        if len(fid) != len(mesh):
+            raise ValueError(f"person {pid}: {len(fid)} frame ids for {len(mesh)} rows")
+        if f.size and f.max() >= mesh.shape[1]:
+            raise ValueError(f"faces index vertex {int(f.max())}, the meshes have {mesh.shape[1]}")
+        folder = os.path.join(obj_folder, "meshes", f"{pid:04d}")
+        if len(fid):
+            os.makedirs(folder, exist_ok=True)
+        flipped = mesh.astype(np.float64) * np.array([1.0, -1.0, -1.0])
+        for verts, frame in zip(flipped, fid):
+            paths.append(os.path.join(folder, f"{int(frame):06d}.obj"))
+            with open(paths[-1], "w") as fh:
+                fh.write("".join("v %.8f %.8f %.8f\n" % tuple(v) for v in verts.tolist()) + tail)
+    return paths
+
+
+@torch.no_grad()
+def draw_tracklets(results, frames, frame_ids=None, inplace: bool = False, **overlay_kwargs):
+    """The debug view of ``run_frames(keep_inputs=True)``' dicts (a list, or a dict by person id): per row the tracker's box
+    ('track_boxes'), the person's id ('person_id') and the 2D keypoints ('keypoints') drawn on frames uint8 [F,H,W,3] (device) by ONE
+    ``overlay.draw`` call over the concatenated rows.  frame_ids: as ``render_tracklets``'.  The persons of a frame are drawn in
+    ``tracklet_draw_order``'s order - the boxes' top edges are read back once for it, as ``render_tracklets`` does.
+    -> (the frames - a copy unless ``inplace`` -, status int32 [sum N_i] in the rows' own order: ``overlay.STATUS_*``)."""
+    from . import overlay
+    keys, pids = _person_ids(results)
+    for k in keys:
+        if "track_boxes" not in results[k] or "keypoints" not in results[k]:
+            raise ValueError(f"draw_tracklets: tracklet {k!r} has no 'track_boxes' / 'keypoints': run the demo with keep_inputs=True")
+    if not keys or not sum(len(results[k]["keypoints"]) for k in keys):
+        return (frames if inplace else frames.clone()), torch.zeros(0, dtype=torch.int32, device=frames.device)
+    ids = []
+    for k in keys:
+        d = results[k]
+        fid = frame_ids[k] if frame_ids is not None else d.get("frame_ids", np.arange(len(d["keypoints"])))
+        if len(fid) != len(d["keypoints"]) or len(fid) != len(d["track_boxes"]):
+            raise ValueError(f"tracklet {k!r}: {len(fid)} frame ids for {len(d['keypoints'])} keypoint rows, {len(d['track_boxes'])} boxes")
+        ids.append(np.asarray(fid.cpu() if isinstance(fid, torch.Tensor) else fid))
+    dev = frames.device
+    cat = lambda name: torch.cat([torch.as_tensor(results[k][name]).to(dev) for k in keys])  # noqa: E731
+    tops = cat("bboxes")[:, 1].cpu().numpy()
+    frame_index, order = tracklet_draw_order([tops], ids)
+    person = np.concatenate([np.full(len(f), pid, np.int64) for f, pid in zip(ids, pids)])
+    order_dev = torch.from_numpy(order).to(dev)
+    out, st = overlay.draw(frames, frame_index[order], boxes=cat("track_boxes")[order_dev], ids=person[order],
+                           keypoints=cat("keypoints")[order_dev], inplace=inplace, **{"box_format": "cxcywh", **overlay_kwargs})
+    status = torch.empty_like(st)
+    status[order_dev] = st
+    return out, status
 
 
 @torch.no_grad()
 def run_video(model, frames, tracklets, extractor, img_wh, extract_batch: int = 256, crop_scale: float = 1.1, crop_size: int = 224,
-              channel_order: str = "rgb", vis_thresh: float = 0.3, **run_tracklets_kwargs):
+              channel_order: str = "rgb", vis_thresh: float = 0.3, track_boxes=None, **run_tracklets_kwargs):
     """Frames to what the demo saves: ``crop_tracklets``, then ``extractor(patches[k:k + extract_batch])`` -> [n, 2048] (the caller's
     callable on device tensors: the reference's is a torch ResNet, main/run_demo.py:248-259,314-321), then ``run_tracklets`` on the
     trimmed keypoints and those features.  -> ``run_tracklets``' dicts, each with 'frame_ids' (host, int64: the frames its rows belong
-    to) added, ready for ``render_tracklets``.  A tracklet shorter than 16 frames after trimming raises ``run_tracklets``' ValueError."""
+    to) added, ready for ``render_tracklets``.  A tracklet shorter than 16 frames after trimming raises ``run_tracklets``' ValueError.
+    ``track_boxes``: per tracklet the tracker's boxes [N_i,4] (``run_frames``' ``keep_inputs``) - the dicts then also carry them and
+    the keypoints, both trimmed as the rows are."""
     if int(extract_batch) < 1:
         raise ValueError(f"extract_batch must be >= 1 (got {extract_batch})")
     if len(tracklets) == 0:
         return []
     c = crop_tracklets(frames, tracklets, scale=crop_scale, size=crop_size, channel_order=channel_order, vis_thresh=vis_thresh)
     _refuse_short(c["offsets"])          # before the extractor runs
-    return _lift_tracklets(model, c, torch.cat(_extract(extractor, c["patches"], extract_batch)), img_wh, run_tracklets_kwargs)
+    return _lift_tracklets(model, c, torch.cat(_extract(extractor, c["patches"], extract_batch)), img_wh, run_tracklets_kwargs, track_boxes)
 
 
 def _refuse_short(off):
@@ -607,13 +773,20 @@ def _extract(extractor, patches, extract_batch):
     return feats
 
 
-def _lift_tracklets(model, c, feats, img_wh, run_tracklets_kwargs):
-    """``run_tracklets`` on the trimmed keypoints of ``c`` (``crop_tracklets``' dict) and features [sum n_i, 2048], 'frame_ids' added."""
+def _lift_tracklets(model, c, feats, img_wh, run_tracklets_kwargs, track_boxes=None):
+    """``run_tracklets`` on the trimmed keypoints of ``c`` (``crop_tracklets``' dict) and features [sum n_i, 2048], 'frame_ids' added -
+    and, with the tracker's untrimmed ``track_boxes`` per tracklet, 'track_boxes' (trimmed by the tracklet's span) and 'keypoints'."""
+    if track_boxes is not None and len(track_boxes) != len(c["keypoints"]):
+        raise ValueError(f"track_boxes: {len(track_boxes)} entries for {len(c['keypoints'])} tracklets")
     off = c["offsets"]
     outs = run_tracklets(model, [(c["keypoints"][i], feats[int(off[i]):int(off[i + 1])]) for i in range(len(off) - 1)], img_wh,
                          **run_tracklets_kwargs)
     for o, fid in zip(outs, c["frame_ids"]):
         o["frame_ids"] = fid
+    if track_boxes is not None:
+        for o, bx, kp, (a, b) in zip(outs, track_boxes, c["keypoints"], c["spans"]):
+            o["track_boxes"] = torch.as_tensor(bx).to(device=kp.device, dtype=torch.float64)[max(a, 0):b]
+            o["keypoints"] = kp
     return outs
 
 
@@ -649,14 +822,22 @@ def tracklet_draw_order(bbox_tops, frame_ids):
 
 
 @torch.no_grad()
-def render_tracklets(results, frames, img_wh, frame_ids=None, renderer=None, order: str = "reference", inplace: bool = False):
+def render_tracklets(results, frames, img_wh, frame_ids=None, renderer=None, order: str = "reference", inplace: bool = False,
+                     plain: bool = False, sideview: bool = False):
     """The demo's overlay video (main/run_demo.py:375-446) from ``run_tracklets``' outputs: results = list (or dict by person id) of dicts
     with 'mesh' [N_i,V,3], 'orig_cam' [N_i,4], 'bboxes' [N_i,4]; frames uint8 [F,H,W,3]; frame_ids = per tracklet the frame of each row
     (same container as results; None: the entry's own 'frame_ids', or rows 0..N_i-1).  renderer: a ``render.Renderer`` for ``img_wh``, or
     a face array to make one from.  The persons of a frame are drawn in ``frame_results``' order (``bbox[1]`` ascending, ties in tracklet
     order), each over the previous one (order "reference") or depth-tested against them ("depth").  Meshes, cameras and frames stay on
-    the device; the boxes' top edges (one number per row) are read back once to build the schedule.  -> the overlaid frames."""
+    the device; the boxes' top edges (one number per row) are read back once to build the schedule.  -> the overlaid frames.
+    ``plain`` (--render_plain, run_demo.py:396-397): the meshes are drawn on black instead of on the frames.  ``sideview`` (--sideview,
+    :399-422): -> uint8 [F,H,2W,3]; the left half is what the call returns without it, the right half the same jobs in the same order,
+    turned by ``render.axis_rotation(270, (0, 1, 0))`` and drawn on black (whether or not ``plain`` is set, as in the reference)."""
     from . import render as R
+    plain, sideview = _flag(plain, "plain"), _flag(sideview, "sideview")
+    if sideview and inplace:
+        raise ValueError("render_tracklets: inplace=True cannot be combined with sideview=True - the result is twice as wide as the "
+                         "frames, so it cannot be written into them")
     if renderer is None:
         raise _lib.PmceError("render_tracklets needs renderer=: a render.Renderer, or the mesh's face array (SMPL's faces are not shipped)")
     if not isinstance(renderer, R.Renderer):
@@ -665,6 +846,11 @@ def render_tracklets(results, frames, img_wh, frame_ids=None, renderer=None, ord
         raise _lib.PmceError(f"the renderer was made for {renderer.width} x {renderer.height}, img_wh is {tuple(img_wh)}")
     keys = list(results.keys()) if isinstance(results, dict) else list(range(len(results)))
     if not keys:
+        if plain or sideview:
+            if plain and inplace:
+                frames[...] = 0
+                return frames
+            return _empty_views(frames, plain, sideview)
         return frames if inplace else (frames.clone() if isinstance(frames, torch.Tensor) else np.array(frames))
     ids = []
     for k in keys:
@@ -676,4 +862,22 @@ def render_tracklets(results, frames, img_wh, frame_ids=None, renderer=None, ord
     cat = lambda name: torch.cat([torch.as_tensor(results[k][name]) for k in keys])  # noqa: E731
     tops = cat("bboxes")[:, 1].cpu().numpy()
     frame_index, draw = tracklet_draw_order([tops], ids)
-    return renderer.render(frames, cat("mesh"), cat("orig_cam"), frame_index=frame_index, order=order, inplace=inplace, draw_order=draw)
+    if not (plain or sideview):
+        return renderer.render(frames, cat("mesh"), cat("orig_cam"), frame_index=frame_index, order=order, inplace=inplace, draw_order=draw)
+    mesh, cams = cat("mesh"), cat("orig_cam")
+    on_device = isinstance(frames, torch.Tensor) and frames.is_cuda
+
+    def black():
+        return torch.zeros(frames.shape, dtype=torch.uint8, device=frames.device) if on_device else np.zeros(tuple(frames.shape), np.uint8)
+
+    if plain and inplace:
+        frames[...] = 0
+        base, into = frames, True
+    else:
+        base, into = (black(), on_device) if plain else (frames, False)       # a canvas of our own is drawn on in place
+    left = renderer.render(base, mesh, cams, frame_index=frame_index, order=order, inplace=into, draw_order=draw)
+    if not sideview:
+        return left
+    side = torch.from_numpy(R.axis_rotation(270, (0, 1, 0)).astype(np.float32))
+    right = renderer.render(black(), mesh, cams, frame_index=frame_index, rotation=side, order=order, inplace=on_device, draw_order=draw)
+    return torch.cat([left, right], 2) if isinstance(left, torch.Tensor) else np.concatenate([left, right], 2)

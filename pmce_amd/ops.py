@@ -767,3 +767,38 @@ def hmr_joints(joints, verts, sel, indptr, indices, data, cam, cam_stride, kp_3d
     _lib.check(_lib.load().pmce_hmr_joints_f32(P(joints), P(verts), P(sel), P(indptr), P(indices), P(data), C.c_void_p(cam.data_ptr()),
                                                int(cam_stride), n, K, V, P(kp_3d), P(kp_2d), _st()), "hmr_joints")
     return kp_3d, kp_2d
+
+
+def overlay_workspace_bytes(width, height, chunk_frames=1):
+    """Bytes of workspace pmce_draw_overlays needs to process ``chunk_frames`` frames per chunk (1 = the least it accepts)."""
+    b = int(_lib.load().pmce_overlay_workspace_bytes(int(width), int(height), int(chunk_frames)))
+    if b == 0:
+        raise _lib.PmceError(f"overlay_workspace_bytes: {_lib.last_error()}")
+    return b
+
+
+def draw_overlays(frames, frame_index_host, frame_index, boxes, box_format, ids, keypoints, skeleton, score_thresh, thickness, radius, label_scale, font,
+                  palette, text_color, alpha, status, workspace):
+    """pmce_draw_overlays on the current stream, in place on frames uint8 [F,H,W,3] (pmce_amd.overlay.draw prepares the tables):
+    frame_index int32 [N] (frame_index_host: the same table as an int32 numpy array when it is ascending, else None), boxes fp64 [N,4], ids int64 [N], keypoints fp64 [N,K,2 or 3], skeleton int32 [L,2], font uint8 [10,7] and
+    palette uint8 [P,3] on the device, text_color uint8 [3] on the host; box_format the C entry's code.  boxes, ids and keypoints may
+    be None."""
+    lib = _lib.load()
+    F, H, W, _ = frames.shape
+    assert frames.dtype == torch.uint8 and frame_index.dtype == torch.int32 and status.dtype == torch.int32
+    assert boxes is None or boxes.dtype == torch.float64
+    assert ids is None or ids.dtype == torch.int64
+    assert keypoints is None or keypoints.dtype == torch.float64
+    assert skeleton.dtype == torch.int32 and font.dtype == torch.uint8 and palette.dtype == torch.uint8
+    assert frame_index_host is None or (frame_index_host.dtype == np.int32 and frame_index_host.flags.c_contiguous and
+                                        frame_index_host.shape == tuple(frame_index.shape))
+    assert text_color.dtype == np.uint8 and text_color.shape == (3,) and text_color.flags.c_contiguous
+    K, D = (keypoints.shape[1], keypoints.shape[2]) if keypoints is not None else (0, 0)
+    _lib.check(lib.pmce_draw_overlays(P(frames), F, W, H,
+                                      None if frame_index_host is None else frame_index_host.ctypes.data_as(C.POINTER(C.c_int)),
+                                      P(frame_index), P(boxes), int(box_format), P(ids), P(keypoints), K, D,
+                                      P(skeleton) if skeleton.numel() else None, skeleton.shape[0], float(score_thresh), thickness, radius,
+                                      label_scale, P(font), P(palette), palette.shape[0], text_color.ctypes.data_as(C.POINTER(C.c_ubyte)),
+                                      alpha, frame_index.shape[0], P(status), C.c_void_p(workspace.data_ptr()), workspace.numel(), _st()),
+               "draw_overlays")
+    return frames

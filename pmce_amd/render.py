@@ -76,6 +76,24 @@ def schedule_layers(frame_index, n_frames: int, draw_order=None):
     return sched.astype(np.int32), offsets
 
 
+def axis_rotation(angle_deg, axis):
+    """The rotation by ``angle_deg`` degrees about ``axis`` -> fp64 [3,3]: cos I + (1 - cos) n n^T + sin [n]x with n = axis / |axis|, the
+    formula behind trimesh's ``rotation_matrix``, which the reference's renderer turns its side view with (demo/renderer.py:76-78:
+    angle 270 about (0, 1, 0)).  Every entry is those three terms summed in that order.  Cast to fp32 it is a ``Renderer.render``
+    ``rotation`` - which acts on the flipped mesh, as the reference's does."""
+    a = np.asarray(axis, dtype=np.float64)
+    if a.shape != (3,) or not np.isfinite(a).all() or not math.isfinite(float(angle_deg)):
+        raise PmceError(f"axis_rotation takes a finite angle and an axis of three finite numbers (got {angle_deg!r}, {axis!r})")
+    length = math.sqrt(float(a[0]) * float(a[0]) + float(a[1]) * float(a[1]) + float(a[2]) * float(a[2]))
+    if length == 0.0:
+        raise PmceError("axis_rotation: the axis has no direction")
+    n = [float(v) / length for v in a]
+    c, s = math.cos(math.radians(float(angle_deg))), math.sin(math.radians(float(angle_deg)))
+    cross = ((0.0, -n[2], n[1]), (n[2], 0.0, -n[0]), (-n[1], n[0], 0.0))
+    return np.array([[c * (1.0 if i == j else 0.0) + (1.0 - c) * n[i] * n[j] + s * cross[i][j] for j in range(3)] for i in range(3)],
+                    dtype=np.float64)
+
+
 def _host(x):
     return x.detach().cpu().numpy() if isinstance(x, torch.Tensor) else np.asarray(x)
 
