@@ -596,6 +596,36 @@ int pmce_smpl_forward_rotmat(const float* v_template_t, const float* dirs_t, con
                              const float* betas, int betas_stride, const float* trans, const int* sample_index, int n, float scale,
                              const float* offset, float* verts_out, float* joints_out, void* workspace, size_t workspace_bytes, int B,
                              int V, pmce_stream_t stream);
+/* The layer's inverse: the SMPL pose, shape and translation nearest to meshes of SMPL's topology (csrc/smpl_fit.hip; the reference has no
+ * such function, the algorithm is this project's and tests/smpl_fit_ref.py restates it).  On the GLOBAL rotations G_j the layer is
+ * linear, v = trans + J_0 + sum_j G_j m_j; a sweep updates G_0..G_23 in index order, each by an orthogonal Procrustes step on the
+ * current residual (3 x 3 SVD in fp64), then solves (betas, trans) by least squares through the 13 x 13 normal equations (fp64, Cholesky).
+ * One launch on `stream`, one workgroup per sample, no atomics, no synchronisation; a sample's result does not depend on the batch it
+ * is in.
+ *   model tables as for pmce_smpl_forward, and subtree_weights_t[24][V]: row c = the sum of weights_t over the subtree of c (c included);
+ *   verts[B][V][3]: the meshes, metres.  V in 1..pmce_smpl_fit_max_verts(): a sample's residual (12 V bytes) is kept in LDS;
+ *   init_rotmats[B][24][3][3] (local, row-major), init_betas[B][10], init_trans[B][3]: the start, each or NULL - the cold start is the
+ *     identity, zeros and mean(verts[b]) - mean(v_template);  fit_shape = 0 leaves the betas what they start as and solves trans alone;
+ *   n_sweeps >= 1;  sample_index[n] or NULL (then n == B) as for pmce_smpl_forward: the rows this call fits, in place;
+ *   rotmats[B][24][3][3] (local rotations), pose[B][72] (their axis-angle form by the rule of lib/geometry.py:84-249, as the HMR head's
+ *     theta), betas[B][10], trans[B][3], residual[B] = mean_v |verts - layer(rotmats, betas, trans)| after the last sweep,
+ *     history[B][n_sweeps] or NULL: the same after every sweep;
+ *   status[B] (int32): PMCE_SMPL_FIT_DEGENERATE_JOINT - some step met sigma_1 == 0, sigma_2 <= 1e-6 sigma_1 or a non-finite sum and kept
+ *     that joint's rotation; PMCE_SMPL_FIT_SINGULAR_SHAPE - a pivot of the factorisation was <= 0 or non-finite and that sweep kept
+ *     (betas, trans); PMCE_SMPL_FIT_NONFINITE - verts[b] holds a non-finite number: the row's results are the identity, zeros, zeros,
+ *     residual and history +inf;
+ *   workspace: 16-byte aligned device memory of at least pmce_smpl_fit_workspace_bytes(B, V) bytes (rows indexed by sample).
+ * The query returns 0 (and sets the error string) for B < 1 or V outside 1..pmce_smpl_fit_max_verts(). */
+#define PMCE_SMPL_FIT_DEGENERATE_JOINT 1
+#define PMCE_SMPL_FIT_SINGULAR_SHAPE 2
+#define PMCE_SMPL_FIT_NONFINITE 4
+int pmce_smpl_fit_max_verts(void);
+size_t pmce_smpl_fit_workspace_bytes(int B, int V);
+int pmce_smpl_fit(const float* v_template_t, const float* dirs_t, const float* weights_t, const float* subtree_weights_t,
+                  const float* j_template, const float* j_shapedirs, const int* parents_host, int n_joints, const float* verts,
+                  const float* init_rotmats, const float* init_betas, const float* init_trans, const int* sample_index, int n,
+                  int n_sweeps, int fit_shape, float* rotmats, float* pose, float* betas, float* trans, float* residual, int* status,
+                  float* history, void* workspace, size_t workspace_bytes, int B, int V, pmce_stream_t stream);
 
 /* ---------------------------------------------------------------------------------------------------------
  * The demo's person crops (lib/utils/_dataset_demo.py:29-75 CropDataset) from frames that are already on the device.

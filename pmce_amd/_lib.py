@@ -128,6 +128,10 @@ PROTOTYPES = {
                           _i, _i, _s],
     "pmce_smpl_forward_rotmat": [_f, _f, _f, _f, _f, C.POINTER(C.c_int), _i, _f, _f, _i, _f, _f, _i, _fl, _f, _f, _f, C.c_void_p,
                                  C.c_size_t, _i, _i, _s],
+    "pmce_smpl_fit_max_verts": [],
+    "pmce_smpl_fit_workspace_bytes": [_i, _i],
+    "pmce_smpl_fit": [_f, _f, _f, _f, _f, _f, C.POINTER(C.c_int), _i, _f, _f, _f, _f, _f, _i, _i, _i, _f, _f, _f, _f, _f, _f, _f, C.c_void_p,
+                      C.c_size_t, _i, _i, _s],
     "pmce_crop_boxes": [_f, _i, _i, _d, _f, _f, _f, _s],
     "pmce_crop_patches": [_f, _i, _i, _i, C.POINTER(C.c_int), _f, _f, _i, _d, _i, _i, _f, _f, _f, _f, _s],
     "pmce_pose_patches": [_f, _i, _i, _i, C.POINTER(C.c_int), _f, _f, _i, _i, _d, _i, _i, _i, _i, _f, _f, _f, _f, _f, _s],
@@ -228,6 +232,7 @@ _RESTYPES = {
     "pmce_vertex_sab_scratch_floats": C.c_longlong,
     "pmce_render_workspace_bytes": C.c_size_t,
     "pmce_smpl_workspace_bytes": C.c_size_t,
+    "pmce_smpl_fit_workspace_bytes": C.c_size_t,
     "pmce_conv_packed_floats": C.c_longlong,
     "pmce_gemm_packed_f16_halves": C.c_longlong,
     "pmce_extractor_destroy": None,

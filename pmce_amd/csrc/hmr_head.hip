@@ -27,6 +27,7 @@
 // microseconds on the vector pipe, next to a backbone of seconds; the split would need a pass that pre-splits the features, M = 157 is
 // no multiple of its tiles, and its products are not exact fp32 products, which the identity property above needs.
 #include "common.hpp"
+#include "rotation.hpp"
 
 namespace {
 
@@ -59,34 +60,7 @@ __device__ __forceinline__ void rot6d_rotmat_aa(const float* x, float* R, float*
   R[0] = b1x, R[1] = b2x, R[2] = b3x;
   R[3] = b1y, R[4] = b2y, R[5] = b3y;
   R[6] = b1z, R[7] = b2z, R[8] = b3z;
-  // geometry.py:169-249, on the transpose the reference takes: rmat_t[i][j] = R[j][i]
-  const float R00 = R[0], R01 = R[1], R02 = R[2], R10 = R[3], R11 = R[4], R12 = R[5], R20 = R[6], R21 = R[7], R22 = R[8];
-  const bool d2 = R22 < 1e-6f, d0_d1 = R00 > R11, d0_nd1 = R00 < -R11;
-  float q0, q1, q2, q3, t;
-  if (d2 && d0_d1) {
-    t = 1.0f + R00 - R11 - R22;
-    q0 = R21 - R12, q1 = t, q2 = R10 + R01, q3 = R02 + R20;
-  } else if (d2) {
-    t = 1.0f - R00 + R11 - R22;
-    q0 = R02 - R20, q1 = R10 + R01, q2 = t, q3 = R21 + R12;
-  } else if (d0_nd1) {
-    t = 1.0f - R00 - R11 + R22;
-    q0 = R10 - R01, q1 = R02 + R20, q2 = R21 + R12, q3 = t;
-  } else {
-    t = 1.0f + R00 + R11 + R22;
-    q0 = t, q1 = R21 - R12, q2 = R02 - R20, q3 = R10 - R01;
-  }
-  const float rt = sqrtf(t);  // (t < 0: NaN, t = 0: a division by zero - both as in the reference, and NaN becomes 0 below)
-  q0 = q0 / rt * 0.5f, q1 = q1 / rt * 0.5f, q2 = q2 / rt * 0.5f, q3 = q3 / rt * 0.5f;
-  // geometry.py:146-166
-  const float s2 = q1 * q1 + q2 * q2 + q3 * q3;
-  const float sn = sqrtf(s2);
-  const float two_theta = 2.0f * (q0 < 0.0f ? atan2f(-sn, -q0) : atan2f(sn, q0));
-  const float k = s2 > 0.0f ? two_theta / sn : 2.0f;
-  const float ax = q1 * k, ay = q2 * k, az = q3 * k;
-  aa[0] = ax != ax ? 0.0f : ax;  // :112, aa[isnan(aa)] = 0
-  aa[1] = ay != ay ? 0.0f : ay;
-  aa[2] = az != az ? 0.0f : az;
+  rotmat_to_angle_axis(R, aa);  // geometry.py:169-249 + :146-166 (rotation.hpp)
 }
 
 __global__ __launch_bounds__(HMR_NT) void hmr_head_kernel(const float* __restrict__ features, const float* __restrict__ q_t,

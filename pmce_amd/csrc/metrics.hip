@@ -4,67 +4,9 @@
 // :218-245 compute_error_accel).  The mesh part is a 165 KB/sample streaming reduction (HBM-bound); the 14-joint
 // Procrustes alignment (3x3 SVD by one-sided Jacobi) runs in fp64 on one lane per sample.
 #include "common.hpp"
+#include "rotation.hpp"  // jacobi_svd3, normalise3, any_orthogonal3, cross3
 
 #define MAXJ 32
-
-// SVD of a 3x3 matrix by one-sided (Hestenes) Jacobi in fp64: the columns of A = H*V are rotated in pairs until they are mutually
-// orthogonal; their norms are then the singular values and V holds the right singular vectors.  H itself is worked on, never H^T H:
-// squaring H squares its condition number and leaves a small singular value known only to sqrt(eps) of the largest, which is what a
-// thin, planar or collinear joint set (in a plane that is not axis-aligned) needs to be resolved.  On return A[:,c] = H V[:,c].
-__device__ void jacobi_svd3(double A[3][3], double V[3][3]) {
-  for (int i = 0; i < 3; ++i)
-    for (int j = 0; j < 3; ++j) V[i][j] = (i == j) ? 1.0 : 0.0;
-  for (int sweep = 0; sweep < 30; ++sweep) {
-    bool rotated = false;
-    for (int p = 0; p < 2; ++p)
-      for (int q = p + 1; q < 3; ++q) {
-        double al = 0.0, be = 0.0, ga = 0.0;
-        for (int k = 0; k < 3; ++k) {
-          al += A[k][p] * A[k][p];
-          be += A[k][q] * A[k][q];
-          ga += A[k][p] * A[k][q];
-        }
-        if (!(ga * ga > 1e-30 * al * be)) continue;  // columns orthogonal to 1e-15 (or one of them zero, or NaN): nothing to do
-        rotated = true;
-        const double zeta = (be - al) / (2.0 * ga);
-        const double t = (zeta >= 0 ? 1.0 : -1.0) / (fabs(zeta) + sqrt(zeta * zeta + 1.0));
-        const double c = 1.0 / sqrt(t * t + 1.0), s = t * c;
-        for (int k = 0; k < 3; ++k) {  // A <- A J
-          const double akp = A[k][p], akq = A[k][q];
-          A[k][p] = c * akp - s * akq;
-          A[k][q] = s * akp + c * akq;
-        }
-        for (int k = 0; k < 3; ++k) {  // V <- V J
-          const double vkp = V[k][p], vkq = V[k][q];
-          V[k][p] = c * vkp - s * vkq;
-          V[k][q] = s * vkp + c * vkq;
-        }
-      }
-    if (!rotated) break;
-  }
-}
-
-// a <- a / |a|; false (a untouched) when |a|^2 is not above floor2, i.e. a is zero, rounding noise or NaN
-__device__ bool normalise3(double a[3], double floor2) {
-  const double n2 = a[0] * a[0] + a[1] * a[1] + a[2] * a[2];
-  if (!(n2 > floor2)) return false;
-  const double inv = 1.0 / sqrt(n2);
-  for (int k = 0; k < 3; ++k) a[k] *= inv;
-  return true;
-}
-
-// r <- the coordinate axis that is furthest from the unit vector u, made orthogonal to u and normalised
-__device__ void any_orthogonal3(const double u[3], double r[3]) {
-  const int k = (fabs(u[0]) <= fabs(u[1]) && fabs(u[0]) <= fabs(u[2])) ? 0 : (fabs(u[1]) <= fabs(u[2]) ? 1 : 2);
-  for (int i = 0; i < 3; ++i) r[i] = (i == k ? 1.0 : 0.0) - u[k] * u[i];
-  normalise3(r, 0.0);
-}
-
-__device__ void cross3(const double a[3], const double b[3], double c[3]) {
-  c[0] = a[1] * b[2] - a[2] * b[1];
-  c[1] = a[2] * b[0] - a[0] * b[2];
-  c[2] = a[0] * b[1] - a[1] * b[0];
-}
 
 // PA-MPJPE of one sample: mean_j || c R P_j + t - G_j || with the similarity (c, R, t) of rigid_transform_3D (coord_utils.py:151-167).
 // H = U diag(s) V^T, R = V U^T.  U and V are built as right-handed frames (third column = cross product of the first two), so R is a

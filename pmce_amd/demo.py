@@ -649,21 +649,75 @@ def _person_ids(results):
     return keys, [int(results[k].get("person_id", k)) for k in keys]
 
 
-def save_results(pkl_path, outs):
+SMPL_KEYS = ("smpl_pose", "smpl_betas", "smpl_trans", "smpl_residual", "smpl_status")
+
+
+@torch.no_grad()
+def fit_tracklets(outs, layer, gender=None, shape: str = "frame", n_sweeps: int = 10):
+    """SMPL parameters for the meshes of ``run_frames``' dicts (a list, or a dict by person id; 'mesh' [N_i,V,3] device tensors in metres,
+    V the vertex count of `layer`, a ``smpl.SMPL``): adds 'smpl_pose' [N_i,72] axis-angle, 'smpl_betas' [N_i,10], 'smpl_trans' [N_i,3],
+    'smpl_residual' [N_i] (mean vertex distance of the fitted body to the mesh, metres) and 'smpl_status' [N_i] (``smpl.STATUS_*`` bits)
+    to every dict, from ONE ``layer.fit`` call over all rows of all tracklets.  gender: one name for all rows, or one per tracklet.
+    shape='frame': every row has its own betas.  shape='tracklet': a person has one body - the rows are fitted free, each tracklet's
+    betas are averaged on the device, and the rows are fitted again with the shape fixed at that mean, warm-started from the first
+    pass; 'smpl_betas' then repeats the mean.  -> outs."""
+    if shape not in ("frame", "tracklet"):
+        raise ValueError(f"shape must be 'frame' or 'tracklet' (got {shape!r})")
+    keys = list(outs.keys()) if isinstance(outs, dict) else list(range(len(outs)))
+    if not keys:
+        return outs
+    meshes = [outs[k]["mesh"] for k in keys]
+    for k, m in zip(keys, meshes):
+        if not isinstance(m, torch.Tensor) or not m.is_cuda:
+            raise ValueError(f"tracklet {k!r}: 'mesh' must be a device tensor")
+    lengths = [int(m.shape[0]) for m in meshes]
+    verts = torch.cat([m.to(torch.float32) for m in meshes], 0)
+    if gender is not None and not isinstance(gender, str):
+        if len(gender) != len(keys):
+            raise ValueError(f"gender holds {len(gender)} entries for {len(keys)} tracklets")
+        gender = [g for g, n in zip(gender, lengths) for _ in range(n)]
+    if verts.shape[0] == 0:
+        fitted = None
+    else:
+        rotmats, pose, betas, trans, residual, status = layer.fit(verts, gender, n_sweeps=n_sweeps)
+        if shape == "tracklet":
+            owner = torch.repeat_interleave(torch.arange(len(keys), device=verts.device),
+                                            torch.tensor(lengths, device=verts.device), output_size=verts.shape[0])
+            mean = torch.zeros(len(keys), betas.shape[1], device=verts.device, dtype=torch.float32).index_add_(0, owner, betas)
+            mean = mean / torch.tensor(lengths, device=verts.device, dtype=torch.float32).clamp(min=1)[:, None]
+            first = status
+            rotmats, pose, betas, trans, residual, status = layer.fit(verts, gender, n_sweeps=n_sweeps, fit_shape=False,
+                                                                      init=(rotmats, betas, trans), betas=mean[owner].contiguous())
+            status = status | first
+        fitted = (pose, betas, trans, residual, status)
+    a = 0
+    for k, n in zip(keys, lengths):
+        for name, t in zip(SMPL_KEYS, fitted if fitted is not None else [None] * len(SMPL_KEYS)):
+            outs[k][name] = t[a:a + n] if t is not None else torch.empty(0)
+        a += n
+    return outs
+
+
+def save_results(pkl_path, outs, smpl: bool = False):
     """--save_pkl (main/run_demo.py:360-373): ``run_frames``' dicts (a list, or a dict by person id) -> a pickle of {person_id:
     {'pred_cam' [N,3], 'mesh' [N,6890,3], 'bboxes' [N,4], 'frame_ids' [N]}} as numpy arrays - the reference's keys.  Written with the
     standard ``pickle`` module; the reference writes with joblib, and reading this file with ``joblib.load`` has not been checked.
-    -> the dict written."""
+    smpl=True (not in the reference; the dicts have been through ``fit_tracklets``) adds 'pose' [N,72], 'betas' [N,10], 'trans' [N,3],
+    'smpl_residual' [N] and 'smpl_status' [N].  -> the dict written."""
     import os
     import pickle
     keys, pids = _person_ids(outs)
     if len(set(pids)) != len(pids):
         raise ValueError(f"save_results: person ids repeat ({pids})")
+    names = {name: name for name in ("pred_cam", "mesh", "bboxes", "frame_ids")}
+    if _flag(smpl, "smpl"):
+        names.update({"smpl_pose": "pose", "smpl_betas": "betas", "smpl_trans": "trans", "smpl_residual": "smpl_residual",
+                      "smpl_status": "smpl_status"})
     data = {}
     for k, pid in zip(keys, pids):
         o = outs[k]
-        data[pid] = {name: np.asarray(o[name].detach().cpu().numpy() if isinstance(o[name], torch.Tensor) else o[name])
-                     for name in ("pred_cam", "mesh", "bboxes", "frame_ids")}
+        data[pid] = {out: np.asarray(o[name].detach().cpu().numpy() if isinstance(o[name], torch.Tensor) else o[name])
+                     for name, out in names.items()}
     folder = os.path.dirname(os.path.abspath(os.fspath(pkl_path)))
     os.makedirs(folder, exist_ok=True)
     with open(pkl_path, "wb") as fh:

@@ -751,6 +751,36 @@ def smpl_forward_rotmat(model, rotmats, betas, trans, sample_index, scale, offse
     return verts_out, joints_out
 
 
+def smpl_fit_workspace_bytes(B, V):
+    """Bytes of workspace pmce_smpl_fit needs for B meshes of V vertices; raises where V is more than a workgroup's LDS holds."""
+    b = int(_lib.load().pmce_smpl_fit_workspace_bytes(int(B), int(V)))
+    if b == 0:
+        raise _lib.PmceError(f"smpl_fit_workspace_bytes: {_lib.last_error()}")
+    return b
+
+
+def smpl_fit(model, verts, init_rotmats, init_betas, init_trans, sample_index, n_sweeps, fit_shape, rotmats, pose, betas, trans, residual,
+             status, history, workspace):
+    """pmce_smpl_fit on the current stream, in place on rotmats [B,24,3,3], pose [B,72], betas [B,10], trans [B,3], residual [B], status
+    [B] int32 and history [B,n_sweeps] or None (pmce_amd.smpl.SMPL.fit prepares the arguments: `model` a smpl.SMPLModel, verts [B,V,3]
+    contiguous fp32, the three init tensors contiguous or None, sample_index an int32 device tensor of the rows to fit or None)."""
+    lib = _lib.load()
+    B, V = verts.shape[0], verts.shape[1]
+    vt, dirs, wts, jt, jsd = model.to(verts.device)
+    sub = model.subtree_to(verts.device)
+    if vt.shape[1] != V:
+        raise _lib.PmceError(f"smpl_fit: the model has {vt.shape[1]} vertices, verts {V}")
+    par = np.ascontiguousarray(model.parents, dtype=np.int32)
+    assert verts.dtype == torch.float32 and verts.is_contiguous() and status.dtype == torch.int32
+    if sample_index is not None:
+        assert sample_index.dtype == torch.int32
+    n = B if sample_index is None else int(sample_index.numel())
+    _lib.check(lib.pmce_smpl_fit(P(vt), P(dirs), P(wts), P(sub), P(jt), P(jsd), par.ctypes.data_as(C.POINTER(C.c_int)), len(par), P(verts),
+                                 P(init_rotmats), P(init_betas), P(init_trans), P(sample_index), n, int(n_sweeps), 1 if fit_shape else 0,
+                                 P(rotmats), P(pose), P(betas), P(trans), P(residual), P(status), P(history),
+                                 C.c_void_p(workspace.data_ptr()), workspace.numel() * workspace.element_size(), B, V, _st()), "smpl_fit")
+
+
 def hmr_head(features, q_t, cst, pmi_t, init, state, rotmat, theta):
     """pmce_hmr_head_f32 on the current stream: features [n,2048], q_t [2048,160], cst [157], pmi_t [157,160] = (P - I)^T + init [n,157] or
     None + None -> state [n,157], rotmat [n,24,3,3], theta [n,85], written in place."""

@@ -24,6 +24,8 @@ from ._lib import PmceError
 
 N_JOINTS, N_SHAPE, N_POSE = 24, 10, 207
 K_PAD = 220                                  # the 217 blend rows padded to a multiple of four (csrc/smpl.hip)
+# bits of ``SMPL.fit``'s status (include/pmce_hip.h, PMCE_SMPL_FIT_*)
+STATUS_DEGENERATE_JOINT, STATUS_SINGULAR_SHAPE, STATUS_NONFINITE = 1, 2, 4
 NPZ_NAMES = ("v_template", "shapedirs", "posedirs", "weights", "J_regressor", "kintree_table", "f")
 # the reference's three files (smplpytorch/pytorch/smpl_layer.py:30-35)
 MODEL_FILES = {"neutral": "basicModel_neutral_lbs_10_207_0_v1.0.0", "female": "basicModel_f_lbs_10_207_0_v1.0.0",
@@ -59,16 +61,29 @@ def pack_tables(v_template, shapedirs, posedirs, weights, J_regressor, dtype=np.
     return c(vt.T), dirs, c(w.T), c(jr @ vt), c(np.einsum("jv,vck->jck", jr, sd))
 
 
+def subtree_weights(weights, parents, dtype=np.float32):
+    """[24, V]: row c holds, per vertex, the sum of the skinning weights of c and of every joint below it in the tree - what the whole
+    subtree of c moves a vertex by (``SMPL.fit``'s linear form).  `weights` [V,24]; `parents`: entry i > 0 in [0, i).  Summed in fp64,
+    children into parents from the last joint up, rounded once to `dtype`; laid out like ``weights_t``."""
+    W = _dense(weights).T.copy()
+    for k in range(N_JOINTS - 1, 0, -1):
+        W[int(parents[k])] += W[k]
+    return np.ascontiguousarray(W, dtype=dtype)
+
+
 class SMPLModel:
     """One gender's model, packed for the kernels (host arrays; ``.to(device)`` uploads them once per device)."""
 
-    def __init__(self, tables, parents, faces, root_row):
+    def __init__(self, tables, parents, faces, root_row, subtree_weights_t=None):
         self.v_template_t, self.dirs_t, self.weights_t, self.j_template, self.j_shapedirs = tables
+        # (from the packed weights when not given: the same numbers the kernels skin with)
+        self.subtree_weights_t = subtree_weights_t if subtree_weights_t is not None else subtree_weights(self.weights_t.T, parents)
         self.parents = parents
         self.faces = faces
         self._root_row = root_row
         self.n_verts = int(self.v_template_t.shape[1])
         self._dev = {}
+        self._dev_subtree = {}
 
     @classmethod
     def from_arrays(cls, v_template, shapedirs, posedirs, weights, J_regressor, parents, faces=None):
@@ -89,7 +104,8 @@ class SMPLModel:
                 raise PmceError(f"faces must be [F, 3] (got {f.shape})")
             f = np.ascontiguousarray(f.astype(np.int32))
         root_row = _dense(J_regressor)[0].astype(np.float32)
-        return cls(pack_tables(v_template, shapedirs, posedirs, weights, J_regressor), par.astype(np.int32), f, root_row)
+        tables = pack_tables(v_template, shapedirs, posedirs, weights, J_regressor)
+        return cls(tables, par.astype(np.int32), f, root_row, subtree_weights(tables[2].T, par))
 
     def to(self, device):
         """The model's tables on `device` (cached)."""
@@ -99,6 +115,14 @@ class SMPLModel:
             self._dev[dev] = tuple(torch.from_numpy(a).to(dev) for a in (self.v_template_t, self.dirs_t, self.weights_t, self.j_template,
                                                                         self.j_shapedirs))
         return self._dev[dev]
+
+    def subtree_to(self, device):
+        """``subtree_weights_t`` on `device` (cached; uploaded only for a model that ``SMPL.fit`` is called on)."""
+        import torch
+        dev = torch.device(device)
+        if dev not in self._dev_subtree:
+            self._dev_subtree[dev] = torch.from_numpy(self.subtree_weights_t).to(dev)
+        return self._dev_subtree[dev]
 
 
 def _from_mapping(d, where):
@@ -289,5 +313,58 @@ class SMPL:
             for g, index in groups:
                 ops.smpl_forward_rotmat(self.models[g], rotmats, shape, trans, index, float(scale), offset, verts, joints, ws)
         return verts, joints
+
+    def fit(self, verts, gender=None, n_sweeps=10, fit_shape=True, init=None, betas=None, return_history=False):
+        """The layer's inverse (csrc/smpl_fit.hip): verts [B,V,3] fp32 on the device, meshes of SMPL's topology in metres ->
+        (rotmats [B,24,3,3] local, pose [B,72] their axis-angle form, betas [B,10], trans [B,3], residual [B], status [B] int32), and
+        history [B,n_sweeps] last with return_history=True.  ``forward_rotmat(rotmats, betas, trans)`` is the fitted body, residual its
+        mean vertex distance to `verts` (history: the same after every sweep), status a set of ``STATUS_*`` bits (0: nothing to report).
+        One launch per gender present on the current stream, no host wait; a row's result does not depend on the batch.
+
+        A sweep updates the 24 global rotations one after the other, each by a closed-form Procrustes step on the current residual,
+        then solves shape and translation by least squares; the residual does not rise from sweep to sweep on SMPL-shaped inputs.
+        n_sweeps=10 is PROVISIONAL: on the synthetic models of the tests 12 cold-start sweeps bring an exact SMPL mesh below 0.1 mm, and no
+        real SMPL body has been fitted (the model files are licensed and were not at hand).
+        init=(rotmats, betas, trans) warm-starts, e.g. from the previous frame; without it the start is the rest pose at the mesh's mean.
+        fit_shape=False keeps the shape at what it starts as - `betas` [B,10] if given, else init's, else zeros - and fits pose and
+        translation only; `betas` with fit_shape=True is the shape's starting point.  gender as in ``forward``.
+        A row with a non-finite vertex returns (identity, 0, 0, 0, +inf, STATUS_NONFINITE)."""
+        import torch
+        from . import ops
+        if not isinstance(verts, torch.Tensor) or not verts.is_cuda or verts.dtype != torch.float32 or verts.dim() != 3 or \
+                verts.shape[0] < 1 or tuple(verts.shape[1:]) != (self.n_verts, 3):
+            raise PmceError(f"verts must be a float32 device tensor [B >= 1, {self.n_verts}, 3] (got {getattr(verts, 'dtype', None)} "
+                            f"{tuple(getattr(verts, 'shape', ()))})")
+        if int(n_sweeps) < 1:
+            raise PmceError(f"n_sweeps must be >= 1 (got {n_sweeps})")
+        dev, B = verts.device, verts.shape[0]
+        verts = verts.contiguous()
+
+        def start(a, tail, name):
+            if a is None:
+                return None
+            if not isinstance(a, torch.Tensor) or a.device != dev or a.dtype != torch.float32 or tuple(a.shape) != (B,) + tail:
+                raise PmceError(f"{name} must be a float32 tensor {[B, *tail]} on {dev} (got {tuple(getattr(a, 'shape', ()))})")
+            return a.contiguous()
+
+        if init is not None and len(init) != 3:
+            raise PmceError("init must be (rotmats, betas, trans)")
+        r0, b0, t0 = init if init is not None else (None, None, None)
+        r0, b0, t0 = start(r0, (N_JOINTS, 3, 3), "init rotmats"), start(b0, (N_SHAPE,), "init betas"), start(t0, (3,), "init trans")
+        if betas is not None:
+            b0 = start(betas, (N_SHAPE,), "betas")
+        with torch.cuda.device(dev):
+            groups = self._gender_groups(gender, B, dev)
+            f32 = dict(device=dev, dtype=torch.float32)
+            rotmats, pose = torch.empty(B, N_JOINTS, 3, 3, **f32), torch.empty(B, 3 * N_JOINTS, **f32)
+            out_betas, trans, residual = torch.empty(B, N_SHAPE, **f32), torch.empty(B, 3, **f32), torch.empty(B, **f32)
+            status = torch.empty(B, device=dev, dtype=torch.int32)
+            history = torch.empty(B, int(n_sweeps), **f32) if return_history else None
+            ws = torch.empty(ops.smpl_fit_workspace_bytes(B, self.n_verts), device=dev, dtype=torch.uint8)
+            for g, index in groups:
+                ops.smpl_fit(self.models[g], verts, r0, b0, t0, index, int(n_sweeps), bool(fit_shape), rotmats, pose, out_betas, trans,
+                             residual, status, history, ws)
+        out = (rotmats, pose, out_betas, trans, residual, status)
+        return out + (history,) if return_history else out
 
     __call__ = forward
